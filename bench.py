@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode throughput benchmark (BASELINE.json metric) for the MI355X engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model llama3-8b]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model llama3-8b] [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[2]/[3]): Llama-3-8B bf16 with
 synthetic weights (seed 0; no checkpoint exists offline), 32 concurrent
@@ -18,8 +18,24 @@ over xGMI and the sampled token ids go back from the last stage to stage 0
 (llama-p2p_amd/pipeline.py).  Per-GPU work is fixed as N grows (weak scaling).
 
 Output: one JSON line (rank 0) with value = total decode tokens/s over all
-GPUs, the dominant kernel's roofline (HIP-event timed, same stream) and the CPU
-oracle timed on this host's cores (N = 1 only).
+GPUs and ms_per_step = the milliseconds one timed step took.  A plain run at
+N = 1 does only that: set-up, warm-up, the K timed steps, the line.  K is not
+bounded by n_ctx at N = 1: when the longest sequence reaches n_ctx the batch is
+re-armed at the prompts' ends (untimed) and decodes the same tokens again.
+
+--full (N = 1) adds every other measurement to the line: the dominant kernel's
+roofline (HIP-event timed, same stream), batch-1 decode, batched prefill, the
+serving path, the CPU oracle timed on this host's cores, TinyLlama, the HBM
+probe, the quantised models, Llama-3-70B and the Llama-2-7B geometry.  The
+per-section flags (--batch1-steps, --q8-steps, --no-cpu-baseline, ...) select
+among these and mean nothing without --full.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path handed to
+its caller as float32 .npy files: DIR/tokens.npy, the greedy token ids of every
+sequence for every step (warm-up steps included; [sequences, W + K], or
+[micro-batches, sequences, W + K] on the pipeline path), and DIR/last_step.npy,
+its last column (the K-th timed step).  Weights, prompts and decoding are
+seeded, so two runs with the same arguments start from identical inputs.
 """
 from __future__ import annotations
 
@@ -55,6 +71,17 @@ def measured_traffic(label: str):
         return json.load(open(path)).get(label)
     except (OSError, ValueError):
         return None
+
+
+def dump_outputs(out_dir: str, toks):
+    """--dump-outputs: the token ids the timed batch returned ([..., sequences, warm-up + timed steps],
+    ids < 2^24 are exact in float32) and the last timed step's column."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    toks = np.asarray(toks, dtype=np.float32)
+    np.save(os.path.join(out_dir, "tokens.npy"), toks)
+    np.save(os.path.join(out_dir, "last_step.npy"), np.ascontiguousarray(toks[..., -1]))
 
 
 def tiny_prompt(vocab: int = 32000):
@@ -128,24 +155,54 @@ def run_single(args):
         pos += list(range(len(p) - 1))
         ids += [int(t) for t in p[:-1]]
     eng.forward_rows(slots, pos, ids, want_logits=False)  # GEMM prefill chunks
-    b = eng.batch(slots=list(range(M)), pos=[len(p) - 1 for p in prompts], ids=[int(p[-1]) for p in prompts],
-                  max_steps=args.warmup + args.steps)
-    for _ in range(args.warmup):
-        b.step()
-    eng.sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        b.step()
-    eng.sync()
-    dt = time.perf_counter() - t0
-    toks = b.tokens()
-    assert toks.shape[1] == args.warmup + args.steps
+    pos0, ids0 = [len(p) - 1 for p in prompts], [int(p[-1]) for p in prompts]
+    total = args.warmup + args.steps
+    # the longest sequence reaches n_ctx after `cycle` steps.  A longer run re-arms the batch there
+    # (untimed: same prompts, positions and graphs; the decode overwrites its own K/V) and goes on, so
+    # any --steps works and every step decodes at a context between the prompts' lengths and n_ctx
+    cycle = args.n_ctx - max(pos0)
+    if cycle < 1:
+        raise ValueError(f"n_ctx {args.n_ctx} leaves no room to decode after a {max(pos0) + 1}-token prompt")
+    b = eng.batch(slots=list(range(M)), pos=pos0, ids=ids0, max_steps=min(total, cycle))
+    in_cycle, hist = 0, []
+
+    def steps(n):
+        """n decode steps; the seconds they took (host clock around work that ends in a synchronise)."""
+        nonlocal in_cycle
+        done, dt = 0, 0.0
+        while done < n:
+            if in_cycle == cycle:
+                hist.append(b.tokens())
+                b.reset(pos0, ids0)
+                in_cycle = 0
+            m = min(n - done, cycle - in_cycle)
+            eng.sync()
+            t0 = time.perf_counter()
+            for _ in range(m):
+                b.step()
+            eng.sync()
+            dt += time.perf_counter() - t0
+            done, in_cycle = done + m, in_cycle + m
+        return dt
+
+    steps(args.warmup)
+    dt = steps(args.steps)
+    toks = np.concatenate(hist + [b.tokens()], axis=1)
+    assert toks.shape[1] == total
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, toks)
     # algorithmic bytes per decode step (SURVEY §8d): weights + KV read/write + logits
-    ctx_sum = sum(len(p) + args.warmup + args.steps / 2 for p in prompts)
+    # (mean context over the timed steps: without a re-arm, prompt + warm-up + steps / 2)
+    mean_off = sum(k % cycle for k in range(args.warmup, total)) / max(1, args.steps) + 0.5
+    ctx_sum = sum(len(p) + mean_off for p in prompts)
     step_bytes = eng.info.weight_bytes + ctx_sum * shape.kv_bytes_per_pos() + M * shape.kv_bytes_per_pos() + \
         M * shape.n_vocab * 4
     res = {"tok_s": M * args.steps / dt, "ms_per_step": dt * 1e3 / args.steps,
            "step_gbs": step_bytes / (dt / args.steps) / 1e9, "step_bytes": step_bytes}
+    if not args.full:
+        b.close()
+        eng.close()
+        return res
     # dominant kernel: ffn gate/up (fused, 2 x n_ff x n_embd bf16 per layer) -- HIP events on the engine stream
     us, wbytes = eng.profile_kernel(2, M, iters=3)
     kbytes = wbytes + M * shape.n_embd * 2 + M * shape.n_ff * 2  # weights + activations in/out
@@ -159,8 +216,9 @@ def run_single(args):
                        "bytes_per_launch": int(kbytes)}
     # batch-1 decode (the north_star's 70% target), same engine
     if args.batch1_steps > 0:
-        b1 = eng.batch(slots=[0], pos=[len(prompts[0]) - 1 + args.warmup + args.steps], ids=[int(toks[0, -1])],
-                       max_steps=args.batch1_steps + 4)
+        # continues sequence 0 where the run above left it (or, that close to n_ctx, as far back as its steps need)
+        b1 = eng.batch(slots=[0], pos=[max(0, min(pos0[0] + in_cycle, args.n_ctx - args.batch1_steps - 4))],
+                       ids=[int(toks[0, -1])], max_steps=args.batch1_steps + 4)
         for _ in range(4):
             b1.step()
         eng.sync()
@@ -582,6 +640,11 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default="llama3-8b")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement (roofline, batch 1, prefill, serving, CPU baseline, "
+                         "other models and precisions); without it only the headline decode is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the token ids the timed steps produced to DIR/tokens.npy and DIR/last_step.npy (float32)")
     ap.add_argument("--seqs", type=int, default=MB_SEQS, help="sequences per micro-batch")
     ap.add_argument("--n-ctx", type=int, default=512)
     ap.add_argument("--batch1-steps", type=int, default=32)
@@ -646,8 +709,11 @@ def main():
                                f"(seed 2), n_ctx {args.n_ctx}", "model": args.model, "stages": 1,
                    "micro_batches": 1, "seqs_per_micro_batch": args.seqs, "parallelism": "pp1"},
         "step_hbm_gbs": round(res["step_gbs"], 1), "step_hbm_frac": round(res["step_gbs"] / HBM_PEAK_GBS, 4),
-        "roofline": res["roofline"],
     }
+    if not args.full:  # the plain run: the headline decode alone
+        print(json.dumps(line), flush=True)
+        return
+    line["roofline"] = res["roofline"]
     for k in ("batch1", "prefill"):
         if k in res:
             line[k] = res[k]

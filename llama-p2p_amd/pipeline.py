@@ -387,6 +387,11 @@ def bench_main(args, metric: str, make_prompts):
     crc = zlib.crc32(np.ascontiguousarray(np.stack(toks).astype(np.int32)).tobytes()) if toks is not None else None
     if toks is not None and os.environ.get("MX_TOKENS_DUMP"):  # diagnosis: [S][M][steps] token ids
         np.save(os.environ["MX_TOKENS_DUMP"], np.stack(toks).astype(np.int32))
+    if toks is not None and getattr(args, "dump_outputs", None):  # bench.py --dump-outputs (last stage writes)
+        out = np.stack(toks).astype(np.float32)  # [S][M][warm-up + steps]; ids < 2^24 are exact in float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), out)
+        np.save(os.path.join(args.dump_outputs, "last_step.npy"), np.ascontiguousarray(out[..., -1]))
     if world > 1 and stage.last:
         comm.send_obj(crc, 0)
     elif world > 1 and rank == 0:

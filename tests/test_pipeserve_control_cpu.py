@@ -46,12 +46,16 @@ class SlowLane(ToyLane):
         super().step_tensors(x_in, x_out)
 
 
-WAVE1 = [(list(range(3 + i, 9 + i)), 36) for i in range(6)]
+# wave 1 is long enough for the planner to see several steady-state stage times after its first
+# min_samples observations (the first one covers the ramp-up and is shorter)
+WAVE1 = [(list(range(3 + i, 9 + i)), 48) for i in range(6)]
 WAVE2 = [(list(range(20 + i, 24 + 2 * i)), 10) for i in range(6)]
 
 
 def _serve_waves(rank, world, parts, comm, out_q, slow_rank=-1, lanes=3, rows=3):
-    delay = lambda r: 0.004 if r == slow_rank else 0.0  # noqa: E731
+    # every stage takes 1 ms per layer (so a stage time is its layers' time, not the host's scheduling
+    # noise around a few tiny tensor operations); the slowed one 5 ms
+    delay = lambda r: 0.005 if r == slow_rank else 0.001 if world > 1 else 0.0  # noqa: E731
 
     def runner_for(ps):
         lb, le = ps[rank]

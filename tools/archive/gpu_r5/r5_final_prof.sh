@@ -5,7 +5,7 @@
 set -o pipefail
 O=gpurun_out/${1:-r5prof}; mkdir -p $O
 export TMPDIR=/tmp
-B="bench.py --steps 16 --warmup 2 --batch1-steps 0 --tiny-tokens 0 --prefill-prompts 0 --q8-steps 0 --kq-steps 0 --q40-steps 0 --big-steps 0 --no-cpu-baseline --serve-requests 0 --geometry-steps 0"
+B="bench.py --full --steps 16 --warmup 2 --batch1-steps 0 --tiny-tokens 0 --prefill-prompts 0 --q8-steps 0 --kq-steps 0 --q40-steps 0 --big-steps 0 --no-cpu-baseline --serve-requests 0 --geometry-steps 0"
 MX_NO_GRAPHS=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python3 $B > $O/trace.log 2>&1 || { tail -30 $O/trace.log; exit 1; }
 db=$(find $O/trace -name '*.db' | head -1)
 python3 tools/prof_db.py "$db" --grid --top 40 > $O/by_grid.txt && head -25 $O/by_grid.txt

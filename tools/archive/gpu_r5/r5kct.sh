@@ -8,7 +8,7 @@ for r in 1 2; do for k in 4 8; do
   echo "kct $k run $r $(grep -o '{"M".*' $O/s$k$r.log | cut -c1-400)"
 done; done
 for k in 4 8 48; do
-  MX_WIDE_KCT=${k:0:1} MX_WIDE_KCT_SLAB=${k: -1} timeout -k 10 400 python -u bench.py --no-cpu-baseline --q8-steps 0 --kq-steps 0 --q40-steps 0 --big-steps 0 --geometry-steps 0 --serve-requests 0 --prefill-prompts 0 --tiny-tokens 0 > $O/b$k.json 2> $O/b$k.err || { tail -20 $O/b$k.err; exit 1; }
+  MX_WIDE_KCT=${k:0:1} MX_WIDE_KCT_SLAB=${k: -1} timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --q8-steps 0 --kq-steps 0 --q40-steps 0 --big-steps 0 --geometry-steps 0 --serve-requests 0 --prefill-prompts 0 --tiny-tokens 0 > $O/b$k.json 2> $O/b$k.err || { tail -20 $O/b$k.err; exit 1; }
   echo "kct $k bench $(python3 -c "import json; d=json.loads(open('$O/b$k.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['us_per_launch'], d['roofline']['frac'])")"
 done
 MX_WIDE_KCT=8 MX_WIDE_KCT_SLAB=8 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest8.log 2>&1 || { tail -30 $O/pytest8.log; exit 1; }

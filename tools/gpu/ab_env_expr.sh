@@ -8,7 +8,7 @@ mkdir -p $OUT
 for i in 1 2 3; do
   for v in $VS; do
     envs=$( [ "$v" = "-" ] && echo "" || echo "$v" | tr ',' ' ')
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline $ARGS > $OUT/$v.$i.json 2> $OUT/$v.$i.err \
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $ARGS > $OUT/$v.$i.json 2> $OUT/$v.$i.err \
       || { tail -20 $OUT/$v.$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/$v.$i.json')); print('$v', $EXPR)"
   done
