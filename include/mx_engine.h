@@ -15,6 +15,8 @@
  *   mx_submit/mx_wait  <- Llama.__call__ -> create_completion -> generate():
  *                         llama_decode + sampling per token (reached from :125)
  *   mx_forward_logits  <- llama_decode + llama_get_logits (Llama.eval), parity hook
+ *   mx_submit_lp / mx_request_logprobs
+ *                      <- create_completion(logprobs=k): Llama.logits_to_logprobs + the top-k sort
  *   mx_engine_destroy  <- llama_free / llama_free_model (Llama.__del__)
  * The Python layer (llama-p2p_amd/llama.py) mirrors the Llama class on top of
  * this ABI, so handle_requests / cached_inference / distributed_inference /
@@ -148,6 +150,35 @@ int mx_poll(mx_engine* e, uint64_t req, int n_have, int32_t* out_ids, int cap, i
 /* Ask the scheduler to end a request after its current step (finish reason STOP), e.g. when the
  * caller found a stop string.  The request still has to be released with mx_wait. */
 int mx_cancel(mx_engine* e, uint64_t req);
+
+/* Per-token log-probabilities (llama-cpp-python's create_completion(logprobs=k)).  For a logits row x
+ * with m = max x and s = sum exp(x_i - m): logprob(i) = (x_i - m) - log(s), in f32, over the raw lm_head
+ * row (before the penalties of the sampler chain rewrite it), computed on the device inside the decode
+ * step, so multi-step rounds keep running without a host round-trip.
+ *
+ * mx_submit_lp: as mx_submit; the request also records, per generated token, the token's log-prob and the
+ * min(n_logprobs, n_vocab) most likely tokens (value descending, ties -> lower id).  n_logprobs 0..64
+ * (0: the chosen token only), anything else MX_ERR_ARG.  prompt_logprobs != 0: also one entry per prompt
+ * position p >= 1 (log-prob of prompt[p] given prompt[:p]); such a request evaluates its whole prompt
+ * (no prefix reuse). */
+int mx_submit_lp(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int n_logprobs,
+                 int prompt_logprobs, uint64_t* req);
+/* Copies the entries the request holds so far -- the prompt's first (when asked for), then one per
+ * generated token; a token returned by mx_poll always has its entry: the first min(cap, n) of
+ * tok_lp[n], top_lp[n][k], top_idx[n][k] (any may be NULL), *n_out = n, *k_out = k.  Never blocks; valid
+ * until mx_wait releases the request.  MX_ERR_ARG for a request submitted without log-probabilities. */
+int mx_request_logprobs(mx_engine* e, uint64_t req, float* tok_lp, float* top_lp, int32_t* top_idx, int cap,
+                        int* n_out, int* k_out);
+/* Parity hook: rows forward as mx_forward_rows (n <= 64), then the log-prob kernels: tgt_lp[n] = log-prob
+ * of targets[i] in row i, top_lp / top_idx [n][min(k, n_vocab)] (k 0..64; NULL allowed when k = 0).
+ * logits_out (optional, [n][n_vocab]) receives the very rows the statistics were computed from. */
+int mx_forward_logprobs(mx_engine* e, int n, const int32_t* slots, const int32_t* pos, const int32_t* ids,
+                        const int32_t* targets, int k, float* tgt_lp, float* top_lp, int32_t* top_idx,
+                        float* logits_out);
+/* The same kernels on caller-supplied rows, no engine (tests on inputs no model produces):
+ * logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64, V <= 262144; outputs as above. */
+int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl, const int32_t* targets, int k,
+                     float* tgt_lp, float* top_lp, int32_t* top_idx);
 
 /* Device-resident decode batch (benchmark, pipeline stages).  Rows are M
  * sequences in KV slots `slots`, next token ids[i] at position pos[i].

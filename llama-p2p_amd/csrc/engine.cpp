@@ -25,6 +25,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/mx_engine.h"
@@ -153,6 +154,21 @@ struct Request {
   int32_t next_tok = 0;
   uint64_t seed = 0;  // sampler stream: the n-th sampled token draws samp_u01(seed, n) (kernels.h)
   std::string error;
+  // per-token log-probabilities (mx_submit_lp): lp_k top entries per token (-1 = off), lp_prompt: also one
+  // entry per prompt position >= 1.  Entries are appended under mu together with `out`, the prompt's first.
+  int lp_k = -1;
+  bool lp_prompt = false;
+  int lp_n_prompt = 0;         // prompt entries held (0 or prompt.size() - 1)
+  std::vector<float> lp_tok;   // [entries] log-prob of the token itself
+  std::vector<float> lp_top;   // [entries][lp_k]
+  std::vector<int32_t> lp_idx; // [entries][lp_k]
+  // one entry [tok_lp | kr top log-probs | kr top ids as int bits] of a round that ran with kr >= lp_k
+  void lp_append(const float* entry, int kr) {
+    lp_tok.push_back(entry[0]);
+    lp_top.insert(lp_top.end(), entry + 1, entry + 1 + lp_k);
+    const int32_t* ip = reinterpret_cast<const int32_t*>(entry) + 1 + kr;
+    lp_idx.insert(lp_idx.end(), ip, ip + lp_k);
+  }
 };
 
 struct GraphKey {
@@ -269,7 +285,8 @@ struct mx_engine {
   std::vector<void*> allocations;
 
   // graphs for the scheduler's decode steps, by (M, top-k of the device sampling chain or 0 = argmax)
-  std::map<std::pair<int, int>, hipGraphExec_t> sched_graphs;
+  // ... and the top-k of the round's log-probabilities (-1: none; such rounds enqueue what they always did)
+  std::map<std::tuple<int, int, int>, hipGraphExec_t> sched_graphs;
   // pipeline stage hand-off dtype: x_in / x_out are bf16 [M][n_embd] instead of f32 (mx_opts.handoff_bf16)
   bool handoff_bf16 = false;
   // token pick at the end of a forward with `argmax` set: greedy argmax, or (pick_samp) the device
@@ -277,14 +294,29 @@ struct mx_engine {
   const SampRow* pick_samp = nullptr;
   int pick_k = 0;
   SampRow* d_samp = nullptr;  // [MAX_ROWS] the scheduler's rows
+  // log-probabilities of the pick (request path): pick_lp >= 0 runs the row statistics
+  // ((m, log s) and the top pick_lp log-probs) on the raw logits before the penalties rewrite them, and
+  // after the pick gathers the chosen token's entry into lp_hist [MAX_ROWS][SCHED_KMAX][1 + 2 pick_lp]
+  int pick_lp = -1;
+  float *lp_part = nullptr, *lp_ms = nullptr, *lp_top = nullptr, *lp_hist = nullptr, *lp_side_val = nullptr;
+  int *lp_idx = nullptr, *lp_side_tok = nullptr, *lp_tgt = nullptr;
   void pick(int n_out, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count, int max_hist,
             hipStream_t s) {
+    const bool lp = pick_lp >= 0;
+    if (lp)
+      launch_logprob_stats(logits, n_vocab, n_out, n_vocab, pick_lp, tk_ws_val, tk_ws_idx, lp_part, lp_ms, lp_top,
+                           lp_idx, s);
     if (pick_samp)
       launch_sample_chain(logits, n_vocab, n_out, n_vocab, pick_samp, pick_k, tk_ws_val, tk_ws_idx, tk_val, tk_idx,
-                          d_tok, ids_next, pos_next, hist, hist_stride, hist_count, max_hist, s);
+                          d_tok, ids_next, pos_next, hist, hist_stride, hist_count, max_hist, s,
+                          lp ? lp_side_tok : nullptr, lp ? lp_side_val : nullptr);
     else
       launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, ids_next, pos_next, hist, hist_stride,
                     hist_count, max_hist, s);
+    if (lp)
+      launch_logprob_gather(logits, n_vocab, n_out, n_vocab, pick_lp, d_tok, hist ? hist_count : nullptr, SCHED_KMAX,
+                            pick_samp ? lp_side_tok : nullptr, lp_side_val, lp_ms, lp_top, lp_idx, lp_hist,
+                            (size_t)SCHED_KMAX * (1 + 2 * pick_lp), s);
   }
   int copy_out(void* x_out, int M, hipStream_t s) {  // the residual stream to the next stage
     if (handoff_bf16) launch_f32_to_bf16((uint16_t*)x_out, x, (size_t)M * n_embd, s);
@@ -382,6 +414,7 @@ struct mx_engine {
   void scheduler_loop();
   int sched_step(std::vector<Request*>& rows);
   int prefill_batch(std::vector<Request*>& reqs);
+  int prefill_prompt_logprobs(Request* r);
   int* sched_hist = nullptr;        // [MAX_ROWS][SCHED_KMAX] tokens of a multi-step greedy run
   int* sched_hist_count = nullptr;  // [MAX_ROWS]
   int32_t sample_host(Request* r, const float* logits);
@@ -482,6 +515,14 @@ int mx_engine::init_common() {
     if (int rc = alloc((void**)&tk_ws_idx, (size_t)MAX_ROWS * 64 * TOPK_MAX * 4)) return rc;
     if (int rc = alloc((void**)&tk_val, (size_t)MAX_ROWS * TOPK_MAX * 4)) return rc;
     if (int rc = alloc((void**)&tk_idx, (size_t)MAX_ROWS * TOPK_MAX * 4)) return rc;
+    if (int rc = alloc((void**)&lp_part, (size_t)MAX_ROWS * 64 * 2 * 4)) return rc;
+    if (int rc = alloc((void**)&lp_ms, (size_t)MAX_ROWS * 2 * 4)) return rc;
+    if (int rc = alloc((void**)&lp_top, (size_t)MAX_ROWS * TOPK_MAX * 4)) return rc;
+    if (int rc = alloc((void**)&lp_idx, (size_t)MAX_ROWS * TOPK_MAX * 4)) return rc;
+    if (int rc = alloc((void**)&lp_hist, (size_t)MAX_ROWS * SCHED_KMAX * (1 + 2 * TOPK_MAX) * 4)) return rc;
+    if (int rc = alloc((void**)&lp_side_tok, (size_t)MAX_ROWS * SAMP_WIN * 4)) return rc;
+    if (int rc = alloc((void**)&lp_side_val, (size_t)MAX_ROWS * SAMP_WIN * 4)) return rc;
+    if (int rc = alloc((void**)&lp_tgt, (size_t)MAX_ROWS * 4)) return rc;
   }
   if (int rc = alloc((void**)&am_idx, (size_t)R * 64 * 4)) return rc;
   if (int rc = alloc((void**)&d_tok, (size_t)R * 4)) return rc;
@@ -1696,6 +1737,11 @@ int mx_engine::prefill_batch(std::vector<Request*>& reqs) {
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
   } log{t0, reqs.size()};
+  // requests with prompt log-probabilities first evaluate prompt[0..n-1) in a pass of their own (all rows
+  // through lm_head); what is left of them is the last prompt row, which joins the batch below
+  for (Request* r : reqs)
+    if (r->lp_prompt && r->prompt.size() > 1)
+      if (int rc = prefill_prompt_logprobs(r)) return rc;
   // every prompt's rows start a 16-row block and are padded to whole blocks (positions past the prompt,
   // overwritten by its decode later; near n_ctx copies of the last row), so each chunk is blocked
   // (attn_prefill_kernel) and a prompt's blocks are the same whatever shares its chunk
@@ -1756,7 +1802,13 @@ int mx_engine::prefill_batch(std::vector<Request*>& reqs) {
     rows_blocked = false;
     prefill_gemm = false;
     if (frc) return frc;
-    int ktop = 0;
+    int ktop = 0, lpk = -1;  // lpk: log-probabilities of the first tokens, from these raw last-row logits
+    for (int k = 0; k < n_out; k++) lpk = std::max(lpk, reqs[q0 + k]->lp_k);
+    pick_lp = lpk;
+    struct ResetLp {
+      mx_engine* e;
+      ~ResetLp() { e->pick_lp = -1; }
+    } reset_lp{this};
     if (n_out && dev_pick) {
       sr.resize(n_out);
       for (int k = 0; k < n_out; k++) {
@@ -1774,26 +1826,93 @@ int mx_engine::prefill_batch(std::vector<Request*>& reqs) {
       pick_k = 0;
       HIPC(hipMemcpyAsync(tok.data() + q0, d_tok, n_out * 4, hipMemcpyDeviceToHost, st));
     } else if (n_out) {
-      launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
+      if (lpk >= 0)
+        pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);  // pick_samp is null: argmax
+      else
+        launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, nullptr, nullptr, nullptr, 0, nullptr,
+                      0, st);
       HIPC(hipMemcpyAsync(tok.data() + q0, d_tok, n_out * 4, hipMemcpyDeviceToHost, st));
       if (any_sampling && !dev_pick) {
         lg.resize((size_t)n_out * n_vocab);
         HIPC(hipMemcpyAsync(lg.data(), logits, lg.size() * 4, hipMemcpyDeviceToHost, st));
       }
     }
+    const size_t lps = (size_t)SCHED_KMAX * (1 + 2 * std::max(lpk, 0));  // floats per row of lp_hist
+    std::vector<float> lph, lpms;
+    if (n_out && lpk >= 0) {
+      lph.resize(n_out * lps);
+      lpms.resize((size_t)n_out * 2);
+      HIPC(hipMemcpyAsync(lph.data(), lp_hist, lph.size() * 4, hipMemcpyDeviceToHost, st));
+      HIPC(hipMemcpyAsync(lpms.data(), lp_ms, lpms.size() * 4, hipMemcpyDeviceToHost, st));
+    }
     HIPC(hipStreamSynchronize(st));
     std::lock_guard<std::mutex> lk(mu);
     for (int k = 0; k < n_out; k++) {
       Request* r = reqs[q0 + k];
       int32_t t = tok[q0 + k];
-      if (!dev_pick && (r->samp.temperature > 0.f || has_penalties(r->samp)))
-        t = sample_host(r, lg.data() + (size_t)k * n_vocab);
+      const bool host_pick = !dev_pick && (r->samp.temperature > 0.f || has_penalties(r->samp));
+      if (host_pick) t = sample_host(r, lg.data() + (size_t)k * n_vocab);
       r->out.push_back(t);
       r->next_tok = t;
+      if (r->lp_k >= 0) {
+        float* ent = lph.data() + k * lps;
+        // host-sampled: the same formula over the raw logit of the copied row
+        if (host_pick) ent[0] = (lg[(size_t)k * n_vocab + t] - lpms[2 * k]) - lpms[2 * k + 1];
+        r->lp_append(ent, lpk);
+      }
     }
     q0 = q1;
     i = e;
   }
+  return 0;
+}
+
+// Prompt log-probabilities of one request (mx_submit_lp with prompt_logprobs): rows 0..n-2 of its prompt
+// in chunks of at most MAX_ROWS rows (whole 16-row blocks, padded as in prefill_batch), every real row
+// through lm_head, then launch_logprobs with the next prompt token as each row's target.  The last prompt
+// row is left to prefill_batch (r->reuse = n - 1), whose logits start generation as for any request.
+int mx_engine::prefill_prompt_logprobs(Request* r) {
+  const int n = (int)r->prompt.size() - 1, k = r->lp_k, stride = 1 + 2 * k;
+  std::vector<float> ent((size_t)MAX_ROWS * stride), all;
+  all.reserve((size_t)n * stride);
+  hipStream_t st = stream;
+  for (int i = 0; i < n; i += MAX_ROWS) {
+    const int m = std::min(MAX_ROWS, n - i), pad = (16 - m % 16) % 16, mp = m + pad;
+    std::vector<int32_t> slots(mp, r->slot), pos(mp), ids(mp), rowmap(m), tgt(m);
+    for (int j = 0; j < m; j++) pos[j] = i + j, ids[j] = r->prompt[i + j], rowmap[j] = j, tgt[j] = r->prompt[i + j + 1];
+    for (int j = 0; j < pad; j++) {
+      pos[m + j] = i + mp <= n_ctx ? i + m + j : i + m - 1;
+      ids[m + j] = r->prompt[i + m - 1];
+    }
+    HIPC(hipMemcpyAsync(d_ids, ids.data(), mp * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_pos, pos.data(), mp * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_slot, slots.data(), mp * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_rowmap, rowmap.data(), m * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(lp_tgt, tgt.data(), m * 4, hipMemcpyHostToDevice, st));
+    rows_distinct = false;
+    rows_blocked = blocked_rows(slots.data(), pos.data(), ids.data(), mp);
+    prefill_gemm = true;
+    const int frc = enqueue_forward(mp, d_ids, d_pos, d_slot, nullptr, nullptr, true, d_rowmap, m, false, nullptr,
+                                    nullptr, nullptr, 0, nullptr, 0, st);
+    rows_blocked = false;
+    prefill_gemm = false;
+    if (frc) {
+      hipStreamSynchronize(st);
+      return frc;
+    }
+    if (launch_logprobs(logits, n_vocab, m, n_vocab, k, lp_tgt, tk_ws_val, tk_ws_idx, lp_part, lp_ms, lp_top, lp_idx,
+                        lp_hist, st)) {
+      hipStreamSynchronize(st);
+      return fail(MX_ERR_ARG, "log-prob launch shape");
+    }
+    HIPC(hipMemcpyAsync(ent.data(), lp_hist, (size_t)m * stride * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    all.insert(all.end(), ent.begin(), ent.begin() + (size_t)m * stride);
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  for (int j = 0; j < n; j++) r->lp_append(all.data() + (size_t)j * stride, k);
+  r->lp_n_prompt = n;
+  r->reuse = n;
   return 0;
 }
 
@@ -1806,8 +1925,9 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   const int M = (int)rows.size();
   std::vector<int32_t> ids(M), pos(M), slots(M);
   bool all_greedy = true, all_dev = true;
-  int room = SCHED_KMAX, need = 1, ktop = 0;
+  int room = SCHED_KMAX, need = 1, ktop = 0, lpk = -1;  // lpk: max lp_k of the rows, -1 = no log-probabilities
   for (int i = 0; i < M; i++) {
+    lpk = std::max(lpk, rows[i]->lp_k);
     ids[i] = rows[i]->next_tok;
     pos[i] = rows[i]->pos;
     slots[i] = rows[i]->slot;
@@ -1844,9 +1964,10 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   rows_distinct = true;  // one row per active request, each its own slot
   pick_samp = dev_chain ? d_samp : nullptr;
   pick_k = dev_chain ? ktop : 0;
+  pick_lp = lpk;
   struct Reset {
     mx_engine* e;
-    ~Reset() { e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; }
+    ~Reset() { e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1; }
   } reset_flags{this};
   auto step = [&]() -> int {
     return enqueue_forward(M, d_ids, d_pos, d_slot, nullptr, nullptr, true, nullptr, M, true, d_ids, d_pos,
@@ -1855,7 +1976,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;  // per-round timing on stderr
   const auto t0 = std::chrono::steady_clock::now();
   bool captured = false;
-  const std::pair<int, int> gkey(M, pick_k);
+  const std::tuple<int, int, int> gkey(M, pick_k, pick_lp);
   auto it = sched_graphs.find(gkey);
   if (use_graphs && it == sched_graphs.end()) {
     captured = true;
@@ -1899,11 +2020,22 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     lg.resize((size_t)M * n_vocab);
     HIPC(hipMemcpyAsync(lg.data(), logits, (size_t)M * n_vocab * 4, hipMemcpyDeviceToHost, s));
   }
+  // the round's log-prob history travels with `hist`; (m, log s) too when the host picks (K = 1)
+  const size_t lpe = 1 + 2 * (size_t)std::max(lpk, 0), lps = SCHED_KMAX * lpe;
+  std::vector<float> lph, lpms;
+  if (lpk >= 0) {
+    lph.resize(M * lps);
+    HIPC(hipMemcpyAsync(lph.data(), lp_hist, lph.size() * 4, hipMemcpyDeviceToHost, s));
+    if (!all_greedy && !dev_chain) {
+      lpms.resize((size_t)M * 2);
+      HIPC(hipMemcpyAsync(lpms.data(), lp_ms, lpms.size() * 4, hipMemcpyDeviceToHost, s));
+    }
+  }
   HIPC(hipStreamSynchronize(s));
   if (trace) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr, "sched: decode M=%d K=%d %s%s%.3f ms\n", M, K, dev_chain ? "(device sampling) " : "",
-            captured ? "(graph captured) " : "", ms);
+    fprintf(stderr, "sched: decode M=%d K=%d %s%s%s%.3f ms\n", M, K, dev_chain ? "(device sampling) " : "",
+            lpk >= 0 ? "(logprobs) " : "", captured ? "(graph captured) " : "", ms);
   }
   std::lock_guard<std::mutex> lk(mu);
   for (int i = 0; i < M; i++) {
@@ -1911,17 +2043,27 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     for (int k = 0; k < K && !r->done; k++) {
       r->pos++;
       int32_t t = hist[(size_t)i * SCHED_KMAX + k];
-      if (!dev_chain && (r->samp.temperature > 0.f || has_penalties(r->samp))) {
+      float raw = 0.f;  // host pick: the chosen token's raw logit (candidate list or copied row)
+      const bool host_pick = !dev_chain && (r->samp.temperature > 0.f || has_penalties(r->samp));
+      if (host_pick) {
         if (!tkv.empty()) {
           std::vector<std::pair<float, int>> c(std::min(r->samp.top_k, n_vocab));
           for (size_t j = 0; j < c.size(); j++) c[j] = {tkv[(size_t)i * TK + j], tki[(size_t)i * TK + j]};
           t = sample_chain(r, c);
+          for (size_t j = 0; j < c.size(); j++)
+            if (tki[(size_t)i * TK + j] == t) raw = tkv[(size_t)i * TK + j];
         } else {
           t = sample_host(r, lg.data() + (size_t)i * n_vocab);
+          raw = lg[(size_t)i * n_vocab + t];
         }
       }
       r->out.push_back(t);
       r->next_tok = t;
+      if (r->lp_k >= 0) {
+        float* ent = lph.data() + i * lps + k * lpe;
+        if (host_pick) ent[0] = (raw - lpms[2 * i]) - lpms[2 * i + 1];
+        r->lp_append(ent, lpk);
+      }
       if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
       else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
     }
@@ -1964,7 +2106,7 @@ void mx_engine::scheduler_loop() {
         r->slot = free_slots[best];
         free_slots.erase(free_slots.begin() + best);
         // at least the last prompt token is evaluated (its logits start generation)
-        r->reuse = std::min(best_lcp, (int)r->prompt.size() - 1);
+        r->reuse = r->lp_prompt ? 0 : std::min(best_lcp, (int)r->prompt.size() - 1);
         stat_prompt_tokens += r->prompt.size();
         stat_reused_tokens += r->reuse;
         admit.push_back(r);
@@ -2248,6 +2390,128 @@ int mx_submit(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int
   if (!e || !ids || n < 1 || !req) return fail(MX_ERR_ARG, "bad arguments");
   const int32_t len = n;
   return mx_submit_batch(e, 1, &ids, &len, s, &max_tokens, req);
+}
+
+int mx_submit_lp(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int n_logprobs,
+                 int prompt_logprobs, uint64_t* req) {
+  if (!e || !ids || n < 1 || !req) return fail(MX_ERR_ARG, "bad arguments");
+  if (n_logprobs < 0 || n_logprobs > TOPK_MAX) return fail(MX_ERR_ARG, "mx_submit_lp: n_logprobs must be 0..64");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit needs a full-model engine");
+  std::unique_ptr<Request> r;
+  if (int rc = make_request(e, ids, n, s, max_tokens, &r)) return rc;
+  r->lp_k = std::min(n_logprobs, e->n_vocab);
+  r->lp_prompt = prompt_logprobs != 0;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->stop) return fail(MX_ERR_STATE, "engine shutting down");
+    Request* rp = r.get();
+    rp->id = e->next_id++;
+    *req = rp->id;
+    e->pending.push_back(rp);
+    e->requests[rp->id] = std::move(r);
+    if (!e->worker_started) {
+      e->worker_started = true;
+      e->worker = std::thread([e] { e->scheduler_loop(); });
+    }
+  }
+  e->cv.notify_all();
+  return 0;
+}
+
+int mx_request_logprobs(mx_engine* e, uint64_t req, float* tok_lp, float* top_lp, int32_t* top_idx, int cap, int* n_out,
+                        int* k_out) {
+  if (!e || cap < 0) return fail(MX_ERR_ARG, "bad arguments");
+  std::lock_guard<std::mutex> lk(e->mu);
+  auto it = e->requests.find(req);
+  if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
+  const Request* r = it->second.get();
+  if (r->lp_k < 0) return fail(MX_ERR_ARG, "request was submitted without log-probabilities");
+  const size_t n = r->lp_tok.size(), c = std::min<size_t>(n, cap), k = r->lp_k;
+  if (tok_lp && c) memcpy(tok_lp, r->lp_tok.data(), c * 4);
+  if (top_lp && c * k) memcpy(top_lp, r->lp_top.data(), c * k * 4);
+  if (top_idx && c * k) memcpy(top_idx, r->lp_idx.data(), c * k * 4);
+  if (n_out) *n_out = (int)n;
+  if (k_out) *k_out = (int)k;
+  return 0;
+}
+
+// [n][1 + 2k] entries (launch_logprobs) -> the three host arrays
+static void split_entries(const std::vector<float>& ent, int n, int k, float* tgt_lp, float* top_lp, int32_t* top_idx) {
+  const size_t st = 1 + 2 * (size_t)k;
+  for (int i = 0; i < n; i++) {
+    const float* o = ent.data() + i * st;
+    if (tgt_lp) tgt_lp[i] = o[0];
+    if (top_lp && k) memcpy(top_lp + (size_t)i * k, o + 1, (size_t)k * 4);
+    if (top_idx && k) memcpy(top_idx + (size_t)i * k, o + 1 + k, (size_t)k * 4);
+  }
+}
+
+int mx_forward_logprobs(mx_engine* e, int n, const int32_t* slots, const int32_t* pos, const int32_t* ids,
+                        const int32_t* targets, int k, float* tgt_lp, float* top_lp, int32_t* top_idx,
+                        float* logits_out) {
+  if (!e || n < 1 || n > MAX_ROWS || !slots || !pos || !ids || !targets || !tgt_lp || k < 0 || k > TOPK_MAX ||
+      (k && (!top_lp || !top_idx)))
+    return fail(MX_ERR_ARG, "mx_forward_logprobs: 1 <= n <= 64 rows, 0 <= k <= 64");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_forward_logprobs needs a full-model engine");
+  for (int i = 0; i < n; i++)
+    if (targets[i] < 0 || targets[i] >= e->n_vocab) return fail(MX_ERR_ARG, "target id out of range");
+  std::lock_guard<std::mutex> lk(e->gpu_mu);
+  hipSetDevice(e->device);
+  k = std::min(k, e->n_vocab);
+  std::vector<float> lg;  // the rows stay on the device too (e->logits): the statistics read those
+  if (!logits_out) lg.resize((size_t)n * e->n_vocab), logits_out = lg.data();
+  if (int rc = e->forward_rows_chunk(n, slots, pos, ids, nullptr, nullptr, logits_out, e->stream)) return rc;
+  std::vector<float> ent((size_t)n * (1 + 2 * k));
+  HIPC(hipMemcpyAsync(e->lp_tgt, targets, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  if (launch_logprobs(e->logits, e->n_vocab, n, e->n_vocab, k, e->lp_tgt, e->tk_ws_val, e->tk_ws_idx, e->lp_part,
+                      e->lp_ms, e->lp_top, e->lp_idx, e->lp_hist, e->stream)) {
+    hipStreamSynchronize(e->stream);
+    return fail(MX_ERR_ARG, "log-prob launch shape");
+  }
+  HIPC(hipMemcpyAsync(ent.data(), e->lp_hist, ent.size() * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  split_entries(ent, n, k, tgt_lp, top_lp, top_idx);
+  return 0;
+}
+
+int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl, const int32_t* targets, int k,
+                     float* tgt_lp, float* top_lp, int32_t* top_idx) {
+  if (!logits_host || !targets || !tgt_lp || n < 1 || n > MAX_ROWS || V < 1 || ldl < V || k < 0 || k > TOPK_MAX ||
+      (k && (!top_lp || !top_idx)))
+    return fail(MX_ERR_ARG, "mx_logprob_probe: 1 <= n <= 64 rows, ldl >= V >= 1, 0 <= k <= 64");
+  for (int i = 0; i < n; i++)
+    if (targets[i] < 0 || targets[i] >= V) return fail(MX_ERR_ARG, "target id out of range");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  k = std::min(k, V);
+  const int kk = std::max(k, 1);
+  const size_t est = 1 + 2 * (size_t)k;
+  float *d_lg = nullptr, *d_wsv = nullptr, *d_part = nullptr, *d_ms = nullptr, *d_top = nullptr, *d_out = nullptr;
+  int *d_wsi = nullptr, *d_idx = nullptr, *d_tgt = nullptr;
+  std::vector<void*> owned;
+  auto dalloc = [&](void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) != hipSuccess) return false;
+    owned.push_back(*p);
+    return true;
+  };
+  struct Free {
+    std::vector<void*>& v;
+    ~Free() { for (void* p : v) hipFree(p); }
+  } free_all{owned};
+  if (!dalloc((void**)&d_lg, (size_t)n * ldl * 4) || !dalloc((void**)&d_wsv, (size_t)n * 64 * kk * 4) ||
+      !dalloc((void**)&d_wsi, (size_t)n * 64 * kk * 4) || !dalloc((void**)&d_part, (size_t)n * 64 * 2 * 4) ||
+      !dalloc((void**)&d_ms, (size_t)n * 2 * 4) || !dalloc((void**)&d_top, (size_t)n * kk * 4) ||
+      !dalloc((void**)&d_idx, (size_t)n * kk * 4) || !dalloc((void**)&d_tgt, (size_t)n * 4) ||
+      !dalloc((void**)&d_out, (size_t)n * est * 4))
+    return fail(MX_ERR_HIP, "mx_logprob_probe: device allocation");
+  HIPC(hipMemcpy(d_lg, logits_host, (size_t)n * ldl * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_tgt, targets, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (launch_logprobs(d_lg, ldl, n, V, k, d_tgt, d_wsv, d_wsi, d_part, d_ms, d_top, d_idx, d_out, nullptr))
+    return fail(MX_ERR_ARG, "log-prob launch shape (V too large for the top-k slices)");
+  HIPC(hipDeviceSynchronize());
+  std::vector<float> ent((size_t)n * est);
+  HIPC(hipMemcpy(ent.data(), d_out, ent.size() * 4, hipMemcpyDeviceToHost));
+  split_entries(ent, n, k, tgt_lp, top_lp, top_idx);
+  return 0;
 }
 
 int mx_wait(mx_engine* e, uint64_t req, int32_t* out_ids, int cap, int* n_out, int* finish) {

@@ -301,7 +301,22 @@ __host__ __device__ inline int samp_pick(const float* vals, const int* ids, int 
 // same token bookkeeping as launch_argmax (tok_out, ids_next, pos_next, history)
 int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* samp, int K, float* ws_val, int* ws_idx,
                         float* tk_val, int* tk_idx, int* tok_out, int* ids_next, int* pos_next, int* hist,
-                        int hist_stride, int* hist_count, int max_hist, hipStream_t s);
+                        int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok = nullptr,
+                        float* side_val = nullptr);  // side_*: [M][SAMP_WIN] raw logits the penalties rewrote
+// ---- per-token log-probabilities, logprob(i) = (x_i - m) - log(sum exp(x - m)) over the raw logits row
+// (DESIGN.md §9).  K = 0..min(TOPK_MAX, V) top entries per row (value descending, ties lower id first).
+// stats: one read of the rows -> part [M][64][2] slice (max, sum) partials, ms [M][2] = (m, log s) and the
+// top-K as log-probs (top_lp / top_idx [M][K]; ws as launch_topk).  gather: per row the entry
+// [logprob of toks[c] | K top log-probs | K top ids as int bits] at out[c * row_stride + step * (1 + 2K)],
+// step = hist_count[c] - 1 (0 when hist_count is null); side_* as written by launch_sample_chain.
+int launch_logprob_stats(const float* logits, int ldl, int M, int V, int K, float* ws_val, int* ws_idx, float* part,
+                         float* ms, float* top_lp, int* top_idx, hipStream_t s);
+int launch_logprob_gather(const float* logits, int ldl, int M, int V, int K, const int* toks, const int* hist_count,
+                          int max_steps, const int* side_tok, const float* side_val, const float* ms,
+                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s);
+// both, for given target tokens: out [M][1 + 2K]
+int launch_logprobs(const float* logits, int ldl, int M, int V, int K, const int* targets, float* ws_val, int* ws_idx,
+                    float* part, float* ms, float* top_lp, int* top_idx, float* out, hipStream_t s);
 // hand-off conversions of the residual stream (pipeline stages): f32 <-> bf16 rows (RNE), and the
 // per-16-element sums of squares of the f32 rows made from bf16 (RMS_NORM-on-load consumers)
 void launch_f32_to_bf16(uint16_t* dst, const float* src, size_t n, hipStream_t s);

@@ -1409,10 +1409,14 @@ void launch_argmax(const float* logits, int ldl, int M, int V, float* ws_val, in
 // when positive (multiplied otherwise), then count*freq + presence subtracted -- engine.cpp
 // sample_host's arithmetic, in the same order.
 // ---------------------------------------------------------------------------
+// side_tok / side_val (optional, [M][SAMP_WIN]): the rewriting lane first saves (token, raw logit) there
+// (-1 in every other lane), so logprob_gather_kernel still finds the raw value of a penalised token.
 __global__ __launch_bounds__(64) void penalty_kernel(float* logits, int ldl, const SampRow* samp, const int* hist,
-                                                     int hist_stride, const int* hist_count) {
+                                                     int hist_stride, const int* hist_count, int* side_tok,
+                                                     float* side_val) {
   const int c = blockIdx.x, lane = threadIdx.x;
   const SampRow& sp = samp[c];
+  if (side_tok) side_tok[c * SAMP_WIN + lane] = -1;
   if (sp.last_n <= 0 || (sp.repeat == 1.0f && sp.freq == 0.0f && sp.presence == 0.0f)) return;
   const int nh = hist ? hist_count[c] : 0;
   const int total = sp.n_win + nh;
@@ -1430,6 +1434,7 @@ __global__ __launch_bounds__(64) void penalty_kernel(float* logits, int ldl, con
   if (first && t >= 0) {
     float* lp = logits + (size_t)c * ldl + t;
     float v = *lp;
+    if (side_tok) side_tok[c * SAMP_WIN + lane] = t, side_val[c * SAMP_WIN + lane] = v;
     if (sp.repeat != 1.0f) v = v <= 0.f ? v * sp.repeat : v / sp.repeat;
     *lp = v - ((float)count * sp.freq + sp.presence);
   }
@@ -1459,13 +1464,129 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* tk_val, const i
 
 int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* samp, int K, float* ws_val, int* ws_idx,
                         float* tk_val, int* tk_idx, int* tok_out, int* ids_next, int* pos_next, int* hist,
-                        int hist_stride, int* hist_count, int max_hist, hipStream_t s) {
+                        int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok,
+                        float* side_val) {
   if (K < 1 || K > TOPK_MAX || M < 1) return -1;
-  penalty_kernel<<<M, 64, 0, s>>>(logits, ldl, samp, hist, hist_stride, hist_count);
+  penalty_kernel<<<M, 64, 0, s>>>(logits, ldl, samp, hist, hist_stride, hist_count, side_tok, side_val);
   if (launch_topk(logits, ldl, M, V, K, ws_val, ws_idx, tk_val, tk_idx, s)) return -1;
   sample_kernel<<<M, 64, 0, s>>>(tk_val, tk_idx, K, samp, tok_out, ids_next, pos_next, hist, hist_stride, hist_count,
                                  max_hist);
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Per-token log-probabilities over the raw lm_head logits row x[0..V): with m = max x and
+// s = sum exp(x_i - m), logprob(i) = (x_i - m) - log(s) -- always in that form (never x_i - (m + log s):
+// the rounded sum loses the result when |m| is large), f32 throughout, no atomics.  Stage 1 is
+// topk_stage1 plus the slice's (m_b, s_b): the slice staged in LDS serves both, one HBM read of the
+// row.  Every sum runs in a fixed order (a thread's strided terms, the wave64 butterfly, the 4 waves,
+// then the slices by index), so a row's result does not depend on M or on its batch-mates.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lse_topk_stage1(const float* logits, int ldl, int V, int K, float* cv, int* ci,
+                                                       float* part) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ float red[4];
+  const int c = blockIdx.y, b = blockIdx.x, nb = gridDim.x;
+  const int lo = (int)((long long)V * b / nb), hi = (int)((long long)V * (b + 1) / nb);
+  __shared__ int ids[4096];
+  __shared__ float vals[4096];
+  float m = -INFINITY;
+  for (int j = threadIdx.x; j < hi - lo; j += 256) {
+    const float v = logits[(size_t)c * ldl + lo + j];
+    vals[j] = v, ids[j] = lo + j;
+    m = fmaxf(m, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();  // also: vals / ids complete
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  if (m > -INFINITY)
+    for (int j = threadIdx.x; j < hi - lo; j += 256) sum += expf(vals[j] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* p = part + ((size_t)c * nb + b) * 2;
+    p[0] = m;
+    p[1] = ((red[0] + red[1]) + red[2]) + red[3];
+  }
+  if (K > 0)
+    topk_select<256>(vals, ids, hi - lo, K, cv + ((size_t)c * nb + b) * K, ci + ((size_t)c * nb + b) * K, sv, si);
+}
+
+// one wave per row: merge the nb <= 64 slice partials (s = sum_b s_b exp(m_b - m), in index order),
+// store (m, log s), and turn the row's merged top-k values into log-probabilities in place
+__global__ __launch_bounds__(64) void logprob_finish_kernel(const float* part, int nb, float* ms, float* top, int K) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  float mb = -INFINITY, sb = 0.f;
+  if (lane < nb) mb = part[((size_t)c * nb + lane) * 2], sb = part[((size_t)c * nb + lane) * 2 + 1];
+  float m = mb;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  const float term = sb > 0.f ? sb * expf(mb - m) : 0.f;
+  float sum = 0.f;
+  for (int b = 0; b < nb; ++b) sum += __shfl(term, b);
+  const float ls = logf(sum);
+  if (lane == 0) ms[c * 2] = m, ms[c * 2 + 1] = ls;
+  if (lane < K) top[(size_t)c * K + lane] = (top[(size_t)c * K + lane] - m) - ls;
+}
+
+// one wave per row, after the pick: entry = [logprob of toks[c] | K top log-probs | K top ids (int bits)]
+// at out[c * row_stride + step * (1 + 2K)], step = hist_count[c] - 1 (the token just appended; 0 without
+// a history).  The token's raw logit comes from the penalty side table when the penalties rewrote it.
+__global__ __launch_bounds__(64) void logprob_gather_kernel(const float* logits, int ldl, int V, int K, const int* toks,
+                                                            const int* hist_count, int max_steps, const int* side_tok,
+                                                            const float* side_val, const float* ms, const float* top,
+                                                            const int* top_idx, float* out, size_t row_stride) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const int step = hist_count ? hist_count[c] - 1 : 0;
+  if (step < 0 || step >= max_steps) return;
+  float* o = out + (size_t)c * row_stride + (size_t)step * (1 + 2 * K);
+  const int tok = toks[c];
+  float raw = tok >= 0 && tok < V ? logits[(size_t)c * ldl + tok] : NAN;
+  if (side_tok) {
+    const bool hit = side_tok[c * SAMP_WIN + lane] == tok;
+    const float sv = hit ? side_val[c * SAMP_WIN + lane] : 0.f;
+    const unsigned long long mask = __ballot(hit);
+    if (mask) raw = __shfl(sv, __ffsll((long long)mask) - 1);
+  }
+  if (lane == 0) o[0] = (raw - ms[c * 2]) - ms[c * 2 + 1];
+  if (lane < K) {
+    o[1 + lane] = top[(size_t)c * K + lane];
+    reinterpret_cast<int*>(o)[1 + K + lane] = top_idx[(size_t)c * K + lane];
+  }
+}
+
+int launch_logprob_stats(const float* logits, int ldl, int M, int V, int K, float* ws_val, int* ws_idx, float* part,
+                         float* ms, float* top_lp, int* top_idx, hipStream_t s) {
+  if (K < 0 || K > TOPK_MAX || K > V || M < 1 || V < 1) return -1;
+  const int nb = std::min(64, std::max(1, (V + 2047) / 2048));
+  if ((V + nb - 1) / nb > 4096) return -1;
+  lse_topk_stage1<<<dim3(nb, M), 256, 0, s>>>(logits, ldl, V, K, ws_val, ws_idx, part);
+  if (K > 0) topk_stage2<<<M, 256, 0, s>>>(ws_val, ws_idx, nb * K, K, top_lp, top_idx);
+  logprob_finish_kernel<<<M, 64, 0, s>>>(part, nb, ms, top_lp, K);
+  return 0;
+}
+
+int launch_logprob_gather(const float* logits, int ldl, int M, int V, int K, const int* toks, const int* hist_count,
+                          int max_steps, const int* side_tok, const float* side_val, const float* ms,
+                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s) {
+  if (K < 0 || K > TOPK_MAX || M < 1 || max_steps < 1 || row_stride < (size_t)max_steps * (1 + 2 * K)) return -1;
+  logprob_gather_kernel<<<M, 64, 0, s>>>(logits, ldl, V, K, toks, hist_count, max_steps, side_tok, side_val, ms,
+                                         top_lp, top_idx, out, row_stride);
+  return 0;
+}
+
+int launch_logprobs(const float* logits, int ldl, int M, int V, int K, const int* targets, float* ws_val, int* ws_idx,
+                    float* part, float* ms, float* top_lp, int* top_idx, float* out, hipStream_t s) {
+  if (launch_logprob_stats(logits, ldl, M, V, K, ws_val, ws_idx, part, ms, top_lp, top_idx, s)) return -1;
+  return launch_logprob_gather(logits, ldl, M, V, K, targets, nullptr, 1, nullptr, nullptr, ms, top_lp, top_idx, out,
+                               (size_t)(1 + 2 * K), s);
 }
 
 // ---------------------------------------------------------------------------

@@ -29,7 +29,9 @@ EXPORTS = [
     "mx_batch_step", "mx_batch_ids_device", "mx_batch_bind_ids", "mx_batch_tokens", "mx_batch_destroy", "mx_stage_rows",
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
+    "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
 ]
+TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
 
 
 class MxError(RuntimeError):
@@ -157,6 +159,10 @@ def lib() -> ctypes.CDLL:
         L.mx_batch_reset.argtypes = [vp, vp, vp, vp, vp, vp]
         L.mx_stage_rows_pick.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.mx_debug.argtypes = [vp, i32, ctypes.c_longlong, vp, ctypes.c_size_t]
+        L.mx_submit_lp.argtypes = [vp, vp, i32, P(MxSampling), i32, i32, i32, P(u64)]
+        L.mx_request_logprobs.argtypes = [vp, u64, vp, vp, vp, i32, P(i32), P(i32)]
+        L.mx_forward_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -191,6 +197,24 @@ def probe_copy(device: int = 0, gib: int = 4, iters: int = 10, read_only: bool =
     return gbs.value, desc.value.decode()
 
 
+def logprob_probe(logits, targets, k: int, V: Optional[int] = None, device: int = 0):
+    """The log-prob kernels on caller-supplied f32 rows (no engine): logits [n][ldl] with V <= ldl valid
+    columns (default all), n <= 64.  Returns (tgt_lp [n], top_lp [n][min(k, V)], top_idx [n][min(k, V)])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    n, ldl = lg.shape
+    V = ldl if V is None else V
+    tg = _i32(targets)
+    if len(tg) != n:
+        raise ValueError("one target per row")
+    ke = max(0, min(k, V))
+    tgt = np.empty(n, dtype=np.float32)
+    top = np.empty((n, ke), dtype=np.float32)
+    idx = np.empty((n, ke), dtype=np.int32)
+    _check(lib().mx_logprob_probe(device, lg.ctypes.data, n, V, ldl, tg.ctypes.data, k, tgt.ctypes.data,
+                                  top.ctypes.data if ke else None, idx.ctypes.data if ke else None))
+    return tgt, top, idx
+
+
 def _check(rc: int):
     if rc != MX_OK:
         raise MxError(rc, lib().mx_last_error().decode(errors="replace"))
@@ -202,6 +226,8 @@ def _i32(a) -> np.ndarray:
 
 class Engine:
     """One engine instance = one GPU, one model (or one pipeline stage of it)."""
+
+    supports_logprobs = True  # submit(logprobs=) / logprobs(): what Llama.create_completion(logprobs=) needs
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
@@ -248,6 +274,21 @@ class Engine:
                                      vals.ctypes.data, idx.ctypes.data))
         return vals, idx
 
+    def forward_logprobs(self, slots, pos, ids, targets, k: int, want_logits: bool = False):
+        """Rows forward (<= 64) + the log-prob kernels: (log-prob of targets[i] in row i [n], top log-probs
+        [n][k'], their ids [n][k']) with k' = min(k, n_vocab); want_logits adds the f32 rows the statistics
+        were computed from."""
+        slots, pos, ids, targets = _i32(slots), _i32(pos), _i32(ids), _i32(targets)
+        n, ke = len(ids), max(0, min(k, self.n_vocab))
+        tgt = np.empty(n, dtype=np.float32)
+        top = np.empty((n, ke), dtype=np.float32)
+        idx = np.empty((n, ke), dtype=np.int32)
+        lg = np.empty((n, self.n_vocab), dtype=np.float32) if want_logits else None
+        _check(lib().mx_forward_logprobs(self._h, n, slots.ctypes.data, pos.ctypes.data, ids.ctypes.data,
+                                         targets.ctypes.data, k, tgt.ctypes.data, top.ctypes.data if ke else None,
+                                         idx.ctypes.data if ke else None, lg.ctypes.data if lg is not None else None))
+        return (tgt, top, idx, lg) if want_logits else (tgt, top, idx)
+
     def stage_rows(self, slots, pos, ids, x_in: int = 0, x_out: int = 0, want_logits: bool = False,
                    stream: int = 0) -> Optional[np.ndarray]:
         slots, pos = _i32(slots), _i32(pos)
@@ -279,7 +320,9 @@ class Engine:
     def submit(self, ids: Sequence[int], max_tokens: int, temperature: float = 0.0, top_k: int = 40,
                top_p: float = 0.95, min_p: float = 0.05, repeat_penalty: float = 1.0, repeat_last_n: int = 64,
                seed: Optional[int] = None, ignore_eos: bool = False, frequency_penalty: float = 0.0,
-               presence_penalty: float = 0.0) -> int:
+               presence_penalty: float = 0.0, logprobs: Optional[int] = None, prompt_logprobs: bool = False) -> int:
+        """logprobs=k (0..64): the request also records each generated token's log-probability and the k
+        most likely tokens (read with logprobs()); prompt_logprobs adds the prompt positions >= 1."""
         ids = _i32(ids)
         s = MxSampling()
         lib().mx_sampling_default(ctypes.byref(s))
@@ -289,8 +332,29 @@ class Engine:
         if seed is not None and seed >= 0:
             s.seed = seed
         req = ctypes.c_uint64()
-        _check(lib().mx_submit(self._h, ids.ctypes.data, len(ids), ctypes.byref(s), max_tokens, ctypes.byref(req)))
+        if logprobs is None:
+            if prompt_logprobs:
+                raise ValueError("prompt_logprobs needs logprobs=k")
+            _check(lib().mx_submit(self._h, ids.ctypes.data, len(ids), ctypes.byref(s), max_tokens, ctypes.byref(req)))
+        else:
+            _check(lib().mx_submit_lp(self._h, ids.ctypes.data, len(ids), ctypes.byref(s), max_tokens, int(logprobs),
+                                      int(bool(prompt_logprobs)), ctypes.byref(req)))
         return req.value
+
+    def logprobs(self, req: int):
+        """Entries a logprobs= request holds so far (prompt positions first when asked for, then one per
+        generated token; never blocks, valid until wait()): (tok_lp [n], top_lp [n][k], top_idx [n][k])."""
+        n, k = ctypes.c_int32(), ctypes.c_int32()
+        L = lib()
+        _check(L.mx_request_logprobs(self._h, req, None, None, None, 0, ctypes.byref(n), ctypes.byref(k)))
+        cap, kk = n.value, k.value
+        tok = np.empty(cap, dtype=np.float32)
+        top = np.empty((cap, kk), dtype=np.float32)
+        idx = np.empty((cap, kk), dtype=np.int32)
+        if cap:
+            _check(L.mx_request_logprobs(self._h, req, tok.ctypes.data, top.ctypes.data if kk else None,
+                                         idx.ctypes.data if kk else None, cap, ctypes.byref(n), ctypes.byref(k)))
+        return tok, top, idx
 
     def submit_many(self, prompts, max_tokens: int, seeds=None, per_request=None, **kw):
         """Several requests queued atomically (one scheduler round admits them all); same sampling

@@ -106,7 +106,13 @@ class Llama:
                           stream: bool = False, seed: Optional[int] = None,
                           **kwargs: Any) -> Union[Dict[str, Any], Iterator[Dict[str, Any]]]:
         if logprobs is not None:
-            raise NotImplementedError("logprobs are not supported")
+            if logprobs < 0 or logprobs > _engine.TOPK_MAX:
+                raise ValueError(f"logprobs must be 0..{_engine.TOPK_MAX} (llama-cpp-python has no cap; the "
+                                 f"engine's device top-k holds at most {_engine.TOPK_MAX} entries per token)")
+            if stream:
+                raise NotImplementedError("logprobs with stream=True are not supported")
+            if not getattr(self._engine, "supports_logprobs", False):
+                raise NotImplementedError("logprobs are not supported by this engine front")
         if typical_p != 1.0:
             raise NotImplementedError("typical_p != 1.0 is not supported (llama-cpp-python's default 1.0 is)")
         created = int(time.time())
@@ -121,9 +127,11 @@ class Llama:
             max_tokens = self._n_ctx - len(prompt_tokens)
         max_tokens = min(max_tokens, self._n_ctx - len(prompt_tokens))
         sd = seed if seed is not None else self._seed
+        lp_kw = {} if logprobs is None else {"logprobs": int(logprobs), "prompt_logprobs": bool(echo)}
         req = self._engine.submit(prompt_tokens, max_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
                                   min_p=min_p, repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty,
-                                  presence_penalty=presence_penalty, seed=None if sd == LLAMA_DEFAULT_SEED else sd)
+                                  presence_penalty=presence_penalty, seed=None if sd == LLAMA_DEFAULT_SEED else sd,
+                                  **lp_kw)
         stops = [s for s in ([stop] if isinstance(stop, str) else list(stop or [])) if s]
         if stream:
             return self._stream(req, prompt_tokens, stops, cid, created, echo)
@@ -137,6 +145,13 @@ class Llama:
                     break
             if not done:
                 self._engine.cancel(req)
+        lp = None
+        if logprobs is not None:  # the entries live with the request: read them before wait() releases it
+            n, done = 0, False
+            while not done:
+                toks, done = self._engine.poll(req, n)
+                n = len(toks)
+            lp = self._engine.logprobs(req)
         toks, finish = self._engine.wait(req)
         finish_reason = "stop" if finish == _engine.FINISH_STOP else "length"
         if toks and self.tokenizer_.is_eog(toks[-1]) and finish == _engine.FINISH_STOP:
@@ -154,16 +169,62 @@ class Llama:
                 if any(s in t for s in stops):
                     toks = toks[:k]
                     break
+        lp_dict = None
+        if lp is not None:
+            prompt_len = len(prompt) if isinstance(prompt, str) else len(self.detokenize(prompt_tokens).decode(
+                "utf-8", errors="ignore"))
+            lp_dict = self._logprobs_dict(prompt_tokens, toks, lp, int(logprobs), echo, prompt_len)
         if echo:
             text = self.detokenize(prompt_tokens).decode("utf-8", errors="ignore") + text
         if suffix is not None:
             text = text + suffix
         return {
             "id": cid, "object": "text_completion", "created": created, "model": self.model_path,
-            "choices": [{"text": text, "index": 0, "logprobs": None, "finish_reason": finish_reason}],
+            "choices": [{"text": text, "index": 0, "logprobs": lp_dict, "finish_reason": finish_reason}],
             "usage": {"prompt_tokens": len(prompt_tokens), "completion_tokens": len(toks),
                       "total_tokens": len(prompt_tokens) + len(toks)},
         }
+
+    def _logprobs_dict(self, prompt_tokens: List[int], toks: List[int], lp, k: int, echo: bool,
+                       prompt_len: int) -> Dict[str, Any]:
+        """choices[0]["logprobs"] as llama-cpp-python builds it: tokens / text_offset / token_logprobs /
+        top_logprobs over the completion tokens that survived trimming (`toks`) and, with echo, the prompt
+        tokens before them (a leading BOS skipped; the first entry's log-probs are None, the OpenAI quirk).
+        lp = Engine.logprobs(): with echo one entry per prompt position >= 1 first, then one per generated
+        token.  Each token is detokenised with the tokens before it as context -- as the text it adds to
+        the text of those tokens, so the strings joined are the returned text even where a character's
+        bytes span two tokens; text_offset is its character offset in the returned text, without echo
+        offset by the prompt's length."""
+        tok_lp, top_lp, top_idx = lp
+        dec = lambda ids, prev: self.detokenize(ids, prev_tokens=prev).decode("utf-8", errors="ignore")
+        n_p = len(prompt_tokens)
+        if echo:  # listed: the prompt without a leading BOS, then the completion; decoded from the start
+            skip = 1 if n_p and prompt_tokens[0] == self.token_bos() else 0
+            listed, base, off0 = list(prompt_tokens[skip:]) + list(toks), [], 0
+            entry = [p - 1 if p >= 1 else None for p in range(skip, n_p)] + [n_p - 1 + i for i in range(len(toks))]
+        else:
+            listed, base, off0 = list(toks), list(prompt_tokens), prompt_len
+            entry = list(range(len(toks)))
+        tokens, offsets, token_logprobs, top_logprobs = [], [], [], []
+        upto = [""] + [dec(listed[:j + 1], base) for j in range(len(listed))]  # text of the first j listed tokens
+        for j, (t, e) in enumerate(zip(listed, entry)):
+            ctx = base + listed[:j]
+            offsets.append(off0 + len(upto[j]))
+            piece = upto[j + 1][len(upto[j]):]
+            tokens.append(piece)
+            if e is None:
+                token_logprobs.append(None)
+                top_logprobs.append(None)
+                continue
+            top = {dec([int(i)], ctx): float(v) for v, i in zip(top_lp[e][:k], top_idx[e][:k])}
+            top[piece] = float(tok_lp[e])
+            token_logprobs.append(float(tok_lp[e]))
+            top_logprobs.append(top)
+        if echo and tokens:
+            token_logprobs[0] = None
+            top_logprobs[0] = None
+        return {"tokens": tokens, "text_offset": offsets, "token_logprobs": token_logprobs,
+                "top_logprobs": top_logprobs}
 
     def _chunk(self, cid: str, created: int, text: str, finish_reason: Optional[str]) -> Dict[str, Any]:
         return {"id": cid, "object": "text_completion", "created": created, "model": self.model_path,
