@@ -179,6 +179,20 @@ int mx_forward_logprobs(mx_engine* e, int n, const int32_t* slots, const int32_t
  * logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64, V <= 262144; outputs as above. */
 int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl, const int32_t* targets, int k,
                      float* tgt_lp, float* top_lp, int32_t* top_idx);
+/* The production attention launchers on caller-supplied q / K / V, no engine (tests on inputs no model
+ * produces).  Geometry: head_dim 64 or 128, n_head / n_head_kv in {1, 2, 4, 8}; caches of n_slots slots with
+ * ctx_stride = n_ctx rounded up to 64 positions; M rows (1..4096) at pos[i] in [0, n_ctx] (n_ctx: the kernels
+ * clamp it) of slot[i]; scale = 1/sqrt(head_dim).  kcache / vcache: the raw tiled bytes,
+ * n_slots * n_head_kv * ctx_stride * head_dim f16 each, copied to the device verbatim and copied back after
+ * the launch.  out [M][n_head * head_dim], f32 (out_f32 != 0) or bf16, filled with 0xFF bytes before the
+ * launch.  mode 0: the decode attention on final q [M][n_head * head_dim] f32; mode 1: the same launcher
+ * finishing q/k/v from split-K slabs [nslab][M][(n_head + 2 n_head_kv) * head_dim] (1 <= nslab <= 8, M <= 64,
+ * every row its own slot) with rope_cs [n_ctx][head_dim/2][cos, sin] -- it stores each row's K/V into the
+ * caches; mode 2: the prefill attention on final q (rows in 16-row blocks of consecutive positions of one
+ * slot, a block may end in copies of its last row).  Anything else is MX_ERR_ARG and nothing is launched. */
+int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                       const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
+                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out);
 
 /* Device-resident decode batch (benchmark, pipeline stages).  Rows are M
  * sequences in KV slots `slots`, next token ids[i] at position pos[i].

@@ -14,7 +14,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 // still as the wide path's split-K slabs (finished here, see below).  Everything that only the
 // chunk holding `pos` (FIN) or the partial last chunk needs sits behind a wave-uniform branch, so
 // the full chunks run the bare MFMA + softmax stream.
-constexpr int ATTN_FIN_MAXSLAB = 8;  // split-K slabs the FIN path can sum (the wide launchers split K at most 8 ways)
 
 // MS: slabs the FIN path loads (>= a.nslab; the ones past a.nslab re-read the last and add zero)
 template <int D, int G, int NW, bool FIN, int MS = ATTN_FIN_MAXSLAB>

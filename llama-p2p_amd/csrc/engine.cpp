@@ -397,7 +397,7 @@ struct mx_engine {
   // rows form blocks of 16 (from row 0) of one slot each, positions consecutive within a block except
   // that a block may end in copies of its last real row (same position and token: the prompt padding
   // near n_ctx) -- what attn_prefill_kernel needs (every key position a block reads is written by it)
-  bool blocked_rows(const int32_t* slots, const int32_t* pos, const int32_t* ids, int m) const {
+  static bool blocked_rows(const int32_t* slots, const int32_t* pos, const int32_t* ids, int m) {
     for (int k = 0; k < m; k++) {
       if (k % 16 == 0) continue;
       if (slots[k] != slots[k - 1]) return false;
@@ -2511,6 +2511,95 @@ int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl
   std::vector<float> ent((size_t)n * est);
   HIPC(hipMemcpy(ent.data(), d_out, ent.size() * 4, hipMemcpyDeviceToHost));
   split_entries(ent, n, k, tgt_lp, top_lp, top_idx);
+  return 0;
+}
+
+int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                       const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
+                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (mode < 0 || mode > 2 || !pos || !slot || !kcache || !vcache || !out)
+    return fail(MX_ERR_ARG, "mx_attention_probe: mode 0..2, non-null pos / slot / caches / out");
+  if ((head_dim != 64 && head_dim != 128) || n_head_kv < 1 || n_head < n_head_kv || n_head % n_head_kv != 0 ||
+      n_head > 1024)
+    return fail(MX_ERR_ARG, "mx_attention_probe: head_dim 64 or 128, n_head a multiple of n_head_kv");
+  const int G = n_head / n_head_kv;
+  if (G != 1 && G != 2 && G != 4 && G != 8)
+    return fail(MX_ERR_ARG, "mx_attention_probe: n_head / n_head_kv must be 1, 2, 4 or 8");
+  if (n_ctx < 1 || n_ctx > (1 << 20) || n_slots < 1 || n_slots > 4096)
+    return fail(MX_ERR_ARG, "mx_attention_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+  if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_attention_probe: 1 <= M <= PREFILL_ROWS rows");
+  const int ctx_stride = (n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+  const size_t slot_stride = (size_t)n_head_kv * ctx_stride * head_dim;
+  const size_t cache_elems = slot_stride * n_slots;
+  if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_attention_probe: caches above 1 GiB each");
+  for (int i = 0; i < M; i++) {
+    if (slot[i] < 0 || slot[i] >= n_slots) return fail(MX_ERR_ARG, "mx_attention_probe: slot out of range");
+    if (pos[i] < 0 || pos[i] > n_ctx) return fail(MX_ERR_ARG, "mx_attention_probe: position outside [0, n_ctx]");
+  }
+  const size_t nq = (size_t)n_head * head_dim, N = nq + 2 * (size_t)n_head_kv * head_dim;
+  if (mode == 1) {
+    if (!slabs || !rope_cs || nslab < 1 || nslab > ATTN_FIN_MAXSLAB || M > MAX_ROWS)
+      return fail(MX_ERR_ARG, "mx_attention_probe: mode 1 takes slabs, rope_cs, 1 <= nslab <= 8, M <= 64");
+    std::vector<int32_t> sorted(slot, slot + M);  // the engine's rows_distinct condition
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      return fail(MX_ERR_ARG, "mx_attention_probe: mode 1 needs every row in its own slot");
+  } else {
+    if (!q) return fail(MX_ERR_ARG, "mx_attention_probe: modes 0 and 2 take q");
+    if (mode == 2 && !mx_engine::blocked_rows(slot, pos, nullptr, M))
+      return fail(MX_ERR_ARG, "mx_attention_probe: mode 2 needs rows in 16-position blocks of one slot each");
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+  std::vector<void*> owned;
+  auto dalloc = [&](void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) != hipSuccess) return false;
+    owned.push_back(*p);
+    return true;
+  };
+  struct Free {
+    std::vector<void*>& v;
+    ~Free() { for (void* p : v) hipFree(p); }
+  } free_all{owned};
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  float *d_q = nullptr, *d_slabs = nullptr, *d_cs = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr;
+  void* d_out = nullptr;
+  const size_t out_bytes = (size_t)M * nq * (out_f32 ? 4 : 2);
+  const size_t cs_bytes = (size_t)n_ctx * head_dim * 4;
+  if (!dalloc((void**)&d_k, cache_elems * 2) || !dalloc((void**)&d_v, cache_elems * 2) ||
+      !dalloc((void**)&d_pos, (size_t)M * 4) || !dalloc((void**)&d_slot, (size_t)M * 4) || !dalloc(&d_out, out_bytes) ||
+      (mode == 1 ? !dalloc((void**)&d_slabs, (size_t)nslab * M * N * 4) || !dalloc((void**)&d_cs, cs_bytes)
+                 : !dalloc((void**)&d_q, (size_t)M * nq * 4)))
+    return fail(MX_ERR_HIP, "mx_attention_probe: device allocation");
+  HIPC(hipMemcpy(d_k, kcache, cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_v, vcache, cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_pos, pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_slot, slot, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_out, 0xFF, out_bytes));  // an element the kernel never wrote reads back as NaN
+  AttnArgs at{};
+  if (mode == 1) {
+    HIPC(hipMemcpy(d_slabs, slabs, (size_t)nslab * M * N * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_cs, rope_cs, cs_bytes, hipMemcpyHostToDevice));
+    at.slabs = d_slabs; at.nslab = nslab; at.slab_stride = (size_t)M * N; at.rope_cs = d_cs; at.kc_w = d_k;
+    at.vc_w = d_v;
+  } else {
+    HIPC(hipMemcpy(d_q, q, (size_t)M * nq * 4, hipMemcpyHostToDevice));
+  }
+  at.q = d_q; at.kc = d_k; at.vc = d_v; at.pos = d_pos; at.slot = d_slot;
+  if (out_f32) at.outf = (float*)d_out;
+  else at.out = (uint16_t*)d_out;
+  at.ldo = (int)nq; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
+  at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
+  at.scale = 1.0f / sqrtf((float)head_dim);
+  HIPC(hipDeviceSynchronize());
+  if (mode == 2) launch_attention_prefill(at, nullptr);
+  else launch_attention(at, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -22,6 +22,7 @@ constexpr int MAX_ROWS = 64;       // tokens per decode / logits forward (4 colu
 constexpr int PREFILL_ROWS = 4096;  // tokens per prefill forward (GEMM path, no logits): ~0.3 GB of activations for 8B
 constexpr int ATTN_CHUNK = 32;     // positions per attention wave-iteration
 constexpr int KV_POS_ALIGN = 64;   // KV rows per slot are allocated in multiples of this
+constexpr int ATTN_FIN_MAXSLAB = 8;  // split-K slabs the attention's FIN path can sum (the wide launchers split K at most 8 ways)
 
 enum Epilogue : int {
   EPI_F32 = 0,     // out[col][row] = acc                         (lm_head logits)

@@ -30,6 +30,7 @@ EXPORTS = [
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
+    "mx_attention_probe",
 ]
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
 
@@ -163,6 +164,8 @@ def lib() -> ctypes.CDLL:
         L.mx_request_logprobs.argtypes = [vp, u64, vp, vp, vp, i32, P(i32), P(i32)]
         L.mx_forward_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.mx_attention_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
+                                         vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -213,6 +216,50 @@ def logprob_probe(logits, targets, k: int, V: Optional[int] = None, device: int 
     _check(lib().mx_logprob_probe(device, lg.ctypes.data, n, V, ldl, tg.ctypes.data, k, tgt.ctypes.data,
                                   top.ctypes.data if ke else None, idx.ctypes.data if ke else None))
     return tgt, top, idx
+
+
+KV_POS_ALIGN = 64  # kernels.h: KV positions per slot are allocated in multiples of this
+
+
+def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot,
+                    kcache, vcache, q=None, slabs=None, rope_cs=None, out_f32: bool = True, device: int = 0):
+    """The production attention launchers on caller-supplied q / K / V (no engine; include/mx_engine.h
+    mx_attention_probe).  kcache / vcache: the raw tiled f16 bits (uint16) of n_slots x n_head_kv x ctx_stride x
+    head_dim elements each, left untouched.  mode 0 / 2: q [M][n_head * head_dim] f32 (decode / prefill
+    kernel); mode 1: slabs [nslab][M][(n_head + 2 n_head_kv) * head_dim] f32 and rope_cs [n_ctx][head_dim/2][2].
+    Returns (out [M][n_head * head_dim] as f32 -- a bf16 output widened exactly --, kcache after, vcache after)."""
+    pos, slot = _i32(pos), _i32(slot)
+    M = len(pos)
+    if len(slot) != M:
+        raise ValueError("one slot per row")
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    elems = max(n_slots, 0) * max(n_head_kv, 0) * ctx_stride * max(head_dim, 0)
+    kc = np.array(kcache, dtype=np.uint16, copy=True).reshape(-1)
+    vc = np.array(vcache, dtype=np.uint16, copy=True).reshape(-1)
+    if kc.size != elems or vc.size != elems:
+        raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+    nq, N = n_head * head_dim, (n_head + 2 * n_head_kv) * head_dim
+    qa = sa = ca = None
+    nslab = 0
+    if mode == 1:
+        sa = np.ascontiguousarray(slabs, dtype=np.float32)
+        ca = np.ascontiguousarray(rope_cs, dtype=np.float32)
+        nslab = sa.shape[0]
+        if sa.shape != (nslab, M, N) or ca.size != max(n_ctx, 0) * head_dim:
+            raise ValueError("slabs [nslab][M][n_q + 2 n_kv] and rope_cs [n_ctx][head_dim/2][2] expected")
+    else:
+        qa = np.ascontiguousarray(q, dtype=np.float32)
+        if qa.size != M * nq:
+            raise ValueError("q [M][n_head * head_dim] expected")
+    out = np.empty((M, max(nq, 0)), dtype=np.float32 if out_f32 else np.uint16)
+    _check(lib().mx_attention_probe(device, mode, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
+                                    slot.ctypes.data, int(bool(out_f32)), qa.ctypes.data if qa is not None else None,
+                                    sa.ctypes.data if sa is not None else None, nslab,
+                                    ca.ctypes.data if ca is not None else None, kc.ctypes.data, vc.ctypes.data,
+                                    out.ctypes.data))
+    if not out_f32:
+        out = (out.astype(np.uint32) << 16).view(np.float32)
+    return out, kc, vc
 
 
 def _check(rc: int):
