@@ -194,6 +194,66 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
                        int nslab, const float* rope_cs, void* kcache, void* vcache, void* out);
 
+/* The production bf16 matmul launchers on caller-supplied W / X, no engine (tests on shapes no model has).
+ * path 0 launch_mm (M 1..64), 1 launch_mm_pers (M 1..16, shapes of mx_matmul_plan's pers_ok), 2 launch_mm_wide
+ * (M 1..64), 3 launch_mm_wide with full_chain, 4 launch_gemm_split (M 65..4096 as in the engine, `target`
+ * 0..256 work-groups, slab space `slab_floats` <= 2^26; act_f32 only with target 0: the split finish writes
+ * bf16).  epi: 0 F32, 1 RESID, 2 QKV, 3 SWIGLU.  w: bf16 [N][K] row-major in GGUF order (N % 16,
+ * K % 32; SWIGLU: rows [0, N/2) ffn_gate, [N/2, N) ffn_up), packed on the device with launch_pack as at model
+ * load (packed_out, optional, receives the N*K packed bf16).  Activations: x bf16 [M][K] -- the device buffer
+ * has 16 / 32 / 64 rows for M <= 16 / 32 / 64 (else M rounded up to 16), rows >= M hold bf16 NaN -- or, paths
+ * 0 and 1 with M <= 4 and not RESID, RMS_NORM on load: xf f32 [M][K], norm_w f32 [K], eps (the sum-of-squares
+ * partials come from launch_ssq, as for an embedded row).
+ * out: [M + 64][ld] elements, filled with 0xFF bytes before the launch (rows >= M are a guard that must
+ * come back as 0xFF): F32 f32, ld N; RESID f32, ld N, rows < M start as resid [M][N] and return updated (the
+ * split paths 2, 3 and a split path 4 fold their partials with launch_resid_norm, as the engine does); SWIGLU
+ * bf16 (act_f32: f32), ld N/2; QKV q f32, ld n_head * head_dim, with N = (n_head + 2 n_head_kv) * head_dim,
+ * head_dim 64 or 128, pos[M] in [0, n_ctx], slot[M] in [0, n_slots), rope_cs [n_ctx][head_dim/2][cos, sin] and
+ * the raw tiled caches as in mx_attention_probe (copied back after the launch).
+ * ssq_out (RESID, paths 0 and 1, optional): the [M][N/16] sum-of-squares partials the epilogue writes.
+ * slabs_out (optional, slabs_cap floats): paths 2 / 3 with QKV or RESID: the raw split-K partials [split][M][N]
+ * as the launcher left them (QKV: before launch_qkv_finish runs), slabs_cap >= kgroups * M * N; path 4: the
+ * whole slab space (slabs_cap >= slab_floats), 0xFF where nothing was written.  *split_out: what the launcher
+ * returned.  Everything a kernel indexes with is checked before any launch (MX_ERR_ARG, nothing launched); a
+ * launcher that refuses the shape gives MX_ERR_ARG with its name in mx_last_error(). */
+typedef struct {
+  int32_t path, epi, M, N, K;
+  const void* w;
+  const void* x;
+  const float* xf;
+  const float* norm_w;
+  float eps;
+  int32_t target;
+  uint64_t slab_floats;
+  int32_t want_ssq, act_f32;
+  int32_t n_head, n_head_kv, head_dim, n_ctx, n_slots;
+  const int32_t* pos;
+  const int32_t* slot;
+  const float* rope_cs;
+  void* kcache;
+  void* vcache;
+  const float* resid;
+  void* out;
+  float* ssq_out;
+  float* slabs_out;
+  uint64_t slabs_cap;
+  int32_t* split_out;
+  void* packed_out;
+} mx_matmul_args;
+int mx_matmul_probe(int device, const mx_matmul_args* a);
+/* The dispatch facts of a bf16 matmul shape, no GPU needed: *kgroups = canon_kgroups(epi, N, K) (the K split
+ * of the 17..64-row launch = the canonical K grouping), *pers_ok = mm_pers_supported(epi, M, N, K),
+ * *norm_on_load_ok = mm_can_norm_on_load(M, K), *gemm_ok = gemm_supported(N, K).  Any pointer may be NULL. */
+int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers_ok, int32_t* norm_on_load_ok,
+                   int32_t* gemm_ok);
+/* launch_resid_norm (row_map NULL) / launch_rmsnorm (row_map given, nslab 0) on caller-supplied rows, no
+ * engine.  x f32 [rows][n] (n % 64, n <= 16384, rows 1..4096); slabs [nslab][rows][n] (0 <= nslab <= 16) are
+ * folded into x in slab order; w f32 [n] (optional): y = bf16(rmsnorm(x, eps) * w) [M][n]; row_map [M] (entries
+ * in [0, rows)): y row i is made from x row row_map[i]; without it M = rows.  x_out [rows + 64][n] and y_out
+ * [M + 64][n] start as 0xFF bytes (x_out rows < rows as x) and return whole.  Anything else: MX_ERR_ARG. */
+int mx_norm_probe(int device, int rows, int n, int M, const float* x, const float* slabs, int nslab, const float* w,
+                  const int32_t* row_map, float eps, float* x_out, void* y_out);
+
 /* Device-resident decode batch (benchmark, pipeline stages).  Rows are M
  * sequences in KV slots `slots`, next token ids[i] at position pos[i].
  * mx_batch_step runs one decode step on `stream` (NULL = engine stream):

@@ -2603,6 +2603,282 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
   return 0;
 }
 
+namespace {
+struct DevBufs {  // device allocations of a probe call, freed on every return path
+  std::vector<void*> v;
+  ~DevBufs() { for (void* p : v) hipFree(p); }
+  bool alloc(void* pp, size_t bytes) {  // pp: address of the (typed) device pointer to set
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return false;
+    v.push_back(q);
+    *static_cast<void**>(pp) = q;
+    return true;
+  }
+};
+constexpr int PROBE_GUARD_ROWS = 64;  // rows of 0xFF after every probe output, returned to the caller
+}  // namespace
+
+int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers_ok, int32_t* norm_on_load_ok,
+                   int32_t* gemm_ok) {
+  if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || N < TILE_N || N % TILE_N || K < TILE_K || K % TILE_K)
+    return fail(MX_ERR_ARG, "mx_matmul_plan: epi 0..3, M >= 1, N a multiple of 16, K a multiple of 32");
+  if (kgroups) *kgroups = canon_kgroups(epi, N, K);
+  if (pers_ok) *pers_ok = mm_pers_supported(epi, M, N, K);
+  if (norm_on_load_ok) *norm_on_load_ok = mm_can_norm_on_load(M, K);
+  if (gemm_ok) *gemm_ok = gemm_supported(N, K);
+  return 0;
+}
+
+int mx_matmul_probe(int device, const mx_matmul_args* pa) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (!pa) return fail(MX_ERR_ARG, "mx_matmul_probe: null arguments");
+  const mx_matmul_args& p = *pa;
+  const int path = p.path, epi = p.epi, M = p.M, N = p.N, K = p.K;
+  if (path < 0 || path > 4 || epi < EPI_F32 || epi > EPI_SWIGLU)
+    return fail(MX_ERR_ARG, "mx_matmul_probe: path 0..4, epi 0..3");
+  if (N < TILE_N || N % TILE_N || K < TILE_K || K % TILE_K || N > (1 << 18) || K > 32768 ||
+      (size_t)N * K > ((size_t)1 << 30))
+    return fail(MX_ERR_ARG, "mx_matmul_probe: N a multiple of 16 (<= 2^18), K a multiple of 32 (<= 32768), N*K <= 2^30");
+  const int min_m = path == 4 ? MAX_ROWS + 1 : 1;
+  const int max_m = path == 1 ? 16 : path == 4 ? PREFILL_ROWS : MAX_ROWS;
+  if (M < min_m || M > max_m)
+    return fail(MX_ERR_ARG, "mx_matmul_probe: M 1..64 (path 1: 1..16; path 4: 65..4096)");
+  if (!p.w || !p.out) return fail(MX_ERR_ARG, "mx_matmul_probe: w and out are required");
+  const bool nol = p.x == nullptr;  // RMS_NORM on load
+  if (nol) {
+    if (path > 1 || M > 4 || epi == EPI_RESID || !p.xf || !p.norm_w)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: without x: paths 0 / 1, M <= 4, not RESID, xf and norm_w given");
+    if (K % 64 || K / 16 > 512 || (path == 0 && !mm_can_norm_on_load(M, K)))
+      return fail(MX_ERR_ARG, "mx_matmul_probe: K has no RMS_NORM-on-load form");
+  }
+  if (p.act_f32 && (epi != EPI_SWIGLU || (path == 4 && p.target > 0)))
+    return fail(MX_ERR_ARG, "mx_matmul_probe: act_f32 is SWIGLU's, and the GEMM's split finish writes bf16 only");
+  if (p.want_ssq && (epi != EPI_RESID || path > 1 || !p.ssq_out))
+    return fail(MX_ERR_ARG, "mx_matmul_probe: want_ssq: RESID on paths 0 / 1, with ssq_out");
+  const bool split_path = path >= 2 && (epi == EPI_QKV || epi == EPI_RESID || (path == 4 && epi == EPI_SWIGLU));
+  if (epi == EPI_RESID) {
+    if (!p.resid) return fail(MX_ERR_ARG, "mx_matmul_probe: RESID takes resid [M][N]");
+    if (path >= 2 && (N % 64 || N > 16384))  // launch_resid_norm's widths
+      return fail(MX_ERR_ARG, "mx_matmul_probe: RESID on a split path: N a multiple of 64, <= 16384");
+  }
+  int n_q = 0, n_kv = 0, ctx_stride = 0;
+  size_t slot_stride = 0, cache_elems = 0;
+  if (epi == EPI_QKV) {
+    if (!p.pos || !p.slot || !p.rope_cs || !p.kcache || !p.vcache)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: QKV takes pos, slot, rope_cs and both caches");
+    if ((p.head_dim != 64 && p.head_dim != 128) || p.n_head < 1 || p.n_head_kv < 1 || p.n_head > 1024 ||
+        p.n_head_kv > 1024 || (long long)(p.n_head + 2 * p.n_head_kv) * p.head_dim != N)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: head_dim 64 or 128, N = (n_head + 2 n_head_kv) * head_dim");
+    if (p.n_ctx < 1 || p.n_ctx > (1 << 20) || p.n_slots < 1 || p.n_slots > 4096)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+    n_q = p.n_head * p.head_dim;
+    n_kv = p.n_head_kv * p.head_dim;
+    ctx_stride = (p.n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+    slot_stride = (size_t)p.n_head_kv * ctx_stride * p.head_dim;
+    cache_elems = slot_stride * p.n_slots;
+    if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_matmul_probe: caches above 1 GiB each");
+    for (int i = 0; i < M; i++) {
+      if (p.slot[i] < 0 || p.slot[i] >= p.n_slots) return fail(MX_ERR_ARG, "mx_matmul_probe: slot out of range");
+      if (p.pos[i] < 0 || p.pos[i] > p.n_ctx) return fail(MX_ERR_ARG, "mx_matmul_probe: position outside [0, n_ctx]");
+    }
+  }
+  // split-K slab space, sized before any launch: the launchers' own split can never exceed it
+  size_t slab_stride = 0, slab_total = 0;
+  int kg = 0;
+  if (split_path && path != 4) {
+    kg = canon_kgroups(epi, N, K);
+    if (kg < 1 || kg > 16) return fail(MX_ERR_ARG, "mx_matmul_probe: K split above 16");
+    slab_stride = (size_t)MAX_ROWS * N;
+    slab_total = slab_stride * kg;
+    if (p.slabs_out && p.slabs_cap < (uint64_t)kg * M * N)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: slabs_out holds fewer than kgroups * M * N floats");
+  } else if (path == 4) {
+    if (p.target < 0 || p.target > 256 || p.slab_floats > ((uint64_t)1 << 26))
+      return fail(MX_ERR_ARG, "mx_matmul_probe: path 4: target 0..256, slab_floats <= 2^26");
+    slab_total = epi == EPI_F32 ? 0 : (size_t)p.slab_floats;
+    if (p.slabs_out && p.slabs_cap < slab_total)
+      return fail(MX_ERR_ARG, "mx_matmul_probe: slabs_out holds fewer than slab_floats floats");
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+
+  DevBufs dev;
+  const size_t wbytes = (size_t)N * K * 2;
+  uint16_t *d_src = nullptr, *d_w = nullptr, *d_x = nullptr;
+  float *d_xf = nullptr, *d_nw = nullptr, *d_ssq = nullptr, *d_slabs = nullptr, *d_cs = nullptr;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr;
+  uint8_t* d_out = nullptr;
+  const int ld = epi == EPI_SWIGLU ? N / 2 : epi == EPI_QKV ? n_q : N;
+  const size_t esz = (epi == EPI_SWIGLU && !p.act_f32) ? 2 : 4;
+  const size_t out_bytes = (size_t)(M + PROBE_GUARD_ROWS) * ld * esz;
+  const int xrows = M <= 16 ? 16 : M <= 32 ? 32 : M <= 64 ? 64 : (M + 15) / 16 * 16;
+  const int np = nol ? K / 16 : N / 16;
+  const size_t ssq_bytes = (size_t)(nol ? 4 : M + PROBE_GUARD_ROWS) * np * 4;
+  if (!dev.alloc(&d_src, wbytes) || !dev.alloc(&d_w, wbytes) || !dev.alloc(&d_out, out_bytes))
+    return fail(MX_ERR_HIP, "mx_matmul_probe: device allocation");
+  if (nol ? (!dev.alloc(&d_xf, (size_t)4 * K * 4) || !dev.alloc(&d_nw, (size_t)K * 4))
+          : !dev.alloc(&d_x, (size_t)xrows * K * 2))
+    return fail(MX_ERR_HIP, "mx_matmul_probe: device allocation");
+  if ((nol || p.want_ssq) && !dev.alloc(&d_ssq, ssq_bytes)) return fail(MX_ERR_HIP, "mx_matmul_probe: device allocation");
+  if (slab_total && !dev.alloc(&d_slabs, slab_total * 4)) return fail(MX_ERR_HIP, "mx_matmul_probe: device allocation");
+  if (epi == EPI_QKV &&
+      (!dev.alloc(&d_k, cache_elems * 2) || !dev.alloc(&d_v, cache_elems * 2) || !dev.alloc(&d_pos, (size_t)M * 4) ||
+       !dev.alloc(&d_slot, (size_t)M * 4) || !dev.alloc(&d_cs, (size_t)p.n_ctx * p.head_dim * 4)))
+    return fail(MX_ERR_HIP, "mx_matmul_probe: device allocation");
+
+  // weights: packed on the device exactly as upload_packed does at model load
+  HIPC(hipMemcpy(d_src, p.w, wbytes, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_w, 0xFF, wbytes));
+  if (epi == EPI_SWIGLU) {
+    launch_pack(d_w, d_src, N / 2, K, PACK_GATE, 0, nullptr);
+    launch_pack(d_w, d_src + (size_t)(N / 2) * K, N / 2, K, PACK_UP, 0, nullptr);
+  } else {
+    launch_pack(d_w, d_src, N, K, PACK_ROWS, 0, nullptr);
+  }
+  HIPC(hipGetLastError());
+  // an element no kernel wrote reads back as 0xFF bytes (NaN); activation rows >= M are bf16 NaN
+  HIPC(hipMemset(d_out, 0xFF, out_bytes));
+  if (epi == EPI_RESID) HIPC(hipMemcpy(d_out, p.resid, (size_t)M * N * 4, hipMemcpyHostToDevice));
+  if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, ssq_bytes));
+  if (d_slabs) HIPC(hipMemset(d_slabs, 0xFF, slab_total * 4));
+  MMArgs a{};
+  a.W = d_w; a.N = N; a.K = K; a.M = M; a.eps = p.eps;
+  if (nol) {
+    HIPC(hipMemset(d_xf, 0xFF, (size_t)4 * K * 4));
+    HIPC(hipMemcpy(d_xf, p.xf, (size_t)M * K * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_nw, p.norm_w, (size_t)K * 4, hipMemcpyHostToDevice));
+    launch_ssq(d_xf, M, K, d_ssq, nullptr);  // the partials as the embedding writes them
+    a.xf = d_xf; a.norm_w = d_nw; a.ssq = d_ssq; a.np = np;
+  } else {
+    HIPC(hipMemset(d_x, 0xFF, (size_t)xrows * K * 2));
+    HIPC(hipMemcpy(d_x, p.x, (size_t)M * K * 2, hipMemcpyHostToDevice));
+    a.X = d_x; a.ldx = K;
+    if (p.want_ssq) a.ssq = d_ssq, a.np = np;
+  }
+  if (epi == EPI_SWIGLU) {
+    if (p.act_f32) a.actf = (float*)d_out;
+    else a.act = (uint16_t*)d_out;
+    a.lda = ld;
+  } else {
+    a.out = (float*)d_out; a.ldo = ld;
+  }
+  if (epi == EPI_QKV) {
+    HIPC(hipMemcpy(d_k, p.kcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_v, p.vcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_pos, p.pos, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_slot, p.slot, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_cs, p.rope_cs, (size_t)p.n_ctx * p.head_dim * 4, hipMemcpyHostToDevice));
+    a.n_q = n_q; a.n_kv = n_kv; a.head_dim = p.head_dim; a.pos = d_pos; a.slot = d_slot; a.rope_cs = d_cs;
+    a.kc = d_k; a.vc = d_v; a.n_ctx = p.n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = p.n_head_kv;
+    a.slot_stride = slot_stride;
+  }
+  HIPC(hipDeviceSynchronize());
+
+  int rc = -1;
+  const char* who = "";
+  std::vector<float> slab_host;  // the raw partials, taken before anything folds or finishes them
+  auto grab_slabs = [&](int nslab, size_t stride) -> int {
+    if (!p.slabs_out) return 0;
+    HIPC(hipDeviceSynchronize());
+    slab_host.resize((size_t)nslab * M * N);
+    for (int k = 0; k < nslab; k++)
+      HIPC(hipMemcpy(slab_host.data() + (size_t)k * M * N, d_slabs + k * stride, (size_t)M * N * 4,
+                     hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (path == 0) {
+    who = "launch_mm";
+    rc = launch_mm(epi, a, nullptr);
+  } else if (path == 1) {
+    who = "launch_mm_pers";
+    rc = launch_mm_pers(epi, a, nullptr);
+  } else if (path == 2 || path == 3) {
+    who = "launch_mm_wide";
+    rc = launch_mm_wide(epi, a, d_slabs, slab_stride, nullptr, false, path == 3);
+    if (rc >= 0 && split_path) {
+      if (rc < 1 || rc > kg) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_STATE, "launch_mm_wide split " + std::to_string(rc) + " outside canon_kgroups " +
+                                      std::to_string(kg));
+      }
+      if (int e2 = grab_slabs(rc, slab_stride)) return e2;
+      if (epi == EPI_QKV) launch_qkv_finish(a, d_slabs, rc, slab_stride, nullptr);
+      else launch_resid_norm(nullptr, 0, (float*)d_out, d_slabs, rc, slab_stride, nullptr, M, N, p.eps, nullptr);
+    }
+  } else {
+    who = "launch_gemm_split";
+    rc = launch_gemm_split(epi, a, d_slabs, slab_total, p.target, nullptr);
+    if (rc > 0 && epi == EPI_RESID)  // the engine's fold (slab stride M * N)
+      launch_resid_norm(nullptr, 0, (float*)d_out, d_slabs, rc, (size_t)M * N, nullptr, M, N, p.eps, nullptr);
+  }
+  if (rc < 0) {
+    hipDeviceSynchronize();
+    return fail(MX_ERR_ARG, std::string("mx_matmul_probe: ") + who + " refused the shape");
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(p.out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  if (p.want_ssq) HIPC(hipMemcpy(p.ssq_out, d_ssq, (size_t)M * np * 4, hipMemcpyDeviceToHost));
+  if (p.slabs_out) {
+    if (path == 4) {
+      if (slab_total) HIPC(hipMemcpy(p.slabs_out, d_slabs, slab_total * 4, hipMemcpyDeviceToHost));
+    } else if (!slab_host.empty()) {
+      memcpy(p.slabs_out, slab_host.data(), slab_host.size() * 4);
+    }
+  }
+  if (p.split_out) *p.split_out = rc;
+  if (p.packed_out) HIPC(hipMemcpy(p.packed_out, d_w, wbytes, hipMemcpyDeviceToHost));
+  if (epi == EPI_QKV) {
+    HIPC(hipMemcpy(p.kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(p.vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int mx_norm_probe(int device, int rows, int n, int M, const float* x, const float* slabs, int nslab, const float* w,
+                  const int32_t* row_map, float eps, float* x_out, void* y_out) {
+  if (rows < 1 || rows > PREFILL_ROWS || !x || !x_out)
+    return fail(MX_ERR_ARG, "mx_norm_probe: 1 <= rows <= 4096, x and x_out required");
+  if (n < 64 || n % 64 || n > 16384) return fail(MX_ERR_ARG, "mx_norm_probe: n a multiple of 64, <= 16384");
+  if (nslab < 0 || nslab > 16 || (nslab > 0 && !slabs))
+    return fail(MX_ERR_ARG, "mx_norm_probe: 0 <= nslab <= 16, slabs given when nslab > 0");
+  if (w && !y_out) return fail(MX_ERR_ARG, "mx_norm_probe: w needs y_out");
+  if (row_map) {
+    if (nslab || !w || M < 1 || M > PREFILL_ROWS)
+      return fail(MX_ERR_ARG, "mx_norm_probe: row_map: no slabs, w given, 1 <= M <= 4096");
+    for (int i = 0; i < M; i++)
+      if (row_map[i] < 0 || row_map[i] >= rows) return fail(MX_ERR_ARG, "mx_norm_probe: row_map entry out of range");
+  } else if (M != rows) {
+    return fail(MX_ERR_ARG, "mx_norm_probe: without row_map M == rows");
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  float *d_x = nullptr, *d_slabs = nullptr, *d_w = nullptr;
+  uint16_t* d_y = nullptr;
+  int* d_map = nullptr;
+  const size_t xb = (size_t)(rows + PROBE_GUARD_ROWS) * n * 4, yb = (size_t)(M + PROBE_GUARD_ROWS) * n * 2;
+  const size_t stride = (size_t)rows * n;
+  if (!dev.alloc(&d_x, xb) || (nslab && !dev.alloc(&d_slabs, stride * nslab * 4)) ||
+      (w && (!dev.alloc(&d_w, (size_t)n * 4) || !dev.alloc(&d_y, yb))) || (row_map && !dev.alloc(&d_map, (size_t)M * 4)))
+    return fail(MX_ERR_HIP, "mx_norm_probe: device allocation");
+  HIPC(hipMemset(d_x, 0xFF, xb));
+  HIPC(hipMemcpy(d_x, x, stride * 4, hipMemcpyHostToDevice));
+  if (nslab) HIPC(hipMemcpy(d_slabs, slabs, stride * nslab * 4, hipMemcpyHostToDevice));
+  if (w) {
+    HIPC(hipMemcpy(d_w, w, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_y, 0xFF, yb));
+  }
+  if (row_map) HIPC(hipMemcpy(d_map, row_map, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  if (row_map) launch_rmsnorm(d_y, n, d_x, d_w, d_map, M, n, eps, nullptr);
+  else launch_resid_norm(d_y, n, d_x, d_slabs, nslab, stride, d_w, M, n, eps, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(x_out, d_x, xb, hipMemcpyDeviceToHost));
+  if (w) HIPC(hipMemcpy(y_out, d_y, yb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int mx_wait(mx_engine* e, uint64_t req, int32_t* out_ids, int cap, int* n_out, int* finish) {
   if (!e) return fail(MX_ERR_ARG, "null engine");
   std::unique_ptr<Request> r;

@@ -1112,6 +1112,8 @@ static int wide_split(int epi, int N, int K, int* cfg_out) {
   static const int t_res = getenv("MX_WIDE_RESID_SPLIT") ? atoi(getenv("MX_WIDE_RESID_SPLIT")) : 0;
   if (epi == EPI_QKV && t_qkv > 0) target = t_qkv;
   if (epi == EPI_RESID && t_res > 0) target = t_res;
+  // the engine's slab buffer and the attention's FIN path hold ATTN_FIN_MAXSLAB partials: no override above it
+  target = std::min(target, ATTN_FIN_MAXSLAB);
   if (cfg_out) *cfg_out = cfg;
   return KT % 4 ? 0 : pick_ksplit(KT, target);
 }

@@ -30,7 +30,7 @@ EXPORTS = [
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
-    "mx_attention_probe",
+    "mx_attention_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
 ]
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
 
@@ -66,6 +66,17 @@ class MxSampling(ctypes.Structure):
 class MxRowSampler(ctypes.Structure):
     _fields_ = [("s", MxSampling), ("seed", ctypes.c_uint64), ("n_drawn", ctypes.c_int32), ("n_win", ctypes.c_int32),
                 ("win", ctypes.c_int32 * 64)]
+
+
+class MxMatmulArgs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "epi", "M", "N", "K")] + \
+               [(n, ctypes.c_void_p) for n in ("w", "x", "xf", "norm_w")] + \
+               [("eps", ctypes.c_float), ("target", ctypes.c_int32), ("slab_floats", ctypes.c_uint64),
+                ("want_ssq", ctypes.c_int32), ("act_f32", ctypes.c_int32)] + \
+               [(n, ctypes.c_int32) for n in ("n_head", "n_head_kv", "head_dim", "n_ctx", "n_slots")] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "slot", "rope_cs", "kcache", "vcache", "resid", "out", "ssq_out",
+                                               "slabs_out")] + \
+               [("slabs_cap", ctypes.c_uint64), ("split_out", ctypes.c_void_p), ("packed_out", ctypes.c_void_p)]
 
 
 def sampling(temperature: float = 0.0, top_k: int = 40, top_p: float = 0.95, min_p: float = 0.05,
@@ -166,6 +177,9 @@ def lib() -> ctypes.CDLL:
         L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
         L.mx_attention_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
                                          vp]
+        L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
+        L.mx_matmul_plan.argtypes = [i32, i32, i32, i32, P(i32), P(i32), P(i32), P(i32)]
+        L.mx_norm_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_float, vp, vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -260,6 +274,167 @@ def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
     return out, kc, vc
+
+
+EPI_F32, EPI_RESID, EPI_QKV, EPI_SWIGLU = 0, 1, 2, 3  # kernels.h Epilogue
+PROBE_GUARD_ROWS = 64  # rows of 0xFF bytes the probes return after every output
+
+
+def matmul_plan(epi: int, M: int, N: int, K: int) -> dict:
+    """Dispatch facts of a bf16 matmul shape (mx_matmul_plan; no GPU): kgroups, pers_ok, norm_on_load_ok,
+    gemm_ok."""
+    v = [ctypes.c_int32() for _ in range(4)]
+    _check(lib().mx_matmul_plan(epi, M, N, K, *[ctypes.byref(c) for c in v]))
+    return {"kgroups": v[0].value, "pers_ok": bool(v[1].value), "norm_on_load_ok": bool(v[2].value),
+            "gemm_ok": bool(v[3].value)}
+
+
+class MatmulResult:
+    """out [M][ld] (f32, or the raw bf16 bits for a bf16 SWIGLU act), guard [64][ld] (the same dtype: must be
+    all-ones bits), split (what the launcher returned), ssq [M][N/16], slabs ([split][M][N] on paths 2 / 3, the
+    flat slab space on path 4), packed (uint16 [N*K]), kcache / vcache (after the launch)."""
+    out = guard = ssq = slabs = packed = kcache = vcache = None
+    split = 0
+
+
+def matmul_probe(path: int, epi: int, w, x=None, *, xf=None, norm_w=None, eps: float = 0.0, resid=None, qkv=None,
+                 want_ssq: bool = False, act_f32: bool = False, target: int = 0, slab_floats: int = 0,
+                 want_slabs: bool = False, want_packed: bool = False, out=None, device: int = 0) -> MatmulResult:
+    """A production bf16 matmul launcher on caller-supplied operands (no engine; include/mx_engine.h
+    mx_matmul_probe).  w: bf16 bits (uint16) [N][K] in GGUF order; x: bf16 bits [M][K], or xf f32 [M][K] with
+    norm_w f32 [K] (RMS_NORM on load); resid f32 [M][N] (RESID); qkv: dict(n_head, n_head_kv, head_dim, n_ctx,
+    n_slots, pos, slot, rope_cs, kcache, vcache) with the caches as in attention_probe.  out (optional): a
+    caller-owned buffer for the [M + 64][ld] result (tests of refusals)."""
+    wa = np.ascontiguousarray(w, dtype=np.uint16)
+    N, K = wa.shape
+    xa = fa = na = ra = None
+    if x is not None:
+        xa = np.ascontiguousarray(x, dtype=np.uint16)
+        M = xa.shape[0]
+        if xa.ndim != 2 or xa.shape[1] != K:
+            raise ValueError("x [M][K] expected")
+    else:
+        if xf is None:
+            raise ValueError("x or xf expected")
+        fa = np.ascontiguousarray(xf, dtype=np.float32)
+        M = fa.shape[0]
+        if fa.ndim != 2 or fa.shape[1] != K:
+            raise ValueError("xf [M][K] expected")
+        if norm_w is not None:
+            na = np.ascontiguousarray(norm_w, dtype=np.float32)
+            if na.size != K:
+                raise ValueError("norm_w [K] expected")
+    a = MxMatmulArgs()
+    a.path, a.epi, a.M, a.N, a.K = path, epi, M, N, K
+    a.w = wa.ctypes.data
+    a.x = xa.ctypes.data if xa is not None else None
+    a.xf = fa.ctypes.data if fa is not None else None
+    a.norm_w = na.ctypes.data if na is not None else None
+    a.eps, a.target, a.slab_floats = eps, target, slab_floats
+    a.want_ssq, a.act_f32 = int(bool(want_ssq)), int(bool(act_f32))
+    ld = N
+    keep = [wa, xa, fa, na]
+    kc = vc = None
+    if resid is not None:
+        ra = np.ascontiguousarray(resid, dtype=np.float32)
+        if ra.shape != (M, N):
+            raise ValueError("resid [M][N] expected")
+        a.resid = ra.ctypes.data
+        keep.append(ra)
+    if epi == EPI_SWIGLU:
+        ld = N // 2
+    if qkv is not None:
+        g = qkv
+        a.n_head, a.n_head_kv, a.head_dim = g["n_head"], g["n_head_kv"], g["head_dim"]
+        a.n_ctx, a.n_slots = g["n_ctx"], g["n_slots"]
+        ld = max(g["n_head"] * g["head_dim"], 1)
+        for name in ("pos", "slot"):
+            if g.get(name) is not None:
+                arr = _i32(g[name])
+                if len(arr) != M:
+                    raise ValueError(f"one {name} per row")
+                setattr(a, name, arr.ctypes.data)
+                keep.append(arr)
+        if g.get("rope_cs") is not None:
+            cs = np.ascontiguousarray(g["rope_cs"], dtype=np.float32)
+            if cs.size != max(g["n_ctx"], 0) * g["head_dim"]:
+                raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
+            a.rope_cs = cs.ctypes.data
+            keep.append(cs)
+        stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+        elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
+        if g.get("kcache") is not None and g.get("vcache") is not None:
+            kc = np.array(g["kcache"], dtype=np.uint16, copy=True).reshape(-1)
+            vc = np.array(g["vcache"], dtype=np.uint16, copy=True).reshape(-1)
+            if kc.size != elems or vc.size != elems:
+                raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+            a.kcache, a.vcache = kc.ctypes.data, vc.ctypes.data
+    dt = np.uint16 if (epi == EPI_SWIGLU and not act_f32) else np.float32
+    rows = max(M, 0) + PROBE_GUARD_ROWS
+    if out is None:
+        ob = np.zeros((rows, ld), dtype=dt)
+    else:
+        ob = out
+        if not ob.flags.c_contiguous or ob.nbytes < rows * ld * np.dtype(dt).itemsize:
+            raise ValueError("out too small")
+    a.out = ob.ctypes.data
+    r = MatmulResult()
+    ssq = slabs = packed = None
+    split = ctypes.c_int32(0)
+    a.split_out = ctypes.addressof(split)
+    if want_ssq:
+        ssq = np.zeros((max(M, 0), N // 16), dtype=np.float32)
+        a.ssq_out = ssq.ctypes.data
+    if want_slabs:
+        cap = slab_floats if path == 4 else 16 * max(M, 0) * N
+        slabs = np.zeros(max(cap, 1), dtype=np.float32)
+        a.slabs_out, a.slabs_cap = slabs.ctypes.data, cap
+    if want_packed:
+        packed = np.zeros(N * K, dtype=np.uint16)
+        a.packed_out = packed.ctypes.data
+    _check(lib().mx_matmul_probe(device, ctypes.byref(a)))
+    del keep
+    flat = ob.reshape(-1).view(dt)[:rows * ld].reshape(rows, ld)
+    r.out, r.guard, r.split = flat[:M], flat[M:], split.value
+    r.ssq, r.packed, r.kcache, r.vcache = ssq, packed, kc, vc
+    if want_slabs:
+        if path == 4:
+            r.slabs = slabs[:slab_floats]
+        else:
+            r.slabs = slabs[:max(r.split, 0) * M * N].reshape(-1, M, N)
+    return r
+
+
+def norm_probe(x, slabs=None, w=None, row_map=None, eps: float = 0.0, device: int = 0):
+    """launch_resid_norm / launch_rmsnorm on caller-supplied rows (mx_norm_probe): x f32 [rows][n], slabs
+    [nslab][rows][n], w [n], row_map [M].  Returns (x after [rows][n], x guard [64][n] as uint32, y bf16 bits
+    [M][n] or None, y guard [64][n] or None)."""
+    xa = np.ascontiguousarray(x, dtype=np.float32)
+    rows, n = xa.shape
+    sa = wa = ma = None
+    nslab = 0
+    if slabs is not None:
+        sa = np.ascontiguousarray(slabs, dtype=np.float32)
+        nslab = sa.shape[0]
+        if sa.shape != (nslab, rows, n):
+            raise ValueError("slabs [nslab][rows][n] expected")
+        if nslab == 0:
+            sa = None
+    if w is not None:
+        wa = np.ascontiguousarray(w, dtype=np.float32)
+        if wa.size != n:
+            raise ValueError("w [n] expected")
+    M = rows
+    if row_map is not None:
+        ma = _i32(row_map)
+        M = len(ma)
+    xo = np.zeros((rows + PROBE_GUARD_ROWS, n), dtype=np.float32)
+    yo = np.zeros((M + PROBE_GUARD_ROWS, n), dtype=np.uint16) if wa is not None else None
+    _check(lib().mx_norm_probe(device, rows, n, M, xa.ctypes.data, sa.ctypes.data if sa is not None else None, nslab,
+                               wa.ctypes.data if wa is not None else None, ma.ctypes.data if ma is not None else None,
+                               eps, xo.ctypes.data, yo.ctypes.data if yo is not None else None))
+    return (xo[:rows], xo[rows:].view(np.uint32), yo[:M] if yo is not None else None,
+            yo[M:] if yo is not None else None)
 
 
 def _check(rc: int):
