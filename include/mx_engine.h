@@ -17,6 +17,7 @@
  *   mx_forward_logits  <- llama_decode + llama_get_logits (Llama.eval), parity hook
  *   mx_submit_lp / mx_request_logprobs
  *                      <- create_completion(logprobs=k): Llama.logits_to_logprobs + the top-k sort
+ *   mx_submit_spec     <- Llama(draft_model=LlamaPromptLookupDecoding(...)): generate()'s draft / verify loop
  *   mx_engine_destroy  <- llama_free / llama_free_model (Llama.__del__)
  * The Python layer (llama-p2p_amd/llama.py) mirrors the Llama class on top of
  * this ABI, so handle_requests / cached_inference / distributed_inference /
@@ -179,6 +180,40 @@ int mx_forward_logprobs(mx_engine* e, int n, const int32_t* slots, const int32_t
  * logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64, V <= 262144; outputs as above. */
 int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl, const int32_t* targets, int k,
                      float* tgt_lp, float* top_lp, int32_t* top_idx);
+/* Prompt-lookup speculative decoding (llama-cpp-python's draft_model=LlamaPromptLookupDecoding(max_ngram_size,
+ * num_pred_tokens)), on the device: the draft is the tokens that followed the earliest earlier occurrence of the
+ * sequence's last n-gram, verified in one forward of 1 + num_pred_tokens rows of the request's slot.  The tokens
+ * are bitwise those of the same request submitted with mx_submit.
+ *
+ * mx_submit_spec: as mx_submit; num_pred_tokens 1..15, max_ngram_size >= 1 (otherwise MX_ERR_ARG).  A request
+ * speculates in the rounds where every active request is eligible -- greedy (temperature <= 0), no penalties,
+ * a bf16 model -- their rows fit (requests x (1 + largest num_pred_tokens) <= 16) and none is close to n_ctx;
+ * every other round, and an ineligible request always, decodes as after mx_submit. */
+int mx_submit_spec(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int num_pred_tokens,
+                   int max_ngram_size, uint64_t* req);
+/* steps: speculating forwards whose tokens the request kept; drafted / accepted: draft tokens those verified /
+ * found right (a step yields accepted + 1 tokens).  req: a registered request (until mx_wait releases it), or
+ * 0 for the totals of every request so far. */
+typedef struct {
+  uint64_t steps, drafted, accepted;
+} mx_spec_counts;
+int mx_spec_stats(mx_engine* e, uint64_t req, mx_spec_counts* out);
+/* The draft kernel on caller-supplied sequences, no engine: R (1..8) sequences tokens[r][0..lens[r]) in rows of
+ * `stride` int32 (1 <= lens[r] <= stride <= 2^20), D = num_pred_tokens 1..15 with R (1 + D) <= 16, ngram >= 1,
+ * pos0[r] (>= 0, pos0[r] + D < 2^30) / slot0[r] (>= 0) the position and slot of each sequence's row 0.
+ * ids / pos / slot [R][1 + D] and n_draft [R] start as 0xFF bytes and return whole (row 0 of ids untouched:
+ * the kernel writes rows 1..D).  Anything else: MX_ERR_ARG, nothing launched. */
+int mx_draft_probe(int device, int R, const int32_t* tokens, int stride, const int32_t* lens, int D, int ngram,
+                   const int32_t* pos0, const int32_t* slot0, int32_t* ids, int32_t* pos, int32_t* slot,
+                   int32_t* n_draft);
+/* argmax_stage1 + the accept kernel on caller-supplied logits rows [R (1 + D)][V] (R 1..8, D 1..15,
+ * R (1 + D) <= 16, 1 <= V <= 2^20), draft [R][D] (ids in [0, V)), n_draft [R] (0..D), pos0 [R] >= 0.
+ * a [R]: accepted drafts; emitted [R][1 + D]: the a + 1 tokens, the rest still 0xFF bytes; next_id [R];
+ * new_pos [R] = pos0 + a + 1; counts [R][3] = steps, drafted, accepted (from 0).  Anything else: MX_ERR_ARG. */
+int mx_accept_probe(int device, int R, int D, int V, const float* logits, const int32_t* draft, const int32_t* n_draft,
+                    const int32_t* pos0, int32_t* a, int32_t* emitted, int32_t* next_id, int32_t* new_pos,
+                    int32_t* counts);
+
 /* The production attention launchers on caller-supplied q / K / V, no engine (tests on inputs no model
  * produces).  Geometry: head_dim 64 or 128, n_head / n_head_kv in {1, 2, 4, 8}; caches of n_slots slots with
  * ctx_stride = n_ctx rounded up to 64 positions; M rows (1..4096) at pos[i] in [0, n_ctx] (n_ctx: the kernels

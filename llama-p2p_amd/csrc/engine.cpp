@@ -162,6 +162,10 @@ struct Request {
   std::vector<float> lp_tok;   // [entries] log-prob of the token itself
   std::vector<float> lp_top;   // [entries][lp_k]
   std::vector<int32_t> lp_idx; // [entries][lp_k]
+  // prompt-lookup speculation (mx_submit_spec): num_pred_tokens (0 = not asked for) and max_ngram_size; the
+  // counters cover the speculating steps whose tokens the request kept
+  int spec_d = 0, spec_ng = 0;
+  uint64_t spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
   // one entry [tok_lp | kr top log-probs | kr top ids as int bits] of a round that ran with kr >= lp_k
   void lp_append(const float* entry, int kr) {
     lp_tok.push_back(entry[0]);
@@ -417,6 +421,17 @@ struct mx_engine {
   int prefill_prompt_logprobs(Request* r);
   int* sched_hist = nullptr;        // [MAX_ROWS][SCHED_KMAX] tokens of a multi-step greedy run
   int* sched_hist_count = nullptr;  // [MAX_ROWS]
+  // speculating rounds: graphs by (requests, draft rows per request), and the device state
+  // of the round's requests -- their token sequences [SPEC_MAX_REQ][n_ctx] and lengths, {num_pred_tokens,
+  // max_ngram_size}, draft lengths, the variable-length token history [SPEC_MAX_REQ][SCHED_KMAX * SPEC_ROWS]
+  // with its counts, the counters [.][3] and the per-step log [.][SCHED_KMAX][2] = {n_draft, accepted}
+  std::map<std::pair<int, int>, hipGraphExec_t> spec_graphs;
+  int *spec_ctx = nullptr, *spec_len = nullptr, *spec_par = nullptr, *spec_ndraft = nullptr, *spec_hist = nullptr;
+  int *spec_hist_count = nullptr, *spec_cnt = nullptr, *spec_log = nullptr;
+  uint64_t stat_spec_steps = 0, stat_spec_drafted = 0, stat_spec_accepted = 0;
+  bool spec_eligible(const Request* r) const;
+  // 1 when the round ran speculating (rows updated), 0 when it has to run plain, < 0 on an error
+  int sched_step_spec(std::vector<Request*>& rows);
   int32_t sample_host(Request* r, const float* logits);
   int32_t sample_chain(Request* r, std::vector<std::pair<float, int>>& c);  // c: top-k, sorted
   void finish(Request* r, int why);
@@ -430,6 +445,7 @@ mx_engine::~mx_engine() {
   cv.notify_all();
   if (worker.joinable()) worker.join();
   for (auto& kv : sched_graphs) hipGraphExecDestroy(kv.second);
+  for (auto& kv : spec_graphs) hipGraphExecDestroy(kv.second);
   if (stream) hipStreamSynchronize(stream);
 
   for (void* p : allocations) hipFree(p);
@@ -534,6 +550,16 @@ int mx_engine::init_common() {
   if (int rc = alloc((void**)&sched_hist, (size_t)MAX_ROWS * SCHED_KMAX * 4)) return rc;
   if (int rc = alloc((void**)&sched_hist_count, (size_t)MAX_ROWS * 4)) return rc;
   if (int rc = alloc((void**)&d_samp, (size_t)MAX_ROWS * sizeof(SampRow))) return rc;
+  if (has_embed && has_head && !wq8 && !wkq) {
+    if (int rc = alloc((void**)&spec_ctx, (size_t)SPEC_MAX_REQ * n_ctx * 4)) return rc;
+    if (int rc = alloc((void**)&spec_len, SPEC_MAX_REQ * 4)) return rc;
+    if (int rc = alloc((void**)&spec_par, SPEC_MAX_REQ * 2 * 4)) return rc;
+    if (int rc = alloc((void**)&spec_ndraft, SPEC_MAX_REQ * 4)) return rc;
+    if (int rc = alloc((void**)&spec_hist, (size_t)SPEC_MAX_REQ * SCHED_KMAX * SPEC_ROWS * 4)) return rc;
+    if (int rc = alloc((void**)&spec_hist_count, SPEC_MAX_REQ * 4)) return rc;
+    if (int rc = alloc((void**)&spec_cnt, SPEC_MAX_REQ * 3 * 4)) return rc;
+    if (int rc = alloc((void**)&spec_log, SPEC_MAX_REQ * SCHED_KMAX * 2 * 4)) return rc;
+  }
   if (wq8 || wkq) {
     const size_t kmax = std::max(n_embd, n_ff);
     if (int rc = alloc((void**)&xq8, (size_t)R * kmax)) return rc;
@@ -1916,12 +1942,142 @@ int mx_engine::prefill_prompt_logprobs(Request* r) {
   return 0;
 }
 
+// Prompt-lookup speculation.  Eligible: asked for, greedy without penalties or
+// log-probabilities, on a whole bf16 model -- the path whose rows are bitwise independent of the row count.
+bool mx_engine::spec_eligible(const Request* r) const {
+  return r->spec_d > 0 && spec_ctx && r->samp.temperature <= 0.f && !has_penalties(r->samp) && r->lp_k < 0 &&
+         !embd_q8 && !out_q8 && !embd_kq_type && !out_kq_head;
+}
+
+// A speculating round: every active request eligible, their R (1 + D) rows within the <= 16-row decode path
+// (D = the largest num_pred_tokens asked for), and no row able to reach n_ctx in the round's K steps.  A step
+// = draft kernel -> forward over R (1 + D) rows (row r(1+D): the request's last token, then its draft, all
+// in its slot; lm_head on every row) -> argmax partials -> accept kernel; everything it indexes with lives
+// on the device, so one captured graph replays K times.  Then the variable-length history of each request
+// is applied with the plain round's EOS / max_tokens / cancel rules: tokens past the end are dropped, and
+// pos / the slot's recorded tokens cover only what was kept.  Returns 1, 0 (run this round plain), or < 0.
+int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
+  const int R = (int)rows.size();
+  if (R > SPEC_MAX_REQ) return 0;
+  int D = 0, need = 1;
+  for (const Request* r : rows) {
+    if (!spec_eligible(r) || r->pos + 1 != (int)(r->prompt.size() + r->out.size())) return 0;
+    D = std::max(D, r->spec_d);
+    // steps the request still needs at the tokens per step it has had so far (1 + accepted / steps; at least
+    // one token per step): a round that falls short is followed by another, one that overshoots wasted steps
+    const uint64_t left = (uint64_t)std::max(1, r->max_tokens - (int)r->out.size());
+    const uint64_t st = std::max<uint64_t>(1, r->spec_steps), per = st + r->spec_accepted;
+    need = std::max(need, (int)((left * st + per - 1) / per));
+  }
+  if (R * (1 + D) > SPEC_ROWS) return 0;
+  int K = std::min(SCHED_KMAX, need);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!pending.empty() && !free_slots.empty()) K = 1;  // admit waiting requests at the next round
+  }
+  for (const Request* r : rows)
+    while (K >= 1 && r->pos + K * (1 + D) + D > n_ctx - 1) K--;
+  if (K < 1) return 0;  // close to n_ctx: the plain round reaches the last positions
+  const int M = R * (1 + D), HS = SCHED_KMAX * SPEC_ROWS;
+  std::vector<int32_t> ids(M), pos(M), slots(M), par(2 * R), len(R);
+  std::vector<std::vector<int32_t>> ctx(R);
+  hipStream_t s = stream;
+  for (int i = 0; i < R; i++) {
+    const Request* r = rows[i];
+    for (int j = 0; j <= D; j++) {  // rows 1..D are rewritten by the draft kernel
+      ids[i * (1 + D) + j] = r->next_tok;
+      pos[i * (1 + D) + j] = r->pos;
+      slots[i * (1 + D) + j] = r->slot;
+    }
+    par[2 * i] = r->spec_d;
+    par[2 * i + 1] = r->spec_ng;
+    ctx[i] = r->prompt;
+    ctx[i].insert(ctx[i].end(), r->out.begin(), r->out.end());
+    len[i] = (int)ctx[i].size();
+    HIPC(hipMemcpyAsync(spec_ctx + (size_t)i * n_ctx, ctx[i].data(), (size_t)len[i] * 4, hipMemcpyHostToDevice, s));
+  }
+  HIPC(hipMemcpyAsync(d_ids, ids.data(), M * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_pos, pos.data(), M * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_slot, slots.data(), M * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(spec_par, par.data(), R * 2 * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(spec_len, len.data(), R * 4, hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(spec_hist_count, 0, R * 4, s));
+  HIPC(hipMemsetAsync(spec_cnt, 0, R * 3 * 4, s));
+  auto step = [&]() -> int {
+    launch_spec_draft(spec_ctx, n_ctx, spec_len, spec_par, R, D, d_ids, d_pos, d_slot, spec_ndraft, s);
+    // rows of one slot: the plain <= 16-row path, whose q|k|v epilogue stores every row's K/V before the
+    // attention launch reads them (rows_distinct stays false)
+    if (int rc = enqueue_forward(M, d_ids, d_pos, d_slot, nullptr, nullptr, true, nullptr, M, false, nullptr, nullptr,
+                                 nullptr, 0, nullptr, 0, s))
+      return rc;
+    launch_argmax_stage1(logits, n_vocab, M, n_vocab, am_val, am_idx, s);
+    launch_spec_accept(am_val, am_idx, R, D, d_ids, d_pos, spec_ndraft, spec_ctx, n_ctx, spec_len, spec_hist, HS,
+                       spec_hist_count, spec_cnt, spec_log, SCHED_KMAX, s);
+    return 0;
+  };
+  static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  bool captured = false;
+  auto it = spec_graphs.find({R, D});
+  if (use_graphs && it == spec_graphs.end()) {
+    captured = true;
+    hipGraph_t g;
+    HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = step();
+    hipError_t ce = hipStreamEndCapture(s, &g);
+    if (rc) return rc;
+    if (ce != hipSuccess) return fail(MX_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce));
+    hipGraphExec_t ex;
+    HIPC(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
+    hipGraphDestroy(g);
+    it = spec_graphs.emplace(std::make_pair(R, D), ex).first;
+  }
+  for (int k = 0; k < K; k++) {
+    if (use_graphs) HIPC(hipGraphLaunch(it->second, s));
+    else if (int rc = step()) return rc;
+  }
+  std::vector<int32_t> hist((size_t)R * HS), log((size_t)R * SCHED_KMAX * 2);
+  HIPC(hipMemcpyAsync(hist.data(), spec_hist, hist.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(log.data(), spec_log, log.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  std::lock_guard<std::mutex> lk(mu);
+  int emitted = 0;
+  for (int i = 0; i < R; i++) {
+    Request* r = rows[i];
+    int off = 0;
+    for (int k = 0; k < K && !r->done; k++) {
+      const int nd = log[((size_t)i * SCHED_KMAX + k) * 2], a = log[((size_t)i * SCHED_KMAX + k) * 2 + 1];
+      if (nd < 0 || nd > D || a < 0 || a > nd || off + a + 1 > HS) return fail(MX_ERR_STATE, "speculation step log");
+      int kept = 0;
+      for (int j = 0; j <= a && !r->done; j++, kept++) {
+        const int32_t t = hist[(size_t)i * HS + off + j];
+        r->pos++;
+        r->out.push_back(t);
+        r->next_tok = t;
+        if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
+        else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
+      }
+      off += a + 1;
+      emitted += kept;
+      r->spec_steps++, r->spec_drafted += nd, r->spec_accepted += kept - 1;
+      stat_spec_steps++, stat_spec_drafted += nd, stat_spec_accepted += kept - 1;
+    }
+  }
+  if (trace) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "sched: speculating R=%d D=%d K=%d kept %d tokens %s%.3f ms\n", R, D, K, emitted,
+            captured ? "(graph captured) " : "", ms);
+  }
+  return 1;
+}
+
 // One scheduler round over the active rows.  All greedy (no penalties): K decode steps replayed
 // back to back on the device (the captured step feeds its argmax into the next step's ids and
 // positions and appends it to a history), one sync, then the K tokens of every row are applied in
 // order (a row that finishes early ignores the rest).  Otherwise one step, with the sampler chain
 // on the host (top-k candidates from the device when possible).
 int mx_engine::sched_step(std::vector<Request*>& rows) {
+  if (const int sp = sched_step_spec(rows)) return sp < 0 ? sp : 0;
   const int M = (int)rows.size();
   std::vector<int32_t> ids(M), pos(M), slots(M);
   bool all_greedy = true, all_dev = true;
@@ -2876,6 +3032,143 @@ int mx_norm_probe(int device, int rows, int n, int M, const float* x, const floa
   HIPC(hipDeviceSynchronize());
   HIPC(hipMemcpy(x_out, d_x, xb, hipMemcpyDeviceToHost));
   if (w) HIPC(hipMemcpy(y_out, d_y, yb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mx_submit_spec(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int num_pred_tokens,
+                   int max_ngram_size, uint64_t* req) {
+  if (!e || !ids || n < 1 || !req) return fail(MX_ERR_ARG, "bad arguments");
+  if (num_pred_tokens < 1 || num_pred_tokens > SPEC_MAX_DRAFT || max_ngram_size < 1)
+    return fail(MX_ERR_ARG, "mx_submit_spec: num_pred_tokens must be 1..15 and max_ngram_size >= 1");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit needs a full-model engine");
+  std::unique_ptr<Request> r;
+  if (int rc = make_request(e, ids, n, s, max_tokens, &r)) return rc;
+  r->spec_d = num_pred_tokens;
+  r->spec_ng = max_ngram_size;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->stop) return fail(MX_ERR_STATE, "engine shutting down");
+    Request* rp = r.get();
+    rp->id = e->next_id++;
+    *req = rp->id;
+    e->pending.push_back(rp);
+    e->requests[rp->id] = std::move(r);
+    if (!e->worker_started) {
+      e->worker_started = true;
+      e->worker = std::thread([e] { e->scheduler_loop(); });
+    }
+  }
+  e->cv.notify_all();
+  return 0;
+}
+
+int mx_spec_stats(mx_engine* e, uint64_t req, mx_spec_counts* out) {
+  if (!e || !out) return fail(MX_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (req == 0) {
+    *out = {e->stat_spec_steps, e->stat_spec_drafted, e->stat_spec_accepted};
+    return 0;
+  }
+  auto it = e->requests.find(req);
+  if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
+  *out = {it->second->spec_steps, it->second->spec_drafted, it->second->spec_accepted};
+  return 0;
+}
+
+int mx_draft_probe(int device, int R, const int32_t* tokens, int stride, const int32_t* lens, int D, int ngram,
+                   const int32_t* pos0, const int32_t* slot0, int32_t* ids, int32_t* pos, int32_t* slot,
+                   int32_t* n_draft) {
+  if (!tokens || !lens || !pos0 || !slot0 || !ids || !pos || !slot || !n_draft || R < 1 || R > SPEC_MAX_REQ || D < 1 ||
+      D > SPEC_MAX_DRAFT || R * (1 + D) > SPEC_ROWS || ngram < 1 || stride < 1 || stride > (1 << 20))
+    return fail(MX_ERR_ARG, "mx_draft_probe: R 1..8, D 1..15, R (1 + D) <= 16, ngram >= 1, 1 <= stride <= 2^20");
+  for (int r = 0; r < R; r++)
+    if (lens[r] < 1 || lens[r] > stride || pos0[r] < 0 || pos0[r] > (1 << 30) - 1 - D || slot0[r] < 0)
+      return fail(MX_ERR_ARG, "mx_draft_probe: 1 <= lens[r] <= stride, 0 <= pos0[r] < 2^30 - D, slot0[r] >= 0");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const int M = R * (1 + D);
+  DevBufs bufs;
+  int *d_tok, *d_len, *d_par, *d_i, *d_p, *d_s, *d_nd;
+  if (!bufs.alloc(&d_tok, (size_t)R * stride * 4) || !bufs.alloc(&d_len, R * 4) || !bufs.alloc(&d_par, R * 2 * 4) ||
+      !bufs.alloc(&d_i, M * 4) || !bufs.alloc(&d_p, M * 4) || !bufs.alloc(&d_s, M * 4) || !bufs.alloc(&d_nd, R * 4))
+    return fail(MX_ERR_HIP, "mx_draft_probe: device allocation");
+  std::vector<int32_t> par(2 * R), hp(M, -1), hs(M, -1);
+  for (int r = 0; r < R; r++) {
+    par[2 * r] = D, par[2 * r + 1] = ngram;
+    hp[r * (1 + D)] = pos0[r], hs[r * (1 + D)] = slot0[r];
+  }
+  HIPC(hipMemcpy(d_tok, tokens, (size_t)R * stride * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_len, lens, R * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_par, par.data(), R * 2 * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_i, 0xFF, M * 4));
+  HIPC(hipMemcpy(d_p, hp.data(), M * 4, hipMemcpyHostToDevice));  // -1 = 0xFF bytes but for each row 0
+  HIPC(hipMemcpy(d_s, hs.data(), M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_nd, 0xFF, R * 4));
+  launch_spec_draft(d_tok, stride, d_len, d_par, R, D, d_i, d_p, d_s, d_nd, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(ids, d_i, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(pos, d_p, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(slot, d_s, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(n_draft, d_nd, R * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mx_accept_probe(int device, int R, int D, int V, const float* logits, const int32_t* draft, const int32_t* n_draft,
+                    const int32_t* pos0, int32_t* a, int32_t* emitted, int32_t* next_id, int32_t* new_pos,
+                    int32_t* counts) {
+  if (!logits || !draft || !n_draft || !pos0 || !a || !emitted || !next_id || !new_pos || !counts || R < 1 ||
+      R > SPEC_MAX_REQ || D < 1 || D > SPEC_MAX_DRAFT || R * (1 + D) > SPEC_ROWS || V < 1 || V > (1 << 20))
+    return fail(MX_ERR_ARG, "mx_accept_probe: R 1..8, D 1..15, R (1 + D) <= 16, 1 <= V <= 2^20");
+  for (int r = 0; r < R; r++) {
+    if (n_draft[r] < 0 || n_draft[r] > D || pos0[r] < 0 || pos0[r] > (1 << 30))
+      return fail(MX_ERR_ARG, "mx_accept_probe: 0 <= n_draft[r] <= D, 0 <= pos0[r] <= 2^30");
+    for (int j = 0; j < D; j++)
+      if (draft[r * D + j] < 0 || draft[r * D + j] >= V) return fail(MX_ERR_ARG, "mx_accept_probe: draft id out of range");
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const int M = R * (1 + D), CS = 1 + D;  // the sequence buffer: one token already there, room for 1 + D more
+  DevBufs bufs;
+  float *d_lg, *d_wv;
+  int *d_wi, *d_i, *d_p, *d_nd, *d_ctx, *d_len, *d_h, *d_hc, *d_cnt;
+  if (!bufs.alloc(&d_lg, (size_t)M * V * 4) || !bufs.alloc(&d_wv, M * 64 * 4) || !bufs.alloc(&d_wi, M * 64 * 4) ||
+      !bufs.alloc(&d_i, M * 4) || !bufs.alloc(&d_p, M * 4) || !bufs.alloc(&d_nd, R * 4) ||
+      !bufs.alloc(&d_ctx, (size_t)R * (CS + 1) * 4) || !bufs.alloc(&d_len, R * 4) || !bufs.alloc(&d_h, M * 4) ||
+      !bufs.alloc(&d_hc, R * 4) || !bufs.alloc(&d_cnt, R * 3 * 4))
+    return fail(MX_ERR_HIP, "mx_accept_probe: device allocation");
+  std::vector<int32_t> hi(M, -1), hp(M, -1), one(R, 1);
+  for (int r = 0; r < R; r++) {
+    hp[r * (1 + D)] = pos0[r];
+    for (int j = 0; j < D; j++) hi[r * (1 + D) + 1 + j] = draft[r * D + j];
+  }
+  HIPC(hipMemcpy(d_lg, logits, (size_t)M * V * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_i, hi.data(), M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_p, hp.data(), M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_nd, n_draft, R * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_ctx, 0xFF, (size_t)R * (CS + 1) * 4));
+  HIPC(hipMemcpy(d_len, one.data(), R * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_h, 0xFF, M * 4));
+  HIPC(hipMemset(d_hc, 0, R * 4));
+  HIPC(hipMemset(d_cnt, 0, R * 3 * 4));
+  launch_argmax_stage1(d_lg, V, M, V, d_wv, d_wi, nullptr);
+  launch_spec_accept(d_wv, d_wi, R, D, d_i, d_p, d_nd, d_ctx, CS + 1, d_len, d_h, CS, d_hc, d_cnt, nullptr, 0, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  std::vector<int32_t> oi(M), op(M), ctx((size_t)R * (CS + 1)), hc(R);
+  HIPC(hipMemcpy(oi.data(), d_i, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(op.data(), d_p, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(ctx.data(), d_ctx, ctx.size() * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hc.data(), d_hc, R * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(emitted, d_h, M * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(counts, d_cnt, R * 3 * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < R; r++) {
+    a[r] = hc[r] - 1;
+    next_id[r] = oi[r * (1 + D)];
+    new_pos[r] = op[r * (1 + D)];
+    // the copy appended to the sequence must be the history's
+    for (int j = 0; j < CS; j++)
+      if (ctx[(size_t)r * (CS + 1) + 1 + j] != emitted[r * CS + j])
+        return fail(MX_ERR_STATE, "mx_accept_probe: sequence and history disagree");
+  }
   return 0;
 }
 

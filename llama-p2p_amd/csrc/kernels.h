@@ -243,6 +243,25 @@ void launch_argmax(const float* logits, int ldl, int M, int V, float* ws_val, in
                    int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count, int max_hist,
                    hipStream_t s);
 
+// ---- prompt-lookup speculative decoding.  R requests, each with 1 + D rows of the forward
+// (row r(1+D): its last token; the next D: the draft), R(1+D) <= SPEC_ROWS.
+// draft: ctx_tok [R][ctx_stride] holds each request's tokens [0, ctx_len[r]) (ctx_len >= 1), par [R][2] =
+// {num_pred_tokens (clamped to D), max_ngram_size}; reads pos / slot of each request's row 0 and writes
+// ids / pos / slot of its rows 1..D and n_draft[r] (0..D).
+// accept: ws_val / ws_idx = argmax_stage1's partials of all R(1+D) logits rows; per request emits
+// argmax[0..a] to hist[r][hist_count[r]..] and ctx_tok[r][ctx_len[r]..], sets ids of row 0, adds a + 1 to
+// pos of row 0, ctx_len and hist_count, and steps / drafted / accepted to cnt [R][3]; step_log (optional)
+// [R][max_steps][2] = {n_draft, a} of step cnt[r][0].
+constexpr int SPEC_ROWS = 16;      // rows of a speculating forward: the <= 16-row decode path
+constexpr int SPEC_MAX_DRAFT = 15; // so num_pred_tokens <= 15 ...
+constexpr int SPEC_MAX_REQ = 8;    // ... and at most 8 requests (D >= 1) share a round
+void launch_spec_draft(const int* ctx_tok, int ctx_stride, const int* ctx_len, const int* par, int R, int D, int* ids,
+                       int* pos, int* slot, int* n_draft, hipStream_t s);
+void launch_argmax_stage1(const float* logits, int ldl, int M, int V, float* ws_val, int* ws_idx, hipStream_t s);
+void launch_spec_accept(const float* ws_val, const int* ws_idx, int R, int D, int* ids, int* pos, const int* n_draft,
+                        int* ctx_tok, int ctx_stride, int* ctx_len, int* hist, int hist_stride, int* hist_count,
+                        int* cnt, int* step_log, int max_steps, hipStream_t s);
+
 // ---- device sampling chain (llama-cpp-python 0.3's create_completion chain as
 // engine.cpp restates it): penalties over the last last_n tokens -> top_k -> top_p -> min_p ->
 // temperature -> draw; temperature <= 0 = greedy (after the penalties).  One SampRow per logits row.

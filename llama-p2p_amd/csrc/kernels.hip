@@ -1405,6 +1405,130 @@ void launch_argmax(const float* logits, int ldl, int M, int V, float* ws_val, in
 }
 
 // ---------------------------------------------------------------------------
+// Prompt-lookup speculative decoding (llama-cpp-python's LlamaPromptLookupDecoding).
+// Request r of a speculating round owns rows [r(1+D), (r+1)(1+D)) of the forward: row 0 is its last
+// token at its position p, rows 1..D the draft at p+1..p+D, all in the request's KV slot.
+//
+// spec_draft_kernel, one work-group per request: find_candidate_pred_tokens over ctx_tok[r][0..len).
+// For g = min(ng, len-1) .. 1 the key is the last g tokens; thread t tests the windows t, t+256, ... of
+// [0, len-g) in increasing order and keeps its first match, the work-group takes the minimum (wave
+// butterfly, then LDS) -- the lowest matching index, whose continuation is never empty (i + g < len).
+// The draft is ctx_tok[i+g .. min(i+g+d, len)), d = the request's own num_pred_tokens (<= D).
+// Rows past n_draft repeat the last draft token (the last context token when n_draft = 0): they are
+// forwarded but never accepted, and their K/V lands at positions past the sequence's end.  That is
+// harmless: a position is read by attention only from rows at or after it, and the next step, starting
+// at its new p <= the old p + n_draft + 1, rewrites every position p..p+D in its q|k|v epilogue before
+// its attention launch reads any of them -- so no stale K/V past the accepted prefix is ever read.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void spec_draft_kernel(const int* ctx_tok, int ctx_stride, const int* ctx_len,
+                                                         const int* par, int D, int* ids, int* pos, int* slot,
+                                                         int* n_draft) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int* tok = ctx_tok + (size_t)r * ctx_stride;
+  const int len = ctx_len[r], d = min(par[2 * r], D), ng = par[2 * r + 1];
+  const int base = r * (1 + D);
+  __shared__ int sm[4];
+  int found = 0x7fffffff, g = min(ng, len - 1);
+  for (; g >= 1; --g) {
+    const int* key = tok + (len - g);
+    int best = 0x7fffffff;
+    for (int i = tid; i < len - g; i += 256) {
+      int k = 0;
+      while (k < g && tok[i + k] == key[k]) ++k;
+      if (k == g) {
+        best = i;
+        break;
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
+    if ((tid & 63) == 0) sm[tid >> 6] = best;
+    __syncthreads();
+    found = min(min(sm[0], sm[1]), min(sm[2], sm[3]));
+    __syncthreads();
+    if (found != 0x7fffffff) break;
+  }
+  const bool hit = found != 0x7fffffff;
+  const int start = hit ? found + g : 0;
+  const int n = hit ? max(0, min(d, len - start)) : 0;
+  if (tid < D) {
+    const int p = pos[base], sl = slot[base];
+    const int t = tid < n ? tok[start + tid] : (n > 0 ? tok[start + n - 1] : tok[len - 1]);
+    ids[base + 1 + tid] = t;
+    pos[base + 1 + tid] = p + 1 + tid;
+    slot[base + 1 + tid] = sl;
+  }
+  if (tid == 0) n_draft[r] = n;
+}
+
+// spec_accept_kernel, one wave per request, after argmax_stage1 over all R(1+D) logits rows: finishes
+// the argmax of rows 0..n_draft exactly as argmax_stage2 (ties -> lowest id), a = the number of leading
+// j < n_draft with argmax[j] == draft[j], and emits argmax[0..a]: appended to the round's history and
+// to ctx_tok[r], argmax[a] becomes row 0's next id, position and length advance by a + 1.  cnt[r] =
+// {steps, drafted, accepted} of the round so far; step_log[r][step] = {n_draft, a} lets the host count
+// only the steps whose tokens it keeps.
+__global__ __launch_bounds__(64) void spec_accept_kernel(const float* ws_val, const int* ws_idx, int D, int* ids,
+                                                        int* pos, const int* n_draft, int* ctx_tok, int ctx_stride,
+                                                        int* ctx_len, int* hist, int hist_stride, int* hist_count,
+                                                        int* cnt, int* step_log, int max_steps) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int base = r * (1 + D), nd = min(n_draft[r], D);
+  int mine = 0, a = 0;
+  bool ok = true;
+  for (int j = 0; j <= nd; ++j) {
+    const int c = base + j;
+    float bv = ws_val[c * ARGMAX_CHUNKS + lane];
+    int bi = ws_idx[c * ARGMAX_CHUNKS + lane];
+    for (int o = 32; o > 0; o >>= 1) {
+      float ov = __shfl_xor(bv, o);
+      int oi = __shfl_xor(bi, o);
+      better(bv, bi, ov, oi);
+    }
+    if (bi == 0x7fffffff) bi = 0;  // all-NaN row
+    if (lane == j) mine = bi;
+    if (j < nd) {
+      ok = ok && bi == ids[base + 1 + j];
+      if (ok) a = j + 1;
+    }
+  }
+  const int len = ctx_len[r], hc = hist_count[r];
+  __syncthreads();  // every lane has read the drafts / length / count before any of them is rewritten
+  if (lane <= a) {
+    if (hc + lane < hist_stride) hist[(size_t)r * hist_stride + hc + lane] = mine;
+    if (len + lane < ctx_stride) ctx_tok[(size_t)r * ctx_stride + len + lane] = mine;
+  }
+  if (lane == a) ids[base] = mine;
+  if (lane == 0) {
+    pos[base] += a + 1;
+    ctx_len[r] = len + a + 1;
+    hist_count[r] = hc + a + 1;
+    const int st = cnt[3 * r];
+    if (step_log && st < max_steps) {
+      step_log[(r * max_steps + st) * 2] = nd;
+      step_log[(r * max_steps + st) * 2 + 1] = a;
+    }
+    cnt[3 * r] = st + 1;
+    cnt[3 * r + 1] += nd;
+    cnt[3 * r + 2] += a;
+  }
+}
+
+void launch_spec_draft(const int* ctx_tok, int ctx_stride, const int* ctx_len, const int* par, int R, int D, int* ids,
+                       int* pos, int* slot, int* n_draft, hipStream_t s) {
+  spec_draft_kernel<<<R, 256, 0, s>>>(ctx_tok, ctx_stride, ctx_len, par, D, ids, pos, slot, n_draft);
+}
+
+void launch_spec_accept(const float* ws_val, const int* ws_idx, int R, int D, int* ids, int* pos, const int* n_draft,
+                        int* ctx_tok, int ctx_stride, int* ctx_len, int* hist, int hist_stride, int* hist_count,
+                        int* cnt, int* step_log, int max_steps, hipStream_t s) {
+  spec_accept_kernel<<<R, 64, 0, s>>>(ws_val, ws_idx, D, ids, pos, n_draft, ctx_tok, ctx_stride, ctx_len, hist,
+                                      hist_stride, hist_count, cnt, step_log, max_steps);
+}
+
+void launch_argmax_stage1(const float* logits, int ldl, int M, int V, float* ws_val, int* ws_idx, hipStream_t s) {
+  argmax_stage1<<<dim3(ARGMAX_CHUNKS, M), 256, 0, s>>>(logits, ldl, V, ws_val, ws_idx);
+}
+
+// ---------------------------------------------------------------------------
 // Device sampling chain.  penalty_kernel: llama.cpp's penalties sampler over the row's window (the
 // last last_n tokens of prompt + output: the n_win tokens given at the start of the run, then the
 // tokens this run generated, hist[0..hist_count)).  Lane j holds window token j; the lane holding a

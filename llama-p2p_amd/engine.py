@@ -31,8 +31,10 @@ EXPORTS = [
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
     "mx_attention_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
+    "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
 ]
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
+SPEC_MAX_DRAFT = 15  # kernels.h: most draft tokens per speculating step (1 + 15 rows of the <= 16-row path)
 
 
 class MxError(RuntimeError):
@@ -66,6 +68,10 @@ class MxSampling(ctypes.Structure):
 class MxRowSampler(ctypes.Structure):
     _fields_ = [("s", MxSampling), ("seed", ctypes.c_uint64), ("n_drawn", ctypes.c_int32), ("n_win", ctypes.c_int32),
                 ("win", ctypes.c_int32 * 64)]
+
+
+class MxSpecCounts(ctypes.Structure):
+    _fields_ = [("steps", ctypes.c_uint64), ("drafted", ctypes.c_uint64), ("accepted", ctypes.c_uint64)]
 
 
 class MxMatmulArgs(ctypes.Structure):
@@ -180,6 +186,10 @@ def lib() -> ctypes.CDLL:
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
         L.mx_matmul_plan.argtypes = [i32, i32, i32, i32, P(i32), P(i32), P(i32), P(i32)]
         L.mx_norm_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_float, vp, vp]
+        L.mx_submit_spec.argtypes = [vp, vp, i32, P(MxSampling), i32, i32, i32, P(u64)]
+        L.mx_spec_stats.argtypes = [vp, u64, P(MxSpecCounts)]
+        L.mx_draft_probe.argtypes = [i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.mx_accept_probe.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -230,6 +240,47 @@ def logprob_probe(logits, targets, k: int, V: Optional[int] = None, device: int 
     _check(lib().mx_logprob_probe(device, lg.ctypes.data, n, V, ldl, tg.ctypes.data, k, tgt.ctypes.data,
                                   top.ctypes.data if ke else None, idx.ctypes.data if ke else None))
     return tgt, top, idx
+
+
+def draft_probe(seqs, num_pred_tokens: int, max_ngram_size: int, pos0=None, slot0=None, device: int = 0):
+    """The prompt-lookup draft kernel on caller-supplied token sequences (no engine; include/mx_engine.h
+    mx_draft_probe).  Returns (ids, pos, slot) [R][1 + D] -- rows 1..D written by the kernel, ids[:, 0] still
+    -1 -- and n_draft [R]."""
+    R, D = len(seqs), int(num_pred_tokens)
+    lens = _i32([len(q) for q in seqs])
+    stride = max(1, int(lens.max()) if R else 1)
+    tok = np.zeros((max(R, 1), stride), dtype=np.int32)
+    for r, q in enumerate(seqs):
+        tok[r, :len(q)] = q
+    p0 = _i32([n - 1 for n in lens] if pos0 is None else pos0)
+    s0 = _i32(list(range(R)) if slot0 is None else slot0)
+    if len(p0) != R or len(s0) != R:
+        raise ValueError("one pos0 / slot0 per sequence")
+    shape = (max(R, 0), 1 + max(D, 0))
+    ids, pos, slot = (np.zeros(shape, dtype=np.int32) for _ in range(3))
+    nd = np.zeros(max(R, 0), dtype=np.int32)
+    _check(lib().mx_draft_probe(device, R, tok.ctypes.data, stride, lens.ctypes.data, D, int(max_ngram_size),
+                                p0.ctypes.data, s0.ctypes.data, ids.ctypes.data, pos.ctypes.data, slot.ctypes.data,
+                                nd.ctypes.data))
+    return ids, pos, slot, nd
+
+
+def accept_probe(logits, draft, n_draft, pos0, device: int = 0):
+    """argmax + the speculation accept kernel on caller-supplied rows (mx_accept_probe): logits [R][1 + D][V]
+    f32, draft [R][D], n_draft [R], pos0 [R].  Returns dict(a [R], emitted [R][1 + D] (-1 past a + 1 tokens),
+    next_id [R], new_pos [R], counts [R][3] = steps, drafted, accepted)."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    R, D1, V = lg.shape
+    D = D1 - 1
+    dr, nd, p0 = _i32(draft).reshape(R, -1), _i32(n_draft), _i32(pos0)
+    if dr.shape != (R, D) or len(nd) != R or len(p0) != R:
+        raise ValueError("draft [R][D], n_draft [R], pos0 [R] expected")
+    a, nxt, npos = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    em = np.zeros((R, D1), dtype=np.int32)
+    cnt = np.zeros((R, 3), dtype=np.int32)
+    _check(lib().mx_accept_probe(device, R, D, V, lg.ctypes.data, dr.ctypes.data, nd.ctypes.data, p0.ctypes.data,
+                                 a.ctypes.data, em.ctypes.data, nxt.ctypes.data, npos.ctypes.data, cnt.ctypes.data))
+    return {"a": a, "emitted": em, "next_id": nxt, "new_pos": npos, "counts": cnt}
 
 
 KV_POS_ALIGN = 64  # kernels.h: KV positions per slot are allocated in multiples of this
@@ -450,6 +501,7 @@ class Engine:
     """One engine instance = one GPU, one model (or one pipeline stage of it)."""
 
     supports_logprobs = True  # submit(logprobs=) / logprobs(): what Llama.create_completion(logprobs=) needs
+    supports_draft = True  # submit(draft=) / spec_stats(): what Llama(draft_model=LlamaPromptLookupDecoding()) needs
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
@@ -542,8 +594,12 @@ class Engine:
     def submit(self, ids: Sequence[int], max_tokens: int, temperature: float = 0.0, top_k: int = 40,
                top_p: float = 0.95, min_p: float = 0.05, repeat_penalty: float = 1.0, repeat_last_n: int = 64,
                seed: Optional[int] = None, ignore_eos: bool = False, frequency_penalty: float = 0.0,
-               presence_penalty: float = 0.0, logprobs: Optional[int] = None, prompt_logprobs: bool = False) -> int:
-        """logprobs=k (0..64): the request also records each generated token's log-probability and the k
+               presence_penalty: float = 0.0, logprobs: Optional[int] = None, prompt_logprobs: bool = False,
+               draft: Optional[Sequence[int]] = None) -> int:
+        """draft=(num_pred_tokens 1..15, max_ngram_size >= 1): prompt-lookup speculative decoding on the device --
+        the same tokens, several per weight pass where the context repeats itself; only greedy requests without
+        penalties or logprobs on a bf16 model ever speculate (spec_stats() tells), the others decode as always.
+        logprobs=k (0..64): the request also records each generated token's log-probability and the k
         most likely tokens (read with logprobs()); prompt_logprobs adds the prompt positions >= 1."""
         ids = _i32(ids)
         s = MxSampling()
@@ -554,7 +610,13 @@ class Engine:
         if seed is not None and seed >= 0:
             s.seed = seed
         req = ctypes.c_uint64()
-        if logprobs is None:
+        if draft is not None and logprobs is None:
+            if prompt_logprobs:
+                raise ValueError("prompt_logprobs needs logprobs=k")
+            d, ng = draft
+            _check(lib().mx_submit_spec(self._h, ids.ctypes.data, len(ids), ctypes.byref(s), max_tokens, int(d), int(ng),
+                                        ctypes.byref(req)))
+        elif logprobs is None:
             if prompt_logprobs:
                 raise ValueError("prompt_logprobs needs logprobs=k")
             _check(lib().mx_submit(self._h, ids.ctypes.data, len(ids), ctypes.byref(s), max_tokens, ctypes.byref(req)))
@@ -577,6 +639,13 @@ class Engine:
             _check(L.mx_request_logprobs(self._h, req, tok.ctypes.data, top.ctypes.data if kk else None,
                                          idx.ctypes.data if kk else None, cap, ctypes.byref(n), ctypes.byref(k)))
         return tok, top, idx
+
+    def spec_stats(self, req: Optional[int] = None) -> dict:
+        """Speculation counters of a request not yet released by wait(), or (None) the engine's totals: steps
+        (speculating forwards whose tokens were kept), drafted and accepted draft tokens."""
+        c = MxSpecCounts()
+        _check(lib().mx_spec_stats(self._h, int(req or 0), ctypes.byref(c)))
+        return {"steps": c.steps, "drafted": c.drafted, "accepted": c.accepted}
 
     def submit_many(self, prompts, max_tokens: int, seeds=None, per_request=None, **kw):
         """Several requests queued atomically (one scheduler round admits them all); same sampling

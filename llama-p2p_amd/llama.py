@@ -22,6 +22,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 
 from . import engine as _engine
 from . import synth as _synth
+from .speculative import LlamaDraftModel, LlamaPromptLookupDecoding
 from .tokenizer import Tokenizer
 
 LLAMA_DEFAULT_SEED = 0xFFFFFFFF
@@ -31,12 +32,14 @@ class Llama:
     def __init__(self, model_path: str, *, n_gpu_layers: int = -1, seed: int = LLAMA_DEFAULT_SEED, n_ctx: int = 512,
                  n_batch: int = 512, n_threads: Optional[int] = None, n_threads_batch: Optional[int] = None,
                  verbose: bool = True, n_seq_max: int = 64, device: int = -1, synthetic_seed: int = 0,
-                 **kwargs: Any):
+                 draft_model: Optional[LlamaDraftModel] = None, **kwargs: Any):
         # n_gpu_layers / n_threads / n_batch are accepted for signature compatibility: the whole model
         # always runs on the GPU, and prompts are processed in 64-row chunks.
         self.model_path = model_path
         self.verbose = verbose
         self._seed = seed
+        self.draft_model = draft_model
+        self._draft = self._draft_numbers(draft_model)
         if n_ctx == 0:
             n_ctx = 4096
         syn = _synth.parse_synthetic_path(model_path)
@@ -47,6 +50,23 @@ class Llama:
         self._n_ctx = n_ctx
         self._init_tokenizer(model_path, self._engine.info.n_vocab)
 
+    @staticmethod
+    def _draft_numbers(draft_model):
+        """(num_pred_tokens, max_ngram_size) for Engine.submit(draft=), or None.  The lookup runs inside the
+        device's decode step, which cannot call Python: only LlamaPromptLookupDecoding is a draft model here."""
+        if draft_model is None:
+            return None
+        if not isinstance(draft_model, LlamaPromptLookupDecoding):
+            raise NotImplementedError("draft_model must be a LlamaPromptLookupDecoding: speculation runs on the "
+                                      "device, which cannot call another Python draft model")
+        d, ng = int(draft_model.num_pred_tokens), int(draft_model.max_ngram_size)
+        if d < 1 or d > _engine.SPEC_MAX_DRAFT:
+            raise ValueError(f"num_pred_tokens must be 1..{_engine.SPEC_MAX_DRAFT} (a speculating step is one "
+                             f"forward of 1 + num_pred_tokens <= 16 rows)")
+        if ng < 1:
+            raise ValueError("max_ngram_size must be >= 1")
+        return d, ng
+
     @classmethod
     def from_engine(cls, model_path: str, engine, n_ctx: int = 512, seed: int = LLAMA_DEFAULT_SEED,
                     verbose: bool = True) -> "Llama":
@@ -55,6 +75,7 @@ class Llama:
         self = cls.__new__(cls)
         self.model_path, self.verbose, self._seed = model_path, verbose, seed
         self._engine, self._n_ctx = engine, n_ctx
+        self.draft_model, self._draft = None, None
         self._init_tokenizer(model_path, engine.n_vocab)
         return self
 
@@ -128,6 +149,9 @@ class Llama:
         max_tokens = min(max_tokens, self._n_ctx - len(prompt_tokens))
         sd = seed if seed is not None else self._seed
         lp_kw = {} if logprobs is None else {"logprobs": int(logprobs), "prompt_logprobs": bool(echo)}
+        draft = getattr(self, "_draft", None)
+        if draft is not None:  # only when set: engine fronts without the keyword keep working
+            lp_kw["draft"] = draft
         req = self._engine.submit(prompt_tokens, max_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
                                   min_p=min_p, repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty,
                                   presence_penalty=presence_penalty, seed=None if sd == LLAMA_DEFAULT_SEED else sd,
