@@ -18,6 +18,10 @@
  *   mx_submit_lp / mx_request_logprobs
  *                      <- create_completion(logprobs=k): Llama.logits_to_logprobs + the top-k sort
  *   mx_submit_spec     <- Llama(draft_model=LlamaPromptLookupDecoding(...)): generate()'s draft / verify loop
+ *   mx_submit_embed / mx_wait_embed
+ *                      <- Llama(embedding=True).embed / create_embedding: llama_decode of the inputs, then
+ *                         llama_get_embeddings (pooling NONE) / llama_get_embeddings_seq (MEAN, CLS, LAST)
+ *   mx_pool_probe      <- the kernels behind them (result_norm, the pooling graph, _normalize_embedding) alone
  *   mx_engine_destroy  <- llama_free / llama_free_model (Llama.__del__)
  * The Python layer (llama-p2p_amd/llama.py) mirrors the Llama class on top of
  * this ABI, so handle_requests / cached_inference / distributed_inference /
@@ -213,6 +217,37 @@ int mx_draft_probe(int device, int R, const int32_t* tokens, int stride, const i
 int mx_accept_probe(int device, int R, int D, int V, const float* logits, const int32_t* draft, const int32_t* n_draft,
                     const int32_t* pos0, int32_t* a, int32_t* emitted, int32_t* next_id, int32_t* new_pos,
                     int32_t* counts);
+
+/* Embeddings (llama-cpp-python's Llama(embedding=True).embed / create_embedding), DESIGN.md §11.  Per row of the
+ * last layer's f32 residual stream x: y = (x * 1/sqrtf(mean(x^2) + eps)) * output_norm.weight in f32 (ggml's
+ * result_norm, with the engine's canonical sum of squares); then over the rows of one sequence of T tokens:
+ * NONE every y, MEAN per column (((y0 + y1) + y2) + ...) / T in f32 in position order, CLS y0, LAST y(T-1);
+ * normalize != 0: every output vector v becomes v / ||v|| (a vector of norm 0 stays as it is; never NaN).
+ * All of it runs on the device; only the result crosses to the host. */
+#define MX_POOL_NONE 0
+#define MX_POOL_MEAN 1
+#define MX_POOL_CLS 2
+#define MX_POOL_LAST 3
+/* n_req embedding requests queued atomically (as mx_submit_batch): one batched prefill without lm_head.  Each
+ * takes a KV slot while it runs and evaluates its whole prompt (no prefix reuse); the slot keeps the prompt's
+ * K/V for a later completion to reuse.  lens[i] 1..n_ctx (0: MX_ERR_ARG, above n_ctx: MX_ERR_CTX); pooling
+ * MX_POOL_*, anything else MX_ERR_ARG; a pipeline-stage engine: MX_ERR_STATE.  mx_wait / mx_poll /
+ * mx_request_logprobs on such a request give MX_ERR_ARG. */
+int mx_submit_embed(mx_engine* e, int n_req, const int32_t* const* ids, const int32_t* lens, int pooling, int normalize,
+                    uint64_t* reqs);
+/* Blocks until the request is done; copies rows * n_embd floats (rows = its length for MX_POOL_NONE, else 1) and
+ * releases it.  Too small a cap: *rows_out set, MX_ERR_ARG, nothing released (as mx_wait).  MX_ERR_ARG for a
+ * request that is not an embedding request. */
+int mx_wait_embed(mx_engine* e, uint64_t req, float* out, size_t cap_floats, int* rows_out);
+/* The same kernels through the same launch sequence on caller-supplied rows, no engine (tests on inputs no model
+ * produces): x f32 [rows][n] (1 <= rows <= 32768, n % 64 == 0, 64 <= n <= 16384, rows * n <= 2^26), w f32 [n];
+ * sequence q is rows [seq_begin[q], seq_begin[q + 1]) (seq_begin [n_seq + 1] strictly increasing from 0 to rows);
+ * x is processed in chunks of chunk_rows rows (a multiple of 16; 0: one chunk), the MEAN running sums carried
+ * between chunks as the engine carries them.  out: [(NONE ? rows : n_seq) + 64][n], filled with 0xFF bytes before
+ * the first launch (the last 64 rows are a guard that must come back as 0xFF).  Anything else is MX_ERR_ARG and
+ * nothing is launched. */
+int mx_pool_probe(int device, int rows, int n, const float* x, const float* w, float eps, int n_seq,
+                  const int32_t* seq_begin, int chunk_rows, int pooling, int normalize, float* out);
 
 /* The production attention launchers on caller-supplied q / K / V, no engine (tests on inputs no model
  * produces).  Geometry: head_dim 64 or 128, n_head / n_head_kv in {1, 2, 4, 8}; caches of n_slots slots with

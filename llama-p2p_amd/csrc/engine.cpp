@@ -77,6 +77,61 @@ const Shape kShapes[] = {
 // decode steps the scheduler runs on the device between host syncs when every active row is greedy
 constexpr int SCHED_KMAX = 8;
 
+// ---- embeddings.  The tail of one forward chunk: its rows of the final residual stream x
+// through the f32 output norm, the pooling and the L2 normalisation (kernels.h launch_embd_*).
+// One EmbdSeg per sequence with rows in the chunk: rows [row0, row0 + rows) of x are its positions
+// [done, done + rows) of T; seq is its accumulator row, dst0 its first output row -- of ybuf for MX_POOL_NONE
+// (one output row per row), of pooled otherwise.  MEAN norms every row into ybuf (compacted from row 0), then
+// one thread per 4 columns adds a segment's rows in order to the sequence's running sum, carried in acc[seq]
+// between chunks; CLS / LAST norm the one row that counts straight into pooled.  L2 runs in place on the
+// vectors this chunk completed.  tab: host copy of the index tables, alive until the stream is synchronised.
+struct EmbdSeg {
+  int row0, rows, seq, done, T, dst0;
+};
+// ints the tables of a chunk of `rows` rows in `segs` sequences can take: src, dst and L2 rows (<= rows each,
+// MEAN: L2 <= segs) plus EMBD_SEG per segment
+constexpr size_t embd_tab_ints(size_t rows, size_t segs) { return 3 * rows + (EMBD_SEG + 1) * segs; }
+int embd_tail(const float* x, const float* w, float eps, int n, const std::vector<EmbdSeg>& segs, int pooling,
+              bool normalize, float* ybuf, float* acc, float* pooled, int* d_tab, size_t tab_ints,
+              std::vector<int32_t>& tab, hipStream_t s) {
+  std::vector<int32_t> src, dst, l2, sg;
+  int k = 0;
+  for (const EmbdSeg& g : segs) {
+    const bool last = g.done + g.rows == g.T;
+    if (pooling == MX_POOL_NONE) {
+      for (int j = 0; j < g.rows; j++) src.push_back(g.row0 + j), dst.push_back(g.dst0 + j), l2.push_back(g.dst0 + j);
+    } else if (pooling == MX_POOL_MEAN) {
+      for (int j = 0; j < g.rows; j++) src.push_back(g.row0 + j), dst.push_back(k + j);
+      const int32_t e[EMBD_SEG] = {k, g.rows, g.seq, g.dst0, g.done == 0, last ? g.T : 0};
+      sg.insert(sg.end(), e, e + EMBD_SEG);
+      if (last) l2.push_back(g.dst0);
+      k += g.rows;
+    } else if (pooling == MX_POOL_CLS ? g.done == 0 : last) {
+      src.push_back(pooling == MX_POOL_CLS ? g.row0 : g.row0 + g.rows - 1);
+      dst.push_back(g.dst0);
+      l2.push_back(g.dst0);
+    }
+  }
+  const size_t ns = src.size(), nl = l2.size(), nseg = sg.size() / EMBD_SEG;
+  if (ns == 0) return 0;  // CLS / LAST: no sequence starts / ends in this chunk
+  tab.assign(src.begin(), src.end());
+  tab.insert(tab.end(), dst.begin(), dst.end());
+  tab.insert(tab.end(), l2.begin(), l2.end());
+  tab.insert(tab.end(), sg.begin(), sg.end());
+  if (tab.size() > tab_ints) return fail(MX_ERR_ARG, "embedding tail: too many rows for the index tables");
+  HIPC(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+  const bool rows_to_ybuf = pooling == MX_POOL_NONE || pooling == MX_POOL_MEAN;
+  if (launch_embd_norm(rows_to_ybuf ? ybuf : pooled, x, w, d_tab, d_tab + ns, (int)ns, n, eps, s))
+    return fail(MX_ERR_ARG, "embedding norm launch shape");
+  if (pooling == MX_POOL_MEAN && launch_embd_mean(ybuf, d_tab + 2 * ns + nl, (int)nseg, n, acc, pooled, s))
+    return fail(MX_ERR_ARG, "embedding mean launch shape");
+  if (normalize && nl &&
+      launch_embd_l2(pooling == MX_POOL_NONE ? ybuf : pooled, d_tab + 2 * ns, (int)nl, n, s))
+    return fail(MX_ERR_ARG, "embedding L2 launch shape");
+  HIPC(hipGetLastError());
+  return 0;
+}
+
 // synth.py tensor ids
 constexpr uint64_t TID_TOK_EMBD = 1, TID_OUT_NORM = 2, TID_OUTPUT = 3;
 enum { L_ATTN_NORM, L_Q, L_K, L_V, L_O, L_FFN_NORM, L_GATE, L_UP, L_DOWN };
@@ -166,6 +221,11 @@ struct Request {
   // counters cover the speculating steps whose tokens the request kept
   int spec_d = 0, spec_ng = 0;
   uint64_t spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
+  // embedding request (mx_submit_embed): no tokens -- its prefill pass leaves embd_rows vectors of
+  // n_embd floats in embd_out (one per prompt token for MX_POOL_NONE, else one) and finishes it
+  bool embd = false, embd_l2 = false;
+  int embd_pool = 0, embd_rows = 0;
+  std::vector<float> embd_out;
   // one entry [tok_lp | kr top log-probs | kr top ids as int bits] of a round that ran with kr >= lp_k
   void lp_append(const float* entry, int kr) {
     lp_tok.push_back(entry[0]);
@@ -419,6 +479,13 @@ struct mx_engine {
   int sched_step(std::vector<Request*>& rows);
   int prefill_batch(std::vector<Request*>& reqs);
   int prefill_prompt_logprobs(Request* r);
+  // embeddings: per KV slot the running MEAN sum of a sequence that spans chunks and its pooled
+  // vector, [n_seq_max][n_embd] each; the row / segment tables of a chunk's tail launches.  The normed rows of a
+  // chunk go to q, which nothing reads once a forward without lm_head has ended.
+  float *embd_acc = nullptr, *embd_pooled = nullptr;
+  int* d_embd_tab = nullptr;
+  static constexpr size_t EMBD_TAB_CAP = embd_tab_ints(PREFILL_ROWS, PREFILL_ROWS / 16);  // a sequence starts a 16-row block
+  int prefill_embed(std::vector<Request*>& reqs);
   int* sched_hist = nullptr;        // [MAX_ROWS][SCHED_KMAX] tokens of a multi-step greedy run
   int* sched_hist_count = nullptr;  // [MAX_ROWS]
   // speculating rounds: graphs by (requests, draft rows per request), and the device state
@@ -559,6 +626,11 @@ int mx_engine::init_common() {
     if (int rc = alloc((void**)&spec_hist_count, SPEC_MAX_REQ * 4)) return rc;
     if (int rc = alloc((void**)&spec_cnt, SPEC_MAX_REQ * 3 * 4)) return rc;
     if (int rc = alloc((void**)&spec_log, SPEC_MAX_REQ * SCHED_KMAX * 2 * 4)) return rc;
+  }
+  if (has_embed && has_head) {
+    if (int rc = alloc((void**)&embd_acc, (size_t)n_seq_max * n_embd * 4)) return rc;
+    if (int rc = alloc((void**)&embd_pooled, (size_t)n_seq_max * n_embd * 4)) return rc;
+    if (int rc = alloc((void**)&d_embd_tab, EMBD_TAB_CAP * 4)) return rc;
   }
   if (wq8 || wkq) {
     const size_t kmax = std::max(n_embd, n_ff);
@@ -1751,7 +1823,7 @@ void mx_engine::samp_row(const Request* r, SampRow* o) const {
 // reads it), lm_head only on each request's last prompt row, and the first token by the device
 // argmax (ties -> lowest id) or, for sampling requests, the device sampling chain (the host sampler
 // when a request's settings are outside the device chain's range).
-int mx_engine::prefill_batch(std::vector<Request*>& reqs) {
+int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   struct Log {
@@ -1762,7 +1834,16 @@ int mx_engine::prefill_batch(std::vector<Request*>& reqs) {
         fprintf(stderr, "sched: prefill %zu requests %.3f ms\n", n,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
-  } log{t0, reqs.size()};
+  } log{t0, admitted.size()};
+  // embedding requests are evaluated in a pass of their own (no lm_head, every row pooled); a round without
+  // them runs on the admitted list as it is
+  std::vector<Request*> embd_reqs, gen_reqs;
+  for (Request* r : admitted) (r->embd ? embd_reqs : gen_reqs).push_back(r);
+  if (!embd_reqs.empty()) {
+    if (int rc = prefill_embed(embd_reqs)) return rc;
+    if (gen_reqs.empty()) return 0;
+  }
+  std::vector<Request*>& reqs = embd_reqs.empty() ? admitted : gen_reqs;
   // requests with prompt log-probabilities first evaluate prompt[0..n-1) in a pass of their own (all rows
   // through lm_head); what is left of them is the last prompt row, which joins the batch below
   for (Request* r : reqs)
@@ -1939,6 +2020,125 @@ int mx_engine::prefill_prompt_logprobs(Request* r) {
   for (int j = 0; j < n; j++) r->lp_append(all.data() + (size_t)j * stride, k);
   r->lp_n_prompt = n;
   r->reuse = n;
+  return 0;
+}
+
+// The embedding requests of a round (mx_submit_embed): their whole prompts (reuse = 0) laid
+// out and padded to 16-row blocks as in prefill_batch, in chunks of the same size, each chunk one forward
+// without lm_head followed by the tail over its real rows (embd_tail; the padding rows are in no segment).
+// The vectors are copied to the requests; the scheduler then finishes them without a decode step.
+int mx_engine::prefill_embed(std::vector<Request*>& reqs) {
+  std::vector<int32_t> slots, pos, ids;
+  std::vector<int> beg(reqs.size());
+  for (size_t ri = 0; ri < reqs.size(); ri++) {
+    Request* r = reqs[ri];
+    const int n = (int)r->prompt.size();
+    beg[ri] = (int)slots.size();
+    for (int p = 0; p < n; p++) {
+      slots.push_back(r->slot);
+      pos.push_back(p);
+      ids.push_back(r->prompt[p]);
+    }
+    const int pad = (16 - n % 16) % 16;
+    for (int k = 0; k < pad; k++) {
+      slots.push_back(r->slot);
+      pos.push_back(n + pad <= n_ctx ? n + k : n - 1);
+      ids.push_back(r->prompt[n - 1]);
+    }
+    r->pos = n;
+    r->embd_rows = r->embd_pool == MX_POOL_NONE ? n : 1;
+    r->embd_out.assign((size_t)r->embd_rows * n_embd, 0.f);
+  }
+  const int chunk = gemm_ok() ? PREFILL_ROWS : MAX_ROWS;
+  const int total = (int)slots.size();
+  hipStream_t st = stream;
+  const size_t h = n_embd;
+  std::vector<std::vector<int32_t>> tabs;  // host index tables, read by async copies until the chunk's sync
+  struct Stage {  // pooled vectors of one tail, copied in one piece: v [owner.size()][n_embd] for reqs[owner[j]]
+    std::vector<size_t> owner;
+    std::vector<float> v;
+  };
+  std::vector<Stage> stages;
+  static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
+  for (int i = 0; i < total; i += chunk) {
+    const int e = std::min(total, i + chunk), m = e - i;
+    const auto t_chunk = std::chrono::steady_clock::now();
+    HIPC(hipMemcpyAsync(d_ids, ids.data() + i, m * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_pos, pos.data() + i, m * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_slot, slots.data() + i, m * 4, hipMemcpyHostToDevice, st));
+    rows_distinct = false;
+    rows_blocked = blocked_rows(slots.data() + i, pos.data() + i, ids.data() + i, m);
+    prefill_gemm = true;
+    const int frc = enqueue_forward(m, d_ids, d_pos, d_slot, nullptr, nullptr, false, nullptr, 0, false, nullptr,
+                                    nullptr, nullptr, 0, nullptr, 0, st);
+    rows_blocked = false;
+    prefill_gemm = false;
+    if (frc) {
+      hipStreamSynchronize(st);
+      return frc;
+    }
+    std::chrono::steady_clock::time_point t_fwd;
+    if (trace) {  // forward and tail timed apart (the extra synchronise only when tracing)
+      hipStreamSynchronize(st);
+      t_fwd = std::chrono::steady_clock::now();
+    }
+    // the requests of one mx_submit_embed call share pooling and normalize, but two calls may share a round:
+    // one tail per (pooling, normalize) present, each followed by its copies (the next tail reuses q and the
+    // pooled vectors).  The pooled vectors a tail completes are consecutive rows of embd_pooled: one copy.
+    tabs.clear();
+    stages.clear();
+    for (int mode = 0; mode < 8; mode++) {
+      const int pooling = mode >> 1;
+      const bool l2 = mode & 1;
+      std::vector<EmbdSeg> segs;
+      std::vector<size_t> owner;
+      Stage sg_out;
+      int k = 0;
+      for (size_t ri = 0; ri < reqs.size(); ri++) {
+        Request* r = reqs[ri];
+        if (r->embd_pool != pooling || r->embd_l2 != l2) continue;
+        const int n = (int)r->prompt.size();
+        const int a = std::max(beg[ri], i), b = std::min(beg[ri] + n, e);
+        if (a >= b) continue;
+        const bool completes = pooling == MX_POOL_CLS ? a == beg[ri] : b == beg[ri] + n;
+        int dst0 = k;  // NONE: the rows compacted in q
+        if (pooling != MX_POOL_NONE) {
+          dst0 = (int)sg_out.owner.size();
+          if (completes) sg_out.owner.push_back(ri);
+        }
+        segs.push_back({a - i, b - a, r->slot, a - beg[ri], n, dst0});
+        owner.push_back(ri);
+        k += b - a;
+      }
+      if (segs.empty()) continue;
+      tabs.emplace_back();
+      int rc = embd_tail(x, out_norm, eps, n_embd, segs, pooling, l2, q, embd_acc, embd_pooled, d_embd_tab,
+                         EMBD_TAB_CAP, tabs.back(), st);
+      if (!rc && pooling == MX_POOL_NONE) {
+        for (size_t g = 0; g < segs.size() && !rc; g++)
+          if (hipMemcpyAsync(reqs[owner[g]]->embd_out.data() + segs[g].done * h, q + segs[g].dst0 * h,
+                             segs[g].rows * h * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = fail(MX_ERR_HIP, "embedding copy");
+      } else if (!rc && !sg_out.owner.empty()) {
+        sg_out.v.resize(sg_out.owner.size() * h);
+        if (hipMemcpyAsync(sg_out.v.data(), embd_pooled, sg_out.v.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+          rc = fail(MX_ERR_HIP, "embedding copy");
+        stages.push_back(std::move(sg_out));
+      }
+      if (rc) {
+        hipStreamSynchronize(st);
+        return rc;
+      }
+    }
+    HIPC(hipStreamSynchronize(st));
+    for (const Stage& sg : stages)
+      for (size_t j = 0; j < sg.owner.size(); j++)
+        memcpy(reqs[sg.owner[j]]->embd_out.data(), sg.v.data() + j * h, h * 4);
+    if (trace)
+      fprintf(stderr, "sched: embed chunk %d rows: forward %.3f ms, tail + copies %.3f ms\n", m,
+              std::chrono::duration<double, std::milli>(t_fwd - t_chunk).count(),
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fwd).count());
+  }
   return 0;
 }
 
@@ -2262,7 +2462,7 @@ void mx_engine::scheduler_loop() {
         r->slot = free_slots[best];
         free_slots.erase(free_slots.begin() + best);
         // at least the last prompt token is evaluated (its logits start generation)
-        r->reuse = r->lp_prompt ? 0 : std::min(best_lcp, (int)r->prompt.size() - 1);
+        r->reuse = (r->lp_prompt || r->embd) ? 0 : std::min(best_lcp, (int)r->prompt.size() - 1);
         stat_prompt_tokens += r->prompt.size();
         stat_reused_tokens += r->reuse;
         admit.push_back(r);
@@ -2276,6 +2476,10 @@ void mx_engine::scheduler_loop() {
         if (rc) {
           r->error = g_err;
           finish(r, MX_FINISH_ERROR);
+          continue;
+        }
+        if (r->embd) {  // no tokens: its vectors are in embd_out, the slot keeps the prompt's K/V
+          finish(r, MX_FINISH_STOP);
           continue;
         }
         const int32_t t = r->out.back();
@@ -3180,6 +3384,7 @@ int mx_wait(mx_engine* e, uint64_t req, int32_t* out_ids, int cap, int* n_out, i
     auto it = e->requests.find(req);
     if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
     Request* rp = it->second.get();
+    if (rp->embd) return fail(MX_ERR_ARG, "mx_wait: an embedding request (use mx_wait_embed)");
     e->cv_done.wait(lk, [&] { return rp->done; });
     if (n_out) *n_out = (int)rp->out.size();
     if ((int)rp->out.size() > cap && rp->finish != MX_FINISH_ERROR)
@@ -3202,6 +3407,7 @@ int mx_poll(mx_engine* e, uint64_t req, int n_have, int32_t* out_ids, int cap, i
   auto it = e->requests.find(req);
   if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
   Request* rp = it->second.get();
+  if (rp->embd) return fail(MX_ERR_ARG, "mx_poll: an embedding request (use mx_wait_embed)");
   e->cv_done.wait(lk, [&] { return rp->done || (int)rp->out.size() > n_have; });
   const int n = (int)rp->out.size();
   if (out_ids && cap > 0) memcpy(out_ids, rp->out.data(), (size_t)std::min(cap, n) * 4);
@@ -3216,6 +3422,125 @@ int mx_cancel(mx_engine* e, uint64_t req) {
   auto it = e->requests.find(req);
   if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
   it->second->cancel = true;
+  return 0;
+}
+
+// all-or-nothing as mx_submit_batch: validated first, then queued under one lock, so the scheduler admits
+// them in one round and prefill_embed evaluates them in one batched pass
+int mx_submit_embed(mx_engine* e, int n_req, const int32_t* const* ids, const int32_t* lens, int pooling, int normalize,
+                    uint64_t* reqs) {
+  if (!e || n_req < 1 || !ids || !lens || !reqs) return fail(MX_ERR_ARG, "bad arguments");
+  if (pooling < MX_POOL_NONE || pooling > MX_POOL_LAST)
+    return fail(MX_ERR_ARG, "mx_submit_embed: pooling must be MX_POOL_NONE, MEAN, CLS or LAST");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit_embed needs a full-model engine");
+  std::vector<std::unique_ptr<Request>> rs(n_req);
+  for (int i = 0; i < n_req; i++) {
+    const int n = lens[i];
+    if (!ids[i] || n < 1) return fail(MX_ERR_ARG, "mx_submit_embed: empty input");
+    if (n > e->n_ctx)
+      return fail(MX_ERR_CTX, "Requested tokens (" + std::to_string(n) + ") exceed context window of " +
+                                  std::to_string(e->n_ctx));
+    for (int j = 0; j < n; j++)
+      if (ids[i][j] < 0 || ids[i][j] >= e->n_vocab) return fail(MX_ERR_ARG, "token id out of range");
+    rs[i] = std::make_unique<Request>();
+    rs[i]->prompt.assign(ids[i], ids[i] + n);
+    mx_sampling_default(&rs[i]->samp);
+    rs[i]->embd = true;
+    rs[i]->embd_pool = pooling;
+    rs[i]->embd_l2 = normalize != 0;
+  }
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->stop) return fail(MX_ERR_STATE, "engine shutting down");
+    for (int i = 0; i < n_req; i++) {
+      Request* r = rs[i].get();
+      r->id = e->next_id++;
+      reqs[i] = r->id;
+      e->pending.push_back(r);
+      e->requests[r->id] = std::move(rs[i]);
+    }
+    if (!e->worker_started) {
+      e->worker_started = true;
+      e->worker = std::thread([e] { e->scheduler_loop(); });
+    }
+  }
+  e->cv.notify_all();
+  return 0;
+}
+
+int mx_wait_embed(mx_engine* e, uint64_t req, float* out, size_t cap_floats, int* rows_out) {
+  if (!e) return fail(MX_ERR_ARG, "null engine");
+  std::unique_ptr<Request> r;
+  {
+    std::unique_lock<std::mutex> lk(e->mu);
+    auto it = e->requests.find(req);
+    if (it == e->requests.end()) return fail(MX_ERR_NOTFOUND, "unknown request id");
+    Request* rp = it->second.get();
+    if (!rp->embd) return fail(MX_ERR_ARG, "mx_wait_embed: not an embedding request (use mx_wait)");
+    e->cv_done.wait(lk, [&] { return rp->done; });
+    const bool ok = rp->finish != MX_FINISH_ERROR && rp->embd_rows > 0;
+    if (rows_out) *rows_out = ok ? rp->embd_rows : 0;
+    if (ok && (rp->embd_out.size() > cap_floats || !out))
+      return fail(MX_ERR_ARG, "mx_wait_embed: " + std::to_string(rp->embd_out.size()) + " floats do not fit cap " +
+                                  std::to_string(cap_floats) + " (request kept; retry with a larger buffer)");
+    r = std::move(it->second);
+    e->requests.erase(it);
+  }
+  if (r->finish == MX_FINISH_ERROR) return fail(MX_ERR_STATE, "request failed: " + r->error);
+  if (r->embd_rows == 0) return fail(MX_ERR_STATE, "request was cancelled before it ran");
+  memcpy(out, r->embd_out.data(), r->embd_out.size() * 4);
+  return 0;
+}
+
+int mx_pool_probe(int device, int rows, int n, const float* x, const float* w, float eps, int n_seq,
+                  const int32_t* seq_begin, int chunk_rows, int pooling, int normalize, float* out) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  constexpr int MAXR = 32768;
+  if (!x || !w || !seq_begin || !out || rows < 1 || rows > MAXR || n < 64 || n % 64 || n > 16384 ||
+      (size_t)rows * n > ((size_t)1 << 26))
+    return fail(MX_ERR_ARG, "mx_pool_probe: 1 <= rows <= 32768, n a multiple of 64 in [64, 16384], rows * n <= 2^26, "
+                            "non-null buffers");
+  if (pooling < MX_POOL_NONE || pooling > MX_POOL_LAST || chunk_rows < 0 || chunk_rows % 16)
+    return fail(MX_ERR_ARG, "mx_pool_probe: pooling 0..3, chunk_rows a multiple of 16 (0: one chunk)");
+  if (n_seq < 1 || n_seq > rows || seq_begin[0] != 0 || seq_begin[n_seq] != rows)
+    return fail(MX_ERR_ARG, "mx_pool_probe: seq_begin [n_seq + 1] must start at 0 and end at rows");
+  for (int q = 0; q < n_seq; q++)
+    if (seq_begin[q + 1] <= seq_begin[q]) return fail(MX_ERR_ARG, "mx_pool_probe: seq_begin must increase");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const int chunk = chunk_rows ? std::min(chunk_rows, rows) : rows;
+  const size_t N = n, out_rows = (size_t)(pooling == MX_POOL_NONE ? rows : n_seq) + PROBE_GUARD_ROWS;
+  const size_t tab_cap = embd_tab_ints(chunk, chunk);
+  DevBufs bufs;
+  float *d_x, *d_w, *d_y, *d_acc, *d_out;
+  int* d_tab;
+  if (!bufs.alloc(&d_x, (size_t)rows * N * 4) || !bufs.alloc(&d_w, N * 4) || !bufs.alloc(&d_y, (size_t)chunk * N * 4) ||
+      !bufs.alloc(&d_acc, (size_t)n_seq * N * 4) || !bufs.alloc(&d_out, out_rows * N * 4) ||
+      !bufs.alloc(&d_tab, tab_cap * 4))
+    return fail(MX_ERR_HIP, "mx_pool_probe: device allocation");
+  HIPC(hipMemcpy(d_x, x, (size_t)rows * N * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_w, w, N * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_y, 0xFF, (size_t)chunk * N * 4));  // a value never written reads back as NaN
+  HIPC(hipMemset(d_acc, 0xFF, (size_t)n_seq * N * 4));
+  HIPC(hipMemset(d_out, 0xFF, out_rows * N * 4));
+  HIPC(hipDeviceSynchronize());
+  std::vector<int32_t> tab;
+  for (int c0 = 0; c0 < rows; c0 += chunk) {
+    const int c1 = std::min(rows, c0 + chunk);
+    std::vector<EmbdSeg> segs;
+    for (int q = 0; q < n_seq; q++) {
+      const int a = std::max(seq_begin[q], c0), b = std::min(seq_begin[q + 1], c1);
+      if (a < b)
+        segs.push_back({a - c0, b - a, q, a - seq_begin[q], seq_begin[q + 1] - seq_begin[q],
+                        pooling == MX_POOL_NONE ? a : q});
+    }
+    // MX_POOL_NONE: the rows go straight to their place in out; MEAN: to the chunk's scratch, as in the engine
+    const int rc = embd_tail(d_x + (size_t)c0 * N, d_w, eps, n, segs, pooling, normalize != 0,
+                             pooling == MX_POOL_NONE ? d_out : d_y, d_acc, d_out, d_tab, tab_cap, tab, nullptr);
+    const hipError_t se = hipDeviceSynchronize();  // tab is reused by the next chunk
+    if (rc) return rc;
+    HIPC(se);
+  }
+  HIPC(hipMemcpy(out, d_out, out_rows * N * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -126,6 +126,18 @@ void launch_embed(float* x, const uint16_t* tok_embd, const int* ids, int M, int
 void launch_ssq(const float* x, int M, int n, float* ssq, hipStream_t s);
 void launch_rmsnorm(uint16_t* y, int ldy, const float* x, const float* w, const int* row_map, int M, int n,
                     float eps, hipStream_t s);
+// ---- embeddings: final RMS_NORM + MUL in f32, pooling, L2 normalisation; n % 64 == 0,
+// n <= 16384 (-1 otherwise, nothing launched).  src / dst / rows: device row indices, nullptr = 0, 1, 2, ...
+// norm: y[dst[c]] = (x[src[c]] * rms_scale(Σx², n, eps)) * w for c < M, Σx² the canonical sum of launch_rmsnorm
+int launch_embd_norm(float* y, const float* x, const float* w, const int* src, const int* dst, int M, int n,
+                     float eps, hipStream_t s);
+// mean: seg [n_seg][EMBD_SEG] = {first y row, rows >= 1, acc row, out row, first, T}: the running sum of a
+// sequence -- its first row (first != 0) or acc[acc row] -- plus the segment's rows of y in order goes to
+// acc[acc row] (T == 0: more rows follow in a later chunk) or, divided by T, to out[out row]
+constexpr int EMBD_SEG = 6;
+int launch_embd_mean(const float* y, const int* seg, int n_seg, int n, float* acc, float* out, hipStream_t s);
+// l2: v[rows[c]] /= ||v[rows[c]]|| in place for c < M (canonical Σv²); a vector of norm 0 is left as it is
+int launch_embd_l2(float* v, const int* rows, int M, int n, hipStream_t s);
 int launch_mm(int epi, const MMArgs& a, hipStream_t s);
 // canonical K groups of a bf16 GEMV shape (= the K split of its 17..64-row mm_wide launch)
 int canon_kgroups(int epi, int N, int K);

@@ -267,6 +267,169 @@ void launch_rmsnorm(uint16_t* y, int ldy, const float* x, const float* w, const 
 }
 
 // ---------------------------------------------------------------------------
+// Embeddings: the tail ggml's result_norm and pooling graph perform on the f32
+// residual stream of the last layer -- final RMS_NORM + MUL kept in f32, pooling over the rows of a
+// sequence, optional L2 normalisation.  Every sum has one order: the sums of squares are the canonical
+// ones above (so a row gives the same bits at every row count and in every chunk), the mean adds a
+// column's rows in position order inside one thread.
+// ---------------------------------------------------------------------------
+// y[dst[c]] = (x[src[c]] * scale) * w in f32: norm_kernel's layout (one 1024-thread work-group per row,
+// every load issued up front) without the slabs and without the bf16 rounding
+template <int IT>
+__global__ __launch_bounds__(1024) void embd_norm_kernel(float* y, const float* x, const float* w, const int* src,
+                                                         const int* dst, int n, float eps) {
+  const int c = blockIdx.x;
+  const float* xr = x + (size_t)(src ? src[c] : c) * n;
+  float* yr = y + (size_t)(dst ? dst[c] : c) * n;
+  const int tid = threadIdx.x;
+  f32x4 v[IT], g[IT];
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int i = (it * 1024 + tid) * 4;
+    v[it] = *reinterpret_cast<const f32x4*>(xr + i);
+    g[it] = *reinterpret_cast<const f32x4*>(w + i);
+  }
+  __shared__ __attribute__((aligned(16))) float part[IT * 256];
+  __shared__ float sc_sh;
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {  // thread 4T+i holds values 4i..4i+3 of tile T (+256 it)
+    double q = ssq4(v[it]);
+    q += __shfl_xor(q, 1);
+    q += __shfl_xor(q, 2);
+    if ((tid & 3) == 0) part[it * 256 + (tid >> 2)] = (float)q;
+  }
+  __syncthreads();
+  if (tid < 64) {
+    f32x4 q[IT];
+#pragma unroll
+    for (int p = 0; p < IT; ++p) q[p] = *reinterpret_cast<const f32x4*>(part + 256 * p + 4 * tid);
+    const double sum = ssq_wave(ssq_lane(q, tid, n / 16));
+    if (tid == 0) sc_sh = rms_scale(sum, n, eps);
+  }
+  __syncthreads();
+  const float scale = sc_sh;
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (v[it][j] * scale) * g[it][j];
+    *reinterpret_cast<f32x4*>(yr + (it * 1024 + tid) * 4) = o;
+  }
+}
+
+// The row sum of squares of v[0..n) (n % 64 == 0, n <= NORM_GENERIC_MAXN) in the canonical form, by a
+// 256-thread work-group: every thread returns it.  part: NORM_GENERIC_MAXN / 16 floats of LDS.
+__device__ __forceinline__ double row_ssq_256(const float* v, int n, float* part, double* sum_sh) {
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {  // n % 64 == 0: the 4 threads of a tile share a pass
+    double q = ssq4(*reinterpret_cast<const f32x4*>(v + i));
+    q += __shfl_xor(q, 1);
+    q += __shfl_xor(q, 2);
+    if ((threadIdx.x & 3) == 0) part[i >> 4] = (float)q;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    constexpr int P = NORM_GENERIC_MAXN / 4096;
+    f32x4 q[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+      q[p] = *reinterpret_cast<const f32x4*>(part + min(256 * p + 4 * (int)threadIdx.x, n / 16 - 4));
+    const double sum = ssq_wave(ssq_lane(q, threadIdx.x, n / 16));
+    if (threadIdx.x == 0) *sum_sh = sum;
+  }
+  __syncthreads();
+  return *sum_sh;
+}
+
+__global__ __launch_bounds__(256) void embd_norm_generic_kernel(float* y, const float* x, const float* w,
+                                                                const int* src, const int* dst, int n, float eps) {
+  const int c = blockIdx.x;
+  const float* xr = x + (size_t)(src ? src[c] : c) * n;
+  float* yr = y + (size_t)(dst ? dst[c] : c) * n;
+  __shared__ __attribute__((aligned(16))) float part[NORM_GENERIC_MAXN / 16];
+  __shared__ double sum_sh;
+  const float scale = rms_scale(row_ssq_256(xr, n, part, &sum_sh), n, eps);
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
+    const f32x4 g = *reinterpret_cast<const f32x4*>(w + i);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (v[j] * scale) * g[j];
+    *reinterpret_cast<f32x4*>(yr + i) = o;
+  }
+}
+
+int launch_embd_norm(float* y, const float* x, const float* w, const int* src, const int* dst, int M, int n,
+                     float eps, hipStream_t s) {
+  if (M < 1 || n < 64 || n % 64 || n > NORM_GENERIC_MAXN) return -1;
+  if (n == 4096)
+    embd_norm_kernel<1><<<M, 1024, 0, s>>>(y, x, w, src, dst, n, eps);
+  else if (n == 8192)
+    embd_norm_kernel<2><<<M, 1024, 0, s>>>(y, x, w, src, dst, n, eps);
+  else
+    embd_norm_generic_kernel<<<M, 256, 0, s>>>(y, x, w, src, dst, n, eps);
+  return 0;
+}
+
+// MEAN pooling.  Segment g (grid.y) = EMBD_SEG ints {first y row, rows (>= 1), accumulator row, output row,
+// first, T}: the running sum of a sequence starts from its first row (first != 0) or from acc, takes the
+// segment's rows in order, and goes back to acc (T == 0: the sequence continues in a later chunk) or,
+// divided by T, to out.  A thread owns 4 columns from start to end: (((y0 + y1) + y2) + ...) / T.
+__global__ __launch_bounds__(256) void embd_mean_kernel(const float* y, const int* seg, int n, float* acc, float* out) {
+  const int* sg = seg + EMBD_SEG * blockIdx.y;
+  const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  const int rows = sg[1], T = sg[5];
+  const float* yp = y + (size_t)sg[0] * n + i;
+  float* ap = acc + (size_t)sg[2] * n + i;
+  f32x4 a;
+  int t = 0;
+  if (sg[4]) {
+    a = *reinterpret_cast<const f32x4*>(yp);
+    t = 1;
+  } else {
+    a = *reinterpret_cast<const f32x4*>(ap);
+  }
+#pragma unroll 8
+  for (; t < rows; ++t) a += *reinterpret_cast<const f32x4*>(yp + (size_t)t * n);
+  if (T > 0) {
+    const float d = (float)T;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = a[j] / d;
+    *reinterpret_cast<f32x4*>(out + (size_t)sg[3] * n + i) = a;
+  } else {
+    *reinterpret_cast<f32x4*>(ap) = a;
+  }
+}
+
+int launch_embd_mean(const float* y, const int* seg, int n_seg, int n, float* acc, float* out, hipStream_t s) {
+  if (n_seg < 1 || n_seg > 65535 || n < 64 || n % 64) return -1;
+  embd_mean_kernel<<<dim3((n / 4 + 255) / 256, n_seg), 256, 0, s>>>(y, seg, n, acc, out);
+  return 0;
+}
+
+// v[rows[c]] /= ||v[rows[c]]|| in place, the sum of squares in the canonical form; a vector of norm 0
+// stays as it is (llama-cpp-python's _normalize_embedding), so the result is never NaN
+__global__ __launch_bounds__(256) void embd_l2_kernel(float* v, const int* rows, int n) {
+  float* vr = v + (size_t)(rows ? rows[blockIdx.x] : blockIdx.x) * n;
+  __shared__ __attribute__((aligned(16))) float part[NORM_GENERIC_MAXN / 16];
+  __shared__ double sum_sh;
+  const float nrm = (float)sqrt(row_ssq_256(vr, n, part, &sum_sh));
+  if (nrm == 0.0f) return;
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    f32x4 o = *reinterpret_cast<const f32x4*>(vr + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = o[j] / nrm;
+    *reinterpret_cast<f32x4*>(vr + i) = o;
+  }
+}
+
+int launch_embd_l2(float* v, const int* rows, int M, int n, hipStream_t s) {
+  if (M < 1 || n < 64 || n % 64 || n > NORM_GENERIC_MAXN) return -1;
+  embd_l2_kernel<<<M, 256, 0, s>>>(v, rows, n);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // MUL_MAT with bf16 weights for 1..64 tokens (decode GEMV / skinny GEMM) with
 // fused epilogues.  
 //

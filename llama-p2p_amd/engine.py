@@ -32,7 +32,9 @@ EXPORTS = [
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
     "mx_attention_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
+    "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
 ]
+POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3  # mx_engine.h MX_POOL_*: how embed() pools a sequence's rows
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
 SPEC_MAX_DRAFT = 15  # kernels.h: most draft tokens per speculating step (1 + 15 rows of the <= 16-row path)
 
@@ -190,6 +192,9 @@ def lib() -> ctypes.CDLL:
         L.mx_spec_stats.argtypes = [vp, u64, P(MxSpecCounts)]
         L.mx_draft_probe.argtypes = [i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
         L.mx_accept_probe.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mx_submit_embed.argtypes = [vp, i32, vp, vp, i32, i32, P(u64)]
+        L.mx_wait_embed.argtypes = [vp, u64, vp, ctypes.c_size_t, P(i32)]
+        L.mx_pool_probe.argtypes = [i32, i32, i32, vp, vp, ctypes.c_float, i32, vp, i32, i32, i32, vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -488,6 +493,34 @@ def norm_probe(x, slabs=None, w=None, row_map=None, eps: float = 0.0, device: in
             yo[M:] if yo is not None else None)
 
 
+def pool_probe(x, w, seq_begin, pooling: int, normalize: bool = False, chunk_rows: int = 0, eps: float = 1e-5,
+               out=None, device: int = 0):
+    """The embedding tail on caller-supplied rows (no engine; include/mx_engine.h mx_pool_probe): x f32
+    [rows][n], w f32 [n], sequence q = rows [seq_begin[q], seq_begin[q + 1]), x taken in chunks of chunk_rows
+    rows (0: one chunk).  Returns (vectors [rows][n] for POOL_NONE else [n_seq][n], guard [64][n] as uint32: must
+    be all-ones bits).  out (optional): a caller-owned buffer for the result (tests of refusals)."""
+    xa = np.ascontiguousarray(x, dtype=np.float32)
+    if xa.ndim != 2:
+        raise ValueError("x [rows][n] expected")
+    rows, n = xa.shape
+    wa = np.ascontiguousarray(w, dtype=np.float32)
+    if wa.size != n:
+        raise ValueError("w [n] expected")
+    sb = _i32(seq_begin)
+    n_seq = len(sb) - 1
+    n_out = max(rows if pooling == POOL_NONE else n_seq, 0)
+    if out is None:
+        ob = np.zeros((n_out + PROBE_GUARD_ROWS, n), dtype=np.float32)
+    else:
+        ob = out
+        if not ob.flags.c_contiguous or ob.dtype != np.float32 or ob.size < (n_out + PROBE_GUARD_ROWS) * n:
+            raise ValueError("out too small")
+    _check(lib().mx_pool_probe(device, rows, n, xa.ctypes.data, wa.ctypes.data, eps, n_seq, sb.ctypes.data,
+                               int(chunk_rows), int(pooling), int(bool(normalize)), ob.ctypes.data))
+    flat = ob.reshape(-1)[:(n_out + PROBE_GUARD_ROWS) * n].reshape(-1, n)
+    return flat[:n_out], flat[n_out:].view(np.uint32)
+
+
 def _check(rc: int):
     if rc != MX_OK:
         raise MxError(rc, lib().mx_last_error().decode(errors="replace"))
@@ -502,6 +535,7 @@ class Engine:
 
     supports_logprobs = True  # submit(logprobs=) / logprobs(): what Llama.create_completion(logprobs=) needs
     supports_draft = True  # submit(draft=) / spec_stats(): what Llama(draft_model=LlamaPromptLookupDecoding()) needs
+    supports_embeddings = True  # embed(): what Llama(embedding=True).embed / create_embedding need
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
@@ -704,6 +738,29 @@ class Engine:
 
     def generate(self, ids, max_tokens: int, **kw):
         return self.wait(self.submit(ids, max_tokens, **kw))
+
+    def embed(self, prompts, pooling: int = POOL_NONE, normalize: bool = False):
+        """Embeddings of token sequences, computed on the device (final norm, pooling, L2 normalisation): one
+        mx_submit_embed call -- a batched prefill without lm_head -- then one np.float32 array per prompt,
+        [len(prompt)][n_embd] for POOL_NONE, [1][n_embd] for POOL_MEAN / POOL_CLS / POOL_LAST."""
+        n = len(prompts)
+        arrs = [_i32(p) for p in prompts]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        lens = _i32([len(a) for a in arrs])
+        reqs = (ctypes.c_uint64 * max(n, 1))()
+        _check(lib().mx_submit_embed(self._h, n, ptrs, lens.ctypes.data, int(pooling), int(bool(normalize)), reqs))
+        outs, err = [], None
+        for i in range(n):  # every request is released, also after a failure
+            rows = len(arrs[i]) if pooling == POOL_NONE else 1
+            out = np.empty((rows, self.n_embd), dtype=np.float32)
+            got = ctypes.c_int32()
+            rc = lib().mx_wait_embed(self._h, reqs[i], out.ctypes.data, out.size, ctypes.byref(got))
+            if rc != MX_OK and err is None:
+                err = MxError(rc, lib().mx_last_error().decode(errors="replace"))
+            outs.append(out[:got.value])
+        if err is not None:
+            raise err
+        return outs
 
     # -- device-resident batches (bench, pipeline) ---------------------------
     def batch(self, slots, pos, ids=None, max_steps: int = 0) -> "Batch":

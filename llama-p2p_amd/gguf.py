@@ -454,7 +454,8 @@ def _mixed_type(wtype: str, name: str) -> int:
 
 
 def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = None, wtype: str = "bf16",
-                         dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None):
+                         dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None,
+                         pooling_type: int = None):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
     "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
@@ -464,7 +465,8 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     rope_freqs: a rope_freqs.weight tensor (head_dim/2 f32, Llama-3.1 style); rope_scaling:
     (type, factor) written as llama.rope.scaling.type / .factor.  embd_type: token_embd.weight as this
     type instead (GGML_Q8_0 or GGML_F16 of the synthetic bf16 table; llama-quantize
-    --token-embedding-type)."""
+    --token-embedding-type).  pooling_type: written as llama.pooling_type (an embedding model's default pooling,
+    llama.h enum llama_pooling_type)."""
     from . import synth
 
     if wtype not in ("bf16", "q8_0", "q4_0_synth") and wtype not in MIXED:
@@ -488,6 +490,8 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     if rope_scaling is not None:
         w.add_string("llama.rope.scaling.type", rope_scaling[0])
         w.add_float32("llama.rope.scaling.factor", rope_scaling[1])
+    if pooling_type is not None:
+        w.add_uint32("llama.pooling_type", pooling_type)
     w.add_uint32("llama.vocab_size", shape.n_vocab)
     toks, scores, types = synthetic_spm_vocab(shape.n_vocab)
     w.add_string("tokenizer.ggml.model", "llama")

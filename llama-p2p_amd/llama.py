@@ -11,6 +11,15 @@ version current at the reference's date).  The
 compute runs in the MI355X engine (engine.py -> libmxllama.so); calls release
 the GIL, and concurrent calls from several threads are micro-batched by the
 engine's scheduler instead of being serialised.
+
+Embeddings (``Llama(embedding=True)``, ``embed``, ``create_embedding``, ``pooling_type``) follow the same
+version.  llama_cpp is not installed here, so the contract is pinned as read from its source (llama.py
+``Llama.embed`` / ``create_embedding`` / ``_normalize_embedding``): a str gives one item and a list a list; an
+item is a list of floats with pooling and a list of per-token lists with LLAMA_POOLING_TYPE_NONE; inputs are
+tokenised with BOS and cut to n_batch tokens (``truncate``) or refused with its ``ValueError``; the
+``RuntimeError`` without ``embedding=True``; ``(result, total_tokens)`` with ``return_count``; the OpenAI-style
+dict of ``create_embedding``.  The final norm, the pooling and the L2 normalisation run on the device
+(DESIGN.md §11); the host does not normalise again.  LLAMA_POOLING_TYPE_RANK is not supported.
 """
 from __future__ import annotations
 
@@ -26,15 +35,24 @@ from .speculative import LlamaDraftModel, LlamaPromptLookupDecoding
 from .tokenizer import Tokenizer
 
 LLAMA_DEFAULT_SEED = 0xFFFFFFFF
+# llama.h enum llama_pooling_type (RANK = 4 is refused: it needs a classification head)
+LLAMA_POOLING_TYPE_UNSPECIFIED = -1
+LLAMA_POOLING_TYPE_NONE = 0
+LLAMA_POOLING_TYPE_MEAN = 1
+LLAMA_POOLING_TYPE_CLS = 2
+LLAMA_POOLING_TYPE_LAST = 3
+_POOLING_TYPES = (LLAMA_POOLING_TYPE_NONE, LLAMA_POOLING_TYPE_MEAN, LLAMA_POOLING_TYPE_CLS, LLAMA_POOLING_TYPE_LAST)
 
 
 class Llama:
     def __init__(self, model_path: str, *, n_gpu_layers: int = -1, seed: int = LLAMA_DEFAULT_SEED, n_ctx: int = 512,
                  n_batch: int = 512, n_threads: Optional[int] = None, n_threads_batch: Optional[int] = None,
                  verbose: bool = True, n_seq_max: int = 64, device: int = -1, synthetic_seed: int = 0,
-                 draft_model: Optional[LlamaDraftModel] = None, **kwargs: Any):
-        # n_gpu_layers / n_threads / n_batch are accepted for signature compatibility: the whole model
-        # always runs on the GPU, and prompts are processed in 64-row chunks.
+                 draft_model: Optional[LlamaDraftModel] = None, embedding: bool = False,
+                 pooling_type: int = LLAMA_POOLING_TYPE_UNSPECIFIED, **kwargs: Any):
+        # n_gpu_layers / n_threads are accepted for signature compatibility: the whole model always runs on
+        # the GPU.  n_batch only bounds the tokens of one embed() input, as in llama-cpp-python.
+        self._check_pooling_type(pooling_type)
         self.model_path = model_path
         self.verbose = verbose
         self._seed = seed
@@ -48,7 +66,27 @@ class Llama:
         self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
                                       seed=synthetic_seed)
         self._n_ctx = n_ctx
+        self.n_batch = min(n_batch, n_ctx)
+        self._embedding = bool(embedding)
         self._init_tokenizer(model_path, self._engine.info.n_vocab)
+        self._pooling_type = self._resolve_pooling_type(pooling_type)
+
+    @staticmethod
+    def _check_pooling_type(pooling_type: int):
+        if pooling_type != LLAMA_POOLING_TYPE_UNSPECIFIED and pooling_type not in _POOLING_TYPES:
+            raise ValueError(f"pooling_type must be LLAMA_POOLING_TYPE_UNSPECIFIED, NONE, MEAN, CLS or LAST "
+                             f"(got {pooling_type}; LLAMA_POOLING_TYPE_RANK is not supported)")
+
+    def _resolve_pooling_type(self, pooling_type: int) -> int:
+        """UNSPECIFIED: the GGUF's llama.pooling_type if it has one, else NONE (llama.cpp's choice for a
+        model without the key)."""
+        self._check_pooling_type(pooling_type)
+        if pooling_type != LLAMA_POOLING_TYPE_UNSPECIFIED:
+            return int(pooling_type)
+        md = int(self.metadata.get("llama.pooling_type", LLAMA_POOLING_TYPE_NONE))
+        if md not in _POOLING_TYPES:
+            raise ValueError(f"llama.pooling_type = {md} in {self.model_path} is not supported")
+        return md
 
     @staticmethod
     def _draft_numbers(draft_model):
@@ -69,14 +107,19 @@ class Llama:
 
     @classmethod
     def from_engine(cls, model_path: str, engine, n_ctx: int = 512, seed: int = LLAMA_DEFAULT_SEED,
-                    verbose: bool = True) -> "Llama":
+                    verbose: bool = True, n_batch: int = 512, embedding: bool = False,
+                    pooling_type: int = LLAMA_POOLING_TYPE_UNSPECIFIED) -> "Llama":
         """A Llama over another engine object with Engine's request methods (submit / poll / cancel /
-        wait, n_vocab, n_embd) -- the pipeline server's rank-0 front (pipeserve.py)."""
+        wait, n_vocab, n_embd) -- the pipeline server's rank-0 front (pipeserve.py).  embed() needs an
+        engine with supports_embeddings and embed()."""
+        cls._check_pooling_type(pooling_type)
         self = cls.__new__(cls)
         self.model_path, self.verbose, self._seed = model_path, verbose, seed
         self._engine, self._n_ctx = engine, n_ctx
         self.draft_model, self._draft = None, None
+        self.n_batch, self._embedding = min(n_batch, n_ctx), bool(embedding)
         self._init_tokenizer(model_path, engine.n_vocab)
+        self._pooling_type = self._resolve_pooling_type(pooling_type)
         return self
 
     def _init_tokenizer(self, model_path: str, n_vocab: int):
@@ -103,6 +146,9 @@ class Llama:
 
     def n_embd(self) -> int:
         return self._engine.n_embd
+
+    def pooling_type(self) -> int:
+        return getattr(self, "_pooling_type", LLAMA_POOLING_TYPE_NONE)
 
     def token_bos(self) -> int:
         return self.tokenizer_.bos_id
@@ -292,6 +338,45 @@ class Llama:
                 self._engine.cancel(req)
             toks, finish = self._engine.wait(req)
         yield self._chunk(cid, created, "", "stop" if cut >= 0 or finish == _engine.FINISH_STOP else "length")
+
+    # ---------------------------------------------------------- embeddings
+    def embed(self, input: Union[str, List[str]], normalize: bool = False, truncate: bool = True,
+              return_count: bool = False):
+        """Embeddings of a str (one item) or a list of str (a list of items), llama-cpp-python's Llama.embed:
+        an item is a list of n_embd floats with MEAN / CLS / LAST pooling and a list of such lists, one per
+        token, with LLAMA_POOLING_TYPE_NONE.  All inputs go to the engine in one call -- one batched prefill
+        without lm_head; output norm, pooling and (normalize) v / ||v|| run on the device."""
+        if not getattr(self, "_embedding", False):
+            raise RuntimeError("Llama model must be created with embedding=True to call this method")
+        if not getattr(self._engine, "supports_embeddings", False):
+            raise NotImplementedError("embeddings are not supported by this engine front")
+        n_batch = getattr(self, "n_batch", self._n_ctx)
+        inputs = [input] if isinstance(input, str) else list(input)
+        prompts, total_tokens = [], 0
+        for text in inputs:
+            tokens = self.tokenize(text.encode("utf-8"))
+            if truncate:
+                tokens = tokens[:n_batch]
+            if len(tokens) > n_batch:
+                raise ValueError(f"Requested tokens ({len(tokens)}) exceed batch size of {n_batch}")
+            total_tokens += len(tokens)
+            prompts.append(tokens)
+        pooling = self.pooling_type()
+        vecs = self._engine.embed(prompts, pooling=pooling, normalize=bool(normalize)) if prompts else []
+        if pooling == LLAMA_POOLING_TYPE_NONE:
+            data = [[[float(v) for v in row] for row in a] for a in vecs]
+        else:
+            data = [[float(v) for v in a[0]] for a in vecs]
+        output = data[0] if isinstance(input, str) else data
+        return (output, total_tokens) if return_count else output
+
+    def create_embedding(self, input: Union[str, List[str]], model: Optional[str] = None) -> Dict[str, Any]:
+        """llama-cpp-python's Llama.create_embedding: the OpenAI-style embedding object."""
+        inputs = input if isinstance(input, list) else [input]
+        embeddings, total_tokens = self.embed(inputs, return_count=True)
+        data = [{"object": "embedding", "embedding": e, "index": i} for i, e in enumerate(embeddings)]
+        return {"object": "list", "data": data, "model": model if model is not None else self.model_path,
+                "usage": {"prompt_tokens": total_tokens, "total_tokens": total_tokens}}
 
     def __call__(self, prompt: Union[str, List[int]], *args, **kwargs) -> Dict[str, Any]:
         return self.create_completion(prompt, *args, **kwargs)
