@@ -264,6 +264,35 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
                        int nslab, const float* rope_cs, void* kcache, void* vcache, void* out);
 
+/* Prefix sharing across KV slots (llama-cpp-python's Llama.set_cache(LlamaRAMCache())), DESIGN.md §12.  Off by
+ * default.  On: at admission a request whose prompt shares a longer prefix with the tokens another slot holds
+ * K/V for -- free or busy, or a request admitted earlier in the same round -- than with its own slot's gets those
+ * positions by a device copy between the slots (one launch for all copies of a round) instead of evaluating
+ * them, when that saves at least 16 positions.  Requests with prompt log-probabilities and embedding requests
+ * evaluate their whole prompt as before (their slots serve as sources).  Takes effect at the next admission; a
+ * pipeline-stage engine returns MX_ERR_STATE. */
+int mx_engine_set_prefix_sharing(mx_engine* e, int on);
+/* shared_prompt_tokens: prompt positions a request received by a copy (mx_stats.reused_prompt_tokens keeps
+ * counting only the positions kept in place); copies: slot-to-slot copies; copied_bytes: bytes they wrote;
+ * follower_requests: requests that waited for a request of their own round and copied its prefix. */
+typedef struct {
+  uint64_t shared_prompt_tokens, copies, copied_bytes, follower_requests;
+} mx_sharing_stats;
+int mx_prefix_sharing_stats(mx_engine* e, mx_sharing_stats* out);
+/* The copy kernel on caller-supplied caches, no engine.  kcache / vcache: the raw tiled bytes of
+ * n_layer * n_slots * n_head_kv * ctx_stride * head_dim f16 each ([layer][slot][kv head], ctx_stride = n_ctx
+ * rounded up to 64), at most 1 GiB each, copied to the device verbatim and copied back after the launch.  Copy i
+ * moves positions [0, P), P = n_pos rounded up to 32, of slot src_slot to slot dst_slot in every layer and kv
+ * head of both caches; every other byte stays.  n_layer 1..256, n_slots 1..4096, n_head_kv 1..64, head_dim 64 or
+ * 128, n_ctx 1..2^20, 1 <= n_copies <= n_slots; slots in range, src_slot != dst_slot, 1 <= n_pos <= n_ctx, no
+ * slot a destination twice, none both a source and a destination.  Anything else is MX_ERR_ARG and nothing is
+ * launched. */
+typedef struct {
+  int32_t src_slot, dst_slot, n_pos;
+} mx_kv_copy;
+int mx_kv_copy_probe(int device, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx, int n_copies,
+                     const mx_kv_copy* copies, void* kcache, void* vcache);
+
 /* The production bf16 matmul launchers on caller-supplied W / X, no engine (tests on shapes no model has).
  * path 0 launch_mm (M 1..64), 1 launch_mm_pers (M 1..16, shapes of mx_matmul_plan's pers_ok), 2 launch_mm_wide
  * (M 1..64), 3 launch_mm_wide with full_chain, 4 launch_gemm_split (M 65..4096 as in the engine, `target`

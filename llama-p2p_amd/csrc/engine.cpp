@@ -401,8 +401,22 @@ struct mx_engine {
   std::map<uint64_t, std::unique_ptr<Request>> requests;
   std::vector<int> free_slots;
   // prefix-KV reuse (llama-cpp-python's Llama.generate keeps the longest common prefix of the previous
-  // evaluation): tokens whose K/V each slot holds at positions 0..n-1, valid while the slot is free
+  // evaluation): tokens whose K/V each slot holds at positions 0..n-1.  Of a busy slot too: cut to the
+  // request's reuse at admission, its whole prompt after the prefill, prompt + out[:-1] cut at its pos after
+  // every round (note_kv) -- what prefix sharing copies from
   std::vector<std::vector<int32_t>> slot_tokens;
+  void note_kv(const Request* r);
+  // prefix sharing across slots (mx_engine_set_prefix_sharing): a copy has to save at least SHARE_MIN positions
+  // -- one prefill row block; below it the block's recomputation is cheaper than a launch
+  static constexpr int SHARE_MIN = 16;
+  bool prefix_sharing = false;
+  KvCopy* d_kvcopy = nullptr;  // [n_seq_max] the copy tables of a round
+  uint64_t stat_shared_tokens = 0, stat_copies = 0, stat_copied_bytes = 0, stat_followers = 0;
+  // the copies of `tab` in one launch.  The admission rule never makes a table the launcher refuses: a
+  // destination is a free slot, taken once; a source that beats the destination's own match is not free (the
+  // destination rule would have taken it), and a slot a copy fills never matches better than the slot it is
+  // filled from, which wins the tie -- so no slot is both
+  int run_kv_copies(const std::vector<KvCopy>& tab);
   uint64_t stat_prompt_tokens = 0, stat_reused_tokens = 0, stat_generated_tokens = 0;
   uint64_t next_id = 1;
   bool stop = false;
@@ -617,6 +631,7 @@ int mx_engine::init_common() {
   if (int rc = alloc((void**)&sched_hist, (size_t)MAX_ROWS * SCHED_KMAX * 4)) return rc;
   if (int rc = alloc((void**)&sched_hist_count, (size_t)MAX_ROWS * 4)) return rc;
   if (int rc = alloc((void**)&d_samp, (size_t)MAX_ROWS * sizeof(SampRow))) return rc;
+  if (int rc = alloc((void**)&d_kvcopy, (size_t)n_seq_max * sizeof(KvCopy))) return rc;
   if (has_embed && has_head && !wq8 && !wkq) {
     if (int rc = alloc((void**)&spec_ctx, (size_t)SPEC_MAX_REQ * n_ctx * 4)) return rc;
     if (int rc = alloc((void**)&spec_len, SPEC_MAX_REQ * 4)) return rc;
@@ -1721,6 +1736,46 @@ int mx_engine::forward_rows_chunk(int n, const int32_t* slots, const int32_t* po
 }
 
 // ---------------------------------------------------------------- scheduler
+// The slot's record after a round of a live request (under mu): K/V are valid for the prompt and every generated
+// token but the last (never fed back), and only below r->pos -- a speculating round leaves the K/V of rejected
+// drafts past it, which must not count.  The record is a prefix of that sequence already, so it only grows.
+void mx_engine::note_kv(const Request* r) {
+  if (r->slot < 0) return;
+  std::vector<int32_t>& st = slot_tokens[r->slot];
+  const size_t np = r->prompt.size(), total = np + (r->out.empty() ? 0 : r->out.size() - 1);
+  const size_t n = std::min(total, (size_t)std::max(0, r->pos));
+  if (st.size() > n) st.resize(n);
+  for (size_t k = st.size(); k < n; k++) st.push_back(k < np ? r->prompt[k] : r->out[k - np]);
+}
+
+int mx_engine::run_kv_copies(const std::vector<KvCopy>& tab) {
+  static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
+  const int n = (int)tab.size();
+  if (n < 1) return 0;
+  if (n > n_seq_max) return fail(MX_ERR_STATE, "more KV copies than slots in one round");
+  hipStream_t s = stream;
+  HIPC(hipMemcpyAsync(d_kvcopy, tab.data(), (size_t)n * sizeof(KvCopy), hipMemcpyHostToDevice, s));
+  std::chrono::steady_clock::time_point t0;
+  if (trace) {  // the launch timed alone (the extra synchronise only when tracing)
+    hipStreamSynchronize(s);
+    t0 = std::chrono::steady_clock::now();
+  }
+  if (launch_kv_copy(kcache, vcache, tab.data(), d_kvcopy, n, le - lb, n_seq_max, n_head_kv, head_dim, n_ctx,
+                     ctx_stride, slot_stride, layer_kv_stride, s)) {
+    hipStreamSynchronize(s);
+    return fail(MX_ERR_STATE, "KV copy table refused");
+  }
+  HIPC(hipStreamSynchronize(s));  // tab is the caller's: the table upload has read it
+  const size_t bytes = kv_copy_bytes(tab.data(), n, le - lb, n_head_kv, head_dim, ctx_stride);
+  if (trace)
+    fprintf(stderr, "sched: kv copy %d copies %zu bytes %.3f ms\n", n, bytes,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  std::lock_guard<std::mutex> lk(mu);
+  stat_copies += n;
+  stat_copied_bytes += bytes;
+  return 0;
+}
+
 void mx_engine::finish(Request* r, int why) {
   r->finish = why;
   r->done = true;
@@ -2262,6 +2317,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
       r->spec_steps++, r->spec_drafted += nd, r->spec_accepted += kept - 1;
       stat_spec_steps++, stat_spec_drafted += nd, stat_spec_accepted += kept - 1;
     }
+    note_kv(r);  // up to the kept position only
   }
   if (trace) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2423,6 +2479,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
       if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
       else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
     }
+    note_kv(r);
   }
   return 0;
 }
@@ -2431,6 +2488,16 @@ void mx_engine::scheduler_loop() {
   hipSetDevice(device);
   for (;;) {
     std::vector<Request*> admit;
+    // prefix sharing: the round's copies from slots as they stand (pre) and from requests of this
+    // round to their followers (post); all empty while the switch is off
+    std::vector<Request*> followers;
+    std::vector<KvCopy> pre, post;
+    auto lcp = [](const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
+      int l = 0;
+      const int lim = (int)std::min(a.size(), b.size());
+      while (l < lim && a[l] == b[l]) l++;
+      return l;
+    };
     {
       std::unique_lock<std::mutex> lk(mu);
       cv.wait(lk, [&] { return stop || !pending.empty() || !active.empty(); });
@@ -2462,22 +2529,76 @@ void mx_engine::scheduler_loop() {
         r->slot = free_slots[best];
         free_slots.erase(free_slots.begin() + best);
         // at least the last prompt token is evaluated (its logits start generation)
-        r->reuse = (r->lp_prompt || r->embd) ? 0 : std::min(best_lcp, (int)r->prompt.size() - 1);
+        const int n = (int)r->prompt.size();
+        r->reuse = (r->lp_prompt || r->embd) ? 0 : std::min(best_lcp, n - 1);
         stat_prompt_tokens += r->prompt.size();
         stat_reused_tokens += r->reuse;
+        if (prefix_sharing && !r->lp_prompt && !r->embd) {
+          // the longest match over every other slot's record, free or busy (ties: a slot no copy of this round
+          // writes, so no slot is both a source and a destination); worth a copy when it beats the slot's own by
+          // SHARE_MIN
+          int cur = best_lcp, src_slot = -1, src = -1;
+          bool src_written = false;
+          for (int s = 0; s < n_seq_max; s++) {
+            if (s == r->slot) continue;
+            const int l = lcp(slot_tokens[s], r->prompt);
+            const bool written = std::any_of(pre.begin(), pre.end(), [&](const KvCopy& c) { return c.dst == s; });
+            if (l > src || (l == src && src_written && !written)) src = l, src_slot = s, src_written = written;
+          }
+          const bool copy = src_slot >= 0 && src - cur >= SHARE_MIN;
+          if (copy) cur = src;
+          // ... or a request admitted earlier in this round that evaluates the prefix itself (not a follower)
+          Request* lead = nullptr;
+          int fl = -1;
+          for (Request* a : admit) {
+            if (std::find(followers.begin(), followers.end(), a) != followers.end()) continue;
+            const int l = lcp(a->prompt, r->prompt);
+            if (l > fl) fl = l, lead = a;
+          }
+          if (lead && fl - cur >= SHARE_MIN) {
+            cur = fl;
+            r->reuse = std::min(cur, n - 1);
+            post.push_back({lead->slot, r->slot, r->reuse});
+            followers.push_back(r);
+            stat_followers++;
+          } else if (copy) {
+            r->reuse = std::min(cur, n - 1);
+            pre.push_back({src_slot, r->slot, r->reuse});
+          }
+          stat_shared_tokens += r->reuse - std::min(best_lcp, n - 1);
+        }
+        // the record of the now busy slot: what it holds once the copies from slots as they stand have run (a
+        // follower's copy runs after the others' prefill: until then its slot holds its own match only)
+        const bool follows = !followers.empty() && followers.back() == r;
+        const int held = follows ? std::min(best_lcp, n - 1) : r->reuse;
+        slot_tokens[r->slot].assign(r->prompt.begin(), r->prompt.begin() + held);
         admit.push_back(r);
       }
     }
     std::lock_guard<std::mutex> glk(gpu_mu);
     if (!admit.empty()) {
-      const int rc = prefill_batch(admit);
+      // copies from slots as they stand, then the prefill -- with followers: the others' prefill, one copy launch
+      // from their slots, the followers' prefill.  Without sharing this is prefill_batch(admit), as ever.
+      int rc = run_kv_copies(pre);
+      if (!rc && followers.empty()) {
+        rc = prefill_batch(admit);
+      } else if (!rc) {
+        std::vector<Request*> leaders;
+        for (Request* r : admit)
+          if (std::find(followers.begin(), followers.end(), r) == followers.end()) leaders.push_back(r);
+        rc = prefill_batch(leaders);
+        if (!rc) rc = run_kv_copies(post);
+        if (!rc) rc = prefill_batch(followers);
+      }
       std::lock_guard<std::mutex> lk(mu);
       for (Request* r : admit) {
         if (rc) {
+          if (!pre.empty() || !post.empty()) r->pos = 0;  // a copy or a prefill may not have run: the slot keeps no record
           r->error = g_err;
           finish(r, MX_FINISH_ERROR);
           continue;
         }
+        slot_tokens[r->slot] = r->prompt;
         if (r->embd) {  // no tokens: its vectors are in embd_out, the slot keeps the prompt's K/V
           finish(r, MX_FINISH_STOP);
           continue;
@@ -3801,6 +3922,63 @@ int mx_engine_stats(mx_engine* e, mx_stats* out) {
   out->prompt_tokens = e->stat_prompt_tokens;
   out->reused_prompt_tokens = e->stat_reused_tokens;
   out->generated_tokens = e->stat_generated_tokens;
+  return 0;
+}
+
+int mx_engine_set_prefix_sharing(mx_engine* e, int on) {
+  if (!e) return fail(MX_ERR_ARG, "null engine");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "prefix sharing needs a whole-model engine");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->prefix_sharing = on != 0;
+  return 0;
+}
+
+int mx_prefix_sharing_stats(mx_engine* e, mx_sharing_stats* out) {
+  if (!e || !out) return fail(MX_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  out->shared_prompt_tokens = e->stat_shared_tokens;
+  out->copies = e->stat_copies;
+  out->copied_bytes = e->stat_copied_bytes;
+  out->follower_requests = e->stat_followers;
+  return 0;
+}
+
+int mx_kv_copy_probe(int device, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx, int n_copies,
+                     const mx_kv_copy* copies, void* kcache, void* vcache) {
+  // every index the kernel forms is checked before anything is launched: the geometry here, the table below
+  if (!copies || !kcache || !vcache) return fail(MX_ERR_ARG, "mx_kv_copy_probe: non-null copies / caches");
+  if (n_layer < 1 || n_layer > 256 || n_slots < 1 || n_slots > 4096 || n_head_kv < 1 || n_head_kv > 64 ||
+      (head_dim != 64 && head_dim != 128) || n_ctx < 1 || n_ctx > (1 << 20))
+    return fail(MX_ERR_ARG, "mx_kv_copy_probe: n_layer 1..256, n_slots 1..4096, n_head_kv 1..64, head_dim 64 or 128, "
+                            "n_ctx 1..2^20");
+  if (n_copies < 1 || n_copies > n_slots) return fail(MX_ERR_ARG, "mx_kv_copy_probe: 1 <= n_copies <= n_slots");
+  const int ctx_stride = (n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+  const size_t slot_stride = (size_t)n_head_kv * ctx_stride * head_dim, layer_kv_stride = slot_stride * n_slots;
+  const size_t cache_elems = layer_kv_stride * n_layer;
+  if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_kv_copy_probe: caches above 1 GiB each");
+  // the table itself is the launcher's to judge (the scheduler relies on the same refusals): it checks the host
+  // copy and launches nothing on a bad entry
+  std::vector<KvCopy> tab(n_copies);
+  for (int i = 0; i < n_copies; i++) tab[i] = {copies[i].src_slot, copies[i].dst_slot, copies[i].n_pos};
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs bufs;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  KvCopy* d_tab = nullptr;
+  if (!bufs.alloc(&d_k, cache_elems * 2) || !bufs.alloc(&d_v, cache_elems * 2) ||
+      !bufs.alloc(&d_tab, tab.size() * sizeof(KvCopy)))
+    return fail(MX_ERR_HIP, "mx_kv_copy_probe: device allocation");
+  HIPC(hipMemcpy(d_k, kcache, cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_v, vcache, cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(KvCopy), hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  if (launch_kv_copy(d_k, d_v, tab.data(), d_tab, n_copies, n_layer, n_slots, n_head_kv, head_dim, n_ctx, ctx_stride,
+                     slot_stride, layer_kv_stride, nullptr))
+    return fail(MX_ERR_ARG, "mx_kv_copy_probe: launch_kv_copy refused the table (a slot out of range, src == dst, n_pos "
+                            "outside [1, n_ctx], a slot a destination twice or both a source and a destination)");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -356,6 +356,22 @@ void launch_copy_f32(float* dst, const float* src, size_t n, hipStream_t s);
 void launch_f32_in(float* x, const float* src, int M, int n, float* ssq, hipStream_t s);  // + Σx² partials
 void launch_bf16_to_f32(float* dst, const uint16_t* src, int M, int n, float* ssq, hipStream_t s);
 
+// Prefix sharing: copy the K/V of positions [0, P), P = min(ceil32(n_pos), ctx_stride), of slot
+// `src` to slot `dst`, for every layer, kv head, K and V of caches laid out [layer][slot][kv head][ctx_stride * D].
+// Tiles are position-major (32 positions = two K position tiles = one V position tile), so that is one
+// contiguous prefix of P * D elements per (layer, slot, kv head) region of each cache.
+struct KvCopy {
+  int32_t src, dst, n_pos;
+};
+// All copies of `tab` (host, n of them; tab_dev: its device copy, already enqueued on s) in one launch.
+// Returns -1 and launches nothing unless 1 <= n, every slot is in [0, n_slots), src != dst, 1 <= n_pos <= n_ctx,
+// no slot is a destination twice and none is both a source and a destination.
+int launch_kv_copy(_Float16* kc, _Float16* vc, const KvCopy* tab, const KvCopy* tab_dev, int n, int n_layer,
+                   int n_slots, int n_head_kv, int head_dim, int n_ctx, int ctx_stride, size_t slot_stride,
+                   size_t layer_kv_stride, hipStream_t s);
+// bytes the launch reads (= bytes it writes)
+size_t kv_copy_bytes(const KvCopy* tab, int n, int n_layer, int n_head_kv, int head_dim, int ctx_stride);
+
 // HBM streaming probes: variant v of probe_variants() (loads in flight, grid, non-temporal) of a
 // read-only (XOR fold) or copy stream over n16 16-byte words (n16 % 4096 == 0); desc describes it
 int probe_variants();

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 namespace mx {
 
@@ -4047,6 +4048,68 @@ __global__ __launch_bounds__(256) void read_probe_kernel(const u32x4* __restrict
   }
   // sink written only when the fold hits a sentinel (never for the probe's fill): keeps the loads live
   if (x[0] == 0x9e3779b9u && x[1] == 0x7f4a7c15u) sink[(size_t)blockIdx.x * 256 + threadIdx.x] = x;
+}
+
+// Prefix sharing (kernels.h KvCopy): grid (chunks of 256 * U 16-byte words, layer x kv head x K|V, copy), lane i of
+// a work-group moves words i, i + 256, ... of its chunk (coalesced, U loads in flight per lane), in the shape
+// of copy_probe_kernel.  A region prefix is a whole number of 256-word rows (32 positions x 64 dims x 2 B = 4 KiB),
+// so a chunk is cut at a row and every lane of a work-group takes the same branch.  Plain loads and stores: a
+// source may feed several copies, and the destination's prefill attention reads the copy next.
+template <int U>
+__global__ __launch_bounds__(256) void kv_copy_kernel(_Float16* kc, _Float16* vc, const KvCopy* __restrict__ tab,
+                                                      int n_head_kv, int head_dim, int ctx_stride, size_t slot_stride,
+                                                      size_t layer_kv_stride) {
+  const KvCopy c = tab[blockIdx.z];
+  const int P = min((c.n_pos + 31) & ~31, ctx_stride);
+  const size_t n16 = (size_t)P * head_dim / 8;
+  const size_t b0 = (size_t)blockIdx.x * 256 * U;
+  if (b0 >= n16) return;
+  const int lh = blockIdx.y >> 1, layer = lh / n_head_kv, head = lh % n_head_kv;
+  _Float16* base = ((blockIdx.y & 1) ? vc : kc) + (size_t)layer * layer_kv_stride + (size_t)head * ctx_stride * head_dim;
+  const u32x4* src = reinterpret_cast<const u32x4*>(base + (size_t)c.src * slot_stride) + b0 + threadIdx.x;
+  u32x4* dst = reinterpret_cast<u32x4*>(base + (size_t)c.dst * slot_stride) + b0 + threadIdx.x;
+  if (b0 + 256 * U <= n16) {
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = src[256 * u];
+#pragma unroll
+    for (int u = 0; u < U; ++u) dst[256 * u] = v[u];
+  } else {
+    const int rows = (int)((n16 - b0) / 256);
+    for (int u = 0; u < rows; ++u) dst[256 * u] = src[256 * u];
+  }
+}
+
+size_t kv_copy_bytes(const KvCopy* tab, int n, int n_layer, int n_head_kv, int head_dim, int ctx_stride) {
+  size_t b = 0;
+  for (int i = 0; i < n; i++)
+    b += (size_t)std::min((tab[i].n_pos + 31) & ~31, ctx_stride) * head_dim * 2 * n_head_kv * n_layer * 2;
+  return b;
+}
+
+int launch_kv_copy(_Float16* kc, _Float16* vc, const KvCopy* tab, const KvCopy* tab_dev, int n, int n_layer,
+                   int n_slots, int n_head_kv, int head_dim, int n_ctx, int ctx_stride, size_t slot_stride,
+                   size_t layer_kv_stride, hipStream_t s) {
+  if (!kc || !vc || !tab || !tab_dev || n < 1 || n > 65535 || n_layer < 1 || n_slots < 1 || n_head_kv < 1 ||
+      (head_dim != 64 && head_dim != 128) || n_ctx < 1 || ctx_stride < n_ctx || ctx_stride % 32 ||
+      (size_t)n_layer * n_head_kv * 2 > 65535)
+    return -1;
+  std::vector<char> role(n_slots, 0);  // 1 source, 2 destination
+  int max_pos = 0;
+  for (int i = 0; i < n; i++) {
+    const KvCopy& c = tab[i];
+    if (c.src < 0 || c.src >= n_slots || c.dst < 0 || c.dst >= n_slots || c.src == c.dst) return -1;
+    if (c.n_pos < 1 || c.n_pos > n_ctx) return -1;
+    if (role[c.dst] || role[c.src] == 2) return -1;
+    role[c.src] = 1;
+    role[c.dst] = 2;
+    max_pos = std::max(max_pos, c.n_pos);
+  }
+  constexpr int U = 4;
+  const size_t n16 = (size_t)std::min((max_pos + 31) & ~31, ctx_stride) * head_dim / 8;
+  const dim3 grid((unsigned)((n16 + 256 * U - 1) / (256 * U)), (unsigned)(n_layer * n_head_kv * 2), (unsigned)n);
+  kv_copy_kernel<U><<<grid, 256, 0, s>>>(kc, vc, tab_dev, n_head_kv, head_dim, ctx_stride, slot_stride, layer_kv_stride);
+  return 0;
 }
 
 template <int U, bool NT>

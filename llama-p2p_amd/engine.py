@@ -33,6 +33,7 @@ EXPORTS = [
     "mx_attention_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
+    "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
 ]
 POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3  # mx_engine.h MX_POOL_*: how embed() pools a sequence's rows
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
@@ -74,6 +75,15 @@ class MxRowSampler(ctypes.Structure):
 
 class MxSpecCounts(ctypes.Structure):
     _fields_ = [("steps", ctypes.c_uint64), ("drafted", ctypes.c_uint64), ("accepted", ctypes.c_uint64)]
+
+
+class MxSharingStats(ctypes.Structure):
+    _fields_ = [("shared_prompt_tokens", ctypes.c_uint64), ("copies", ctypes.c_uint64),
+                ("copied_bytes", ctypes.c_uint64), ("follower_requests", ctypes.c_uint64)]
+
+
+class MxKvCopy(ctypes.Structure):
+    _fields_ = [("src_slot", ctypes.c_int32), ("dst_slot", ctypes.c_int32), ("n_pos", ctypes.c_int32)]
 
 
 class MxMatmulArgs(ctypes.Structure):
@@ -195,6 +205,9 @@ def lib() -> ctypes.CDLL:
         L.mx_submit_embed.argtypes = [vp, i32, vp, vp, i32, i32, P(u64)]
         L.mx_wait_embed.argtypes = [vp, u64, vp, ctypes.c_size_t, P(i32)]
         L.mx_pool_probe.argtypes = [i32, i32, i32, vp, vp, ctypes.c_float, i32, vp, i32, i32, i32, vp]
+        L.mx_engine_set_prefix_sharing.argtypes = [vp, i32]
+        L.mx_prefix_sharing_stats.argtypes = [vp, P(MxSharingStats)]
+        L.mx_kv_copy_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
         for name in EXPORTS:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -330,6 +343,32 @@ def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
     return out, kc, vc
+
+
+def kv_copy_probe(n_layer: int, n_slots: int, n_head_kv: int, head_dim: int, n_ctx: int, copies, kcache, vcache,
+                  device: int = 0, inplace: bool = False):
+    """The prefix-sharing copy kernel on caller-supplied caches (no engine; include/mx_engine.h mx_kv_copy_probe).
+    kcache / vcache: the raw tiled f16 bits (uint16) of n_layer x n_slots x n_head_kv x ctx_stride x head_dim
+    elements each, left untouched unless `inplace` (flat contiguous uint16 arrays the call works on directly: what
+    a test of a refusal reads afterwards); copies: [(src_slot, dst_slot, n_pos)].  Returns (kcache after, vcache
+    after); a refused table raises MxError(MX_ERR_ARG)."""
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    elems = max(n_layer, 0) * max(n_slots, 0) * max(n_head_kv, 0) * ctx_stride * max(head_dim, 0)
+    if inplace:
+        kc, vc = kcache, vcache
+        if any(a.dtype != np.uint16 or a.ndim != 1 or not a.flags.c_contiguous for a in (kc, vc)):
+            raise ValueError("inplace takes flat contiguous uint16 arrays")
+    else:
+        kc = np.array(kcache, dtype=np.uint16, copy=True).reshape(-1)
+        vc = np.array(vcache, dtype=np.uint16, copy=True).reshape(-1)
+    if kc.size != elems or vc.size != elems:
+        raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+    tab = (MxKvCopy * max(len(copies), 1))()
+    for i, (s, d, n) in enumerate(copies):
+        tab[i].src_slot, tab[i].dst_slot, tab[i].n_pos = int(s), int(d), int(n)
+    _check(lib().mx_kv_copy_probe(device, n_layer, n_slots, n_head_kv, head_dim, n_ctx, len(copies), tab,
+                                  kc.ctypes.data, vc.ctypes.data))
+    return kc, vc
 
 
 EPI_F32, EPI_RESID, EPI_QKV, EPI_SWIGLU = 0, 1, 2, 3  # kernels.h Epilogue
@@ -536,10 +575,11 @@ class Engine:
     supports_logprobs = True  # submit(logprobs=) / logprobs(): what Llama.create_completion(logprobs=) needs
     supports_draft = True  # submit(draft=) / spec_stats(): what Llama(draft_model=LlamaPromptLookupDecoding()) needs
     supports_embeddings = True  # embed(): what Llama(embedding=True).embed / create_embedding need
+    supports_prefix_sharing = True  # set_prefix_sharing() / sharing_stats(): what Llama.set_cache needs
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
-                 handoff_bf16: bool = False):
+                 handoff_bf16: bool = False, prefix_sharing: bool = False):
         L = lib()
         opts = MxOpts()
         L.mx_opts_default(ctypes.byref(opts))
@@ -557,6 +597,19 @@ class Engine:
         self.n_vocab = info.n_vocab
         self.n_embd = info.n_embd
         self.n_ctx = info.n_ctx
+        if prefix_sharing:
+            self.set_prefix_sharing(True)
+
+    def set_prefix_sharing(self, on: bool):
+        """Share prompt prefixes across KV slots by device copies (off by default): from the next
+        admission on.  A pipeline-stage engine raises MxError(MX_ERR_STATE)."""
+        _check(lib().mx_engine_set_prefix_sharing(self._h, int(bool(on))))
+
+    def sharing_stats(self) -> dict:
+        """shared_prompt_tokens (prompt positions received by a copy), copies, copied_bytes, follower_requests."""
+        st = MxSharingStats()
+        _check(lib().mx_prefix_sharing_stats(self._h, ctypes.byref(st)))
+        return {k: getattr(st, k) for k, _ in MxSharingStats._fields_}
 
     # -- parity hooks --------------------------------------------------------
     def forward_logits(self, ids: Sequence[int], pos0: int = 0, slot: int = 0) -> np.ndarray:

@@ -31,6 +31,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 
 from . import engine as _engine
 from . import synth as _synth
+from .llama_cache import BaseLlamaCache, LlamaDiskCache
 from .speculative import LlamaDraftModel, LlamaPromptLookupDecoding
 from .tokenizer import Tokenizer
 
@@ -66,6 +67,7 @@ class Llama:
         self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
                                       seed=synthetic_seed)
         self._n_ctx = n_ctx
+        self.cache = None
         self.n_batch = min(n_batch, n_ctx)
         self._embedding = bool(embedding)
         self._init_tokenizer(model_path, self._engine.info.n_vocab)
@@ -117,6 +119,7 @@ class Llama:
         self.model_path, self.verbose, self._seed = model_path, verbose, seed
         self._engine, self._n_ctx = engine, n_ctx
         self.draft_model, self._draft = None, None
+        self.cache = None
         self.n_batch, self._embedding = min(n_batch, n_ctx), bool(embedding)
         self._init_tokenizer(model_path, engine.n_vocab)
         self._pooling_type = self._resolve_pooling_type(pooling_type)
@@ -136,6 +139,23 @@ class Llama:
             self.tokenizer_ = Tokenizer(toks, scores, types, "llama", bos_id=1, eos_id=2)
             self.metadata = {"general.architecture": "llama", "general.name": model_path}
         self._lock = threading.Lock()
+
+    # ---------------------------------------------------------------- prompt cache
+    def set_cache(self, cache: Optional[BaseLlamaCache]):
+        """llama-cpp-python's ``Llama.set_cache``: with a ``BaseLlamaCache`` (``LlamaRAMCache()``) later prompts
+        start from the longest prefix whose K/V the engine already holds -- in any KV slot, free or busy, or being
+        evaluated by another request of the same round -- copied between slots on the device (llama_cache.py,
+        DESIGN.md §12); ``None`` switches that off.  The object is kept in ``Llama.cache``; its ``capacity_bytes``
+        is not used (the cache is the device's KV slots).  ``LlamaDiskCache``, and an engine front without
+        ``supports_prefix_sharing`` (the pipeline server's), raise ``NotImplementedError``."""
+        if cache is not None and not isinstance(cache, BaseLlamaCache):
+            raise TypeError("set_cache takes a BaseLlamaCache (LlamaRAMCache()) or None")
+        if isinstance(cache, LlamaDiskCache):
+            raise NotImplementedError("LlamaDiskCache is not supported: the prompt cache is the device's KV slots")
+        if not getattr(self._engine, "supports_prefix_sharing", False):
+            raise NotImplementedError("this engine front has no prefix sharing (the pipeline server)")
+        self._engine.set_prefix_sharing(cache is not None)
+        self.cache = cache
 
     # ---------------------------------------------------------------- info
     def n_ctx(self) -> int:
