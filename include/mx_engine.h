@@ -17,6 +17,9 @@
  *   mx_forward_logits  <- llama_decode + llama_get_logits (Llama.eval), parity hook
  *   mx_submit_lp / mx_request_logprobs
  *                      <- create_completion(logprobs=k): Llama.logits_to_logprobs + the top-k sort
+ *   mx_submit_ext      <- create_completion(typical_p=, tfs_z=, mirostat_mode=2, logit_bias=): the samplers
+ *                         Llama._init_sampler puts around the default chain (logit bias, tail-free, typical,
+ *                         Mirostat v2); mx_sample_probe runs that chain on caller-supplied rows
  *   mx_submit_spec     <- Llama(draft_model=LlamaPromptLookupDecoding(...)): generate()'s draft / verify loop
  *   mx_submit_embed / mx_wait_embed
  *                      <- Llama(embedding=True).embed / create_embedding: llama_decode of the inputs, then
@@ -184,6 +187,45 @@ int mx_forward_logprobs(mx_engine* e, int n, const int32_t* slots, const int32_t
  * logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64, V <= 262144; outputs as above. */
 int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl, const int32_t* targets, int k,
                      float* tgt_lp, float* top_lp, int32_t* top_idx);
+/* The rest of llama-cpp-python 0.3.1's sampler chain (create_completion's typical_p, tfs_z, mirostat_mode / tau /
+ * eta and logit_bias), on the device inside the multi-step rounds like the chain of mx_sampling:
+ *   logit_bias -> penalties -> then
+ *     temperature <= 0:    greedy argmax (nothing else applies)
+ *     mirostat_mode == 2:  temperature -> Mirostat v2 over the whole vocabulary (no top_k / tfs / typical / top_p / min_p)
+ *     otherwise:           top_k -> tail-free (tfs_z) -> locally typical (typical_p) -> top_p -> min_p -> temperature -> draw
+ * logit_bias: n_logit_bias <= 256 entries (bias_tok[i], bias_val[i]), distinct ids inside the vocabulary, one f32
+ * add each; -inf bans the token, +inf and NaN are refused.  Mirostat v2 keeps per request mu (2 tau at submission,
+ * carried across steps and rounds): tokens with -log2 p <= mu stay (the argmax when none does), the draw walks them
+ * by ascending id, mu -= eta (-log2 p'_tok - tau).  mirostat_mode 1 (a sort of the whole vocabulary), any other
+ * mode, NaN settings and a bad bias table are MX_ERR_ARG.  Log-probabilities stay those of the raw lm_head row.
+ * A request with any of these settings never speculates.  mx_sampling / mx_row_sampler are unchanged. */
+typedef struct {
+  mx_sampling base;
+  float typical_p, tfs_z;   /* 1.0 = off */
+  int32_t mirostat_mode;    /* 0 or 2 */
+  float mirostat_tau, mirostat_eta; /* 5.0, 0.1 */
+  int32_t n_logit_bias;
+  const int32_t* bias_tok;
+  const float* bias_val;
+} mx_sampling_ext;
+void mx_sampling_ext_default(mx_sampling_ext* s);
+/* As mx_submit (n_logprobs == -1) or mx_submit_lp (n_logprobs 0..64, prompt_logprobs): everything is validated
+ * before the request is queued, and the bias table is copied. */
+int mx_submit_ext(mx_engine* e, const int32_t* ids, int n, const mx_sampling_ext* s, int max_tokens, int n_logprobs,
+                  int prompt_logprobs, uint64_t* req);
+/* As mx_submit_batch with one mx_sampling_ext per request: all validated first, then queued under one lock. */
+int mx_submit_ext_batch(mx_engine* e, int n_req, const int32_t* const* ids, const int32_t* lens,
+                        const mx_sampling_ext* s, const int32_t* max_tokens, uint64_t* reqs);
+/* The chain on caller-supplied rows, no engine: logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64,
+ * V <= 262144; row i samples draw n_drawn[i] of stream seeds[i] with penalty window win[i][0..n_win[i]) (<= 64) and
+ * Mirostat state mu_in[i].  device >= 0: the production launch sequence (bias -> penalties -> top-k -> sample
+ * kernel, Mirostat kernels; top_k 1..64 and repeat_last_n 0..64 as for any device-sampled row); device == -1: the
+ * host sampler, no GPU touched.  tok_out / mu_out [n] start as 0xFF bytes; logits_out (optional, [n][ldl]): the
+ * rows as the chain left them (bias and penalties applied), columns >= V bit-identical.  Anything invalid:
+ * MX_ERR_ARG, nothing launched. */
+int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl, const mx_sampling_ext* samp,
+                    const uint64_t* seeds, const int32_t* n_drawn, const int32_t* win, const int32_t* n_win,
+                    const float* mu_in, int32_t* tok_out, float* mu_out, float* logits_out);
 /* Prompt-lookup speculative decoding (llama-cpp-python's draft_model=LlamaPromptLookupDecoding(max_ngram_size,
  * num_pred_tokens)), on the device: the draft is the tokens that followed the earliest earlier occurrence of the
  * sequence's last n-gram, verified in one forward of 1 + num_pred_tokens rows of the request's slot.  The tokens

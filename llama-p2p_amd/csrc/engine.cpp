@@ -226,6 +226,11 @@ struct Request {
   bool embd = false, embd_l2 = false;
   int embd_pool = 0, embd_rows = 0;
   std::vector<float> embd_out;
+  // the rest of the sampler chain (mx_submit_ext): has_ext when any setting is off its default;
+  // ext.miro is 2 only for a sampling request (temperature > 0); mu: the Mirostat state, 2 tau at submission
+  bool has_ext = false;
+  SampExt ext{};
+  float mu = 0.f;
   // one entry [tok_lp | kr top log-probs | kr top ids as int bits] of a round that ran with kr >= lp_k
   void lp_append(const float* entry, int kr) {
     lp_tok.push_back(entry[0]);
@@ -350,7 +355,8 @@ struct mx_engine {
 
   // graphs for the scheduler's decode steps, by (M, top-k of the device sampling chain or 0 = argmax)
   // ... and the top-k of the round's log-probabilities (-1: none; such rounds enqueue what they always did)
-  std::map<std::tuple<int, int, int>, hipGraphExec_t> sched_graphs;
+  // ... and whether the round runs the extended chain (0: none; 1: bias / tail-free / typical; 2: Mirostat too)
+  std::map<std::tuple<int, int, int, int>, hipGraphExec_t> sched_graphs;
   // pipeline stage hand-off dtype: x_in / x_out are bf16 [M][n_embd] instead of f32 (mx_opts.handoff_bf16)
   bool handoff_bf16 = false;
   // token pick at the end of a forward with `argmax` set: greedy argmax, or (pick_samp) the device
@@ -364,23 +370,70 @@ struct mx_engine {
   int pick_lp = -1;
   float *lp_part = nullptr, *lp_ms = nullptr, *lp_top = nullptr, *lp_hist = nullptr, *lp_side_val = nullptr;
   int *lp_idx = nullptr, *lp_side_tok = nullptr, *lp_tgt = nullptr;
+  // the rest of the chain: pick_ext = d_sext when some row of the run has a SampExt setting
+  // (null: the launches are those of the plain chain), pick_miro when one of them is a Mirostat row.
+  // d_mu [MAX_ROWS]: Mirostat state of the rows, d_mu_hist [MAX_ROWS][SCHED_KMAX] its value after each step
+  const SampExt* pick_ext = nullptr;
+  bool pick_miro = false;
+  SampExt* d_sext = nullptr;
+  float *d_bias_raw = nullptr, *d_mu = nullptr, *d_mu_hist = nullptr, *miro_wf = nullptr;
+  double* miro_wd = nullptr;
+  int* miro_wi = nullptr;
+  std::vector<SampExt> h_sext;  // host staging of upload_ext
+  std::vector<float> h_mu;
+  // SampExt rows and mu of a run over rows[0..n) to the device and pick_ext / pick_miro set; returns the level
+  // the graph key carries (0: no row has a setting, nothing copied; 1: some; 2: a Mirostat row among them)
+  int upload_ext(Request* const* rows, int n, hipStream_t s) {
+    pick_ext = nullptr, pick_miro = false;
+    bool any = false;
+    for (int i = 0; i < n; i++) any |= rows[i]->has_ext;
+    if (!any) return 0;
+    // the buffers of the extended chain come with its first request, so an engine that never sees one has the
+    // device memory layout it always had
+    if (!d_sext &&
+        (alloc((void**)&d_sext, (size_t)MAX_ROWS * sizeof(SampExt)) ||
+         alloc((void**)&d_bias_raw, (size_t)MAX_ROWS * SAMP_BIAS_MAX * 4) || alloc((void**)&d_mu, (size_t)MAX_ROWS * 4) ||
+         alloc((void**)&d_mu_hist, (size_t)MAX_ROWS * SCHED_KMAX * 4) ||
+         alloc((void**)&miro_wf, miro_ws_floats(MAX_ROWS) * 4) || alloc((void**)&miro_wd, miro_ws_doubles(MAX_ROWS) * 8) ||
+         alloc((void**)&miro_wi, miro_ws_ints(MAX_ROWS) * 4))) {
+      d_sext = nullptr;
+      return -1;
+    }
+    h_sext.assign(n, SampExt{});
+    h_mu.assign(n, 0.f);
+    for (int i = 0; i < n; i++) {
+      if (rows[i]->has_ext) h_sext[i] = rows[i]->ext;
+      else h_sext[i].typical_p = h_sext[i].tfs_z = 1.0f;
+      h_mu[i] = rows[i]->mu;
+      pick_miro |= h_sext[i].miro == 2;
+    }
+    if (hipMemcpyAsync(d_sext, h_sext.data(), n * sizeof(SampExt), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_mu, h_mu.data(), n * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+      return -1;
+    pick_ext = d_sext;
+    return pick_miro ? 2 : 1;
+  }
   void pick(int n_out, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count, int max_hist,
             hipStream_t s) {
     const bool lp = pick_lp >= 0;
+    SampExtArgs xa;
+    xa.ext = pick_samp ? pick_ext : nullptr;
+    xa.bias_raw = d_bias_raw, xa.mu = d_mu, xa.mu_hist = d_mu_hist, xa.mu_stride = SCHED_KMAX;
+    xa.ws_f = miro_wf, xa.ws_d = miro_wd, xa.ws_i = miro_wi, xa.any_miro = pick_miro;
     if (lp)
       launch_logprob_stats(logits, n_vocab, n_out, n_vocab, pick_lp, tk_ws_val, tk_ws_idx, lp_part, lp_ms, lp_top,
                            lp_idx, s);
     if (pick_samp)
       launch_sample_chain(logits, n_vocab, n_out, n_vocab, pick_samp, pick_k, tk_ws_val, tk_ws_idx, tk_val, tk_idx,
                           d_tok, ids_next, pos_next, hist, hist_stride, hist_count, max_hist, s,
-                          lp ? lp_side_tok : nullptr, lp ? lp_side_val : nullptr);
+                          lp ? lp_side_tok : nullptr, lp ? lp_side_val : nullptr, xa.ext ? &xa : nullptr);
     else
       launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, ids_next, pos_next, hist, hist_stride,
                     hist_count, max_hist, s);
     if (lp)
       launch_logprob_gather(logits, n_vocab, n_out, n_vocab, pick_lp, d_tok, hist ? hist_count : nullptr, SCHED_KMAX,
                             pick_samp ? lp_side_tok : nullptr, lp_side_val, lp_ms, lp_top, lp_idx, lp_hist,
-                            (size_t)SCHED_KMAX * (1 + 2 * pick_lp), s);
+                            (size_t)SCHED_KMAX * (1 + 2 * pick_lp), s, xa.ext, d_bias_raw);
   }
   int copy_out(void* x_out, int M, hipStream_t s) {  // the residual stream to the next stage
     if (handoff_bf16) launch_f32_to_bf16((uint16_t*)x_out, x, (size_t)M * n_embd, s);
@@ -1801,8 +1854,73 @@ static bool has_penalties(const mx_sampling& sp) {
   return sp.repeat_penalty != 1.0f || sp.frequency_penalty != 0.0f || sp.presence_penalty != 0.0f;
 }
 
+// the request's pick is more than an argmax of the raw row: it samples, or something rewrites its logits first
+static bool needs_chain(const Request* r) {
+  return r->samp.temperature > 0.f || has_penalties(r->samp) || (r->has_ext && r->ext.n_bias > 0);
+}
+// the device chain can serve the request: top_k 1..64 (a Mirostat row takes no top-k) and a window <= 64
+static bool dev_sampleable(const Request* r) {
+  if (r->has_ext && r->ext.miro == 2) {
+    mx_sampling sp = r->samp;
+    sp.top_k = 1;
+    return mx_engine::device_sampleable(sp);
+  }
+  return mx_engine::device_sampleable(r->samp);
+}
+// top-k the request asks of the device chain (what the round's K is the maximum of)
+static int chain_topk(const Request* r, int n_vocab) {
+  return r->has_ext && r->ext.miro == 2 ? 1 : std::max(1, std::min(r->samp.top_k, n_vocab));
+}
+
+// bias and penalties of the host sampler on a copy of the row (the order and f32 arithmetic of the kernels)
+static void rewrite_host(const mx_sampling& sp, const SampExt* ext, const int32_t* win, int n_win, int V, float* x) {
+  if (ext)
+    for (int j = 0; j < ext->n_bias; j++) x[ext->bias_tok[j]] += ext->bias_val[j];
+  if (has_penalties(sp) && sp.repeat_last_n != 0) {
+    const int n = sp.repeat_last_n < 0 ? n_win : std::min<int>(sp.repeat_last_n, n_win);
+    std::vector<int> count(V, 0);
+    for (int i = n_win - n; i < n_win; i++) count[win[i]]++;
+    for (int i = 0; i < V; i++) {
+      const int k = count[i];
+      if (!k) continue;
+      if (sp.repeat_penalty != 1.0f) x[i] = x[i] <= 0 ? x[i] * sp.repeat_penalty : x[i] / sp.repeat_penalty;
+      x[i] -= fmaf((float)k, sp.frequency_penalty, sp.presence_penalty);  // fused, as penalty_kernel
+    }
+  }
+}
+
+// the whole chain on the host for one row x (rewritten in place): what sample_host and mx_sample_probe run
+static int32_t chain_host(const mx_sampling& sp, const SampExt* ext, const int32_t* win, int n_win, int V, float* x,
+                          double u01, float* mu) {
+  rewrite_host(sp, ext, win, n_win, V, x);
+  auto before = [](const std::pair<float, int>& a, const std::pair<float, int>& b) {
+    return a.first > b.first || (a.first == b.first && a.second < b.second);
+  };
+  if (sp.temperature > 0.f && ext && ext->miro == 2)
+    return miro_pick_host(x, V, sp.temperature, ext->tau, ext->eta, u01, mu);
+  std::vector<std::pair<float, int>> c;
+  c.reserve(V);
+  for (int i = 0; i < V; i++) c.push_back({x[i], i});
+  if (sp.temperature <= 0.f) return std::min_element(c.begin(), c.end(), before)->second;
+  const int k = sp.top_k > 0 ? std::min<int>(sp.top_k, V) : V;
+  std::partial_sort(c.begin(), c.begin() + k, c.end(), before);
+  std::vector<float> v(k), cv(k);
+  std::vector<int> id(k), ci(k), ord(k);
+  for (int i = 0; i < k; i++) v[i] = c[i].first, id[i] = c[i].second;
+  std::vector<double> p(k), w(k);
+  return samp_pick(v.data(), id.data(), k, sp.temperature, sp.top_p, sp.min_p, u01, p.data(), w.data(),
+                   ext ? ext->tfs_z : 1.0f, ext ? ext->typical_p : 1.0f, cv.data(), ci.data(), ord.data());
+}
+
 int32_t mx_engine::sample_host(Request* r, const float* lg) {
   const mx_sampling& sp = r->samp;
+  if (r->has_ext) {
+    std::vector<float> x(lg, lg + n_vocab);
+    std::vector<int32_t> hist(r->prompt);
+    hist.insert(hist.end(), r->out.begin(), r->out.end());
+    return chain_host(sp, &r->ext, hist.data(), (int)hist.size(), n_vocab, x.data(), samp_u01(r->seed, r->out.size()),
+                      &r->mu);
+  }
   std::vector<std::pair<float, int>> c;
   c.reserve(n_vocab);
   for (int i = 0; i < n_vocab; i++) c.push_back({lg[i], i});
@@ -1932,9 +2050,9 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
   std::vector<int32_t> tok(reqs.size());
   bool any_sampling = false, dev_pick = use_dev_topk;
   for (Request* r : reqs)
-    if (r->samp.temperature > 0.f || has_penalties(r->samp)) {
+    if (needs_chain(r)) {
       any_sampling = true;
-      dev_pick &= device_sampleable(r->samp);
+      dev_pick &= dev_sampleable(r);
     }
   // every sampling request fits the device chain: first tokens are drawn on the device (the same
   // samp_pick and counter-based draw 0 as the host sampler), no logits rows cross PCIe
@@ -1975,17 +2093,24 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       sr.resize(n_out);
       for (int k = 0; k < n_out; k++) {
         samp_row(reqs[q0 + k], &sr[k]);
-        const mx_sampling& sp = reqs[q0 + k]->samp;
-        if (sp.temperature > 0.f || has_penalties(sp)) ktop = std::max(ktop, std::min(sp.top_k, n_vocab));
+        if (needs_chain(reqs[q0 + k])) ktop = std::max(ktop, chain_topk(reqs[q0 + k], n_vocab));
       }
     }
+    std::vector<float> mu_new;
     if (n_out && ktop > 0) {
       HIPC(hipMemcpyAsync(d_samp, sr.data(), n_out * sizeof(SampRow), hipMemcpyHostToDevice, st));
+      const int xl = upload_ext(reqs.data() + q0, n_out, st);
+      if (xl < 0) return fail(MX_ERR_HIP, "sampler settings copy");
       pick_samp = d_samp;
       pick_k = ktop;
       pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
       pick_samp = nullptr;
       pick_k = 0;
+      pick_ext = nullptr, pick_miro = false;
+      if (xl == 2) {
+        mu_new.resize(n_out);
+        HIPC(hipMemcpyAsync(mu_new.data(), d_mu, n_out * 4, hipMemcpyDeviceToHost, st));
+      }
       HIPC(hipMemcpyAsync(tok.data() + q0, d_tok, n_out * 4, hipMemcpyDeviceToHost, st));
     } else if (n_out) {
       if (lpk >= 0)
@@ -2012,8 +2137,9 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
     for (int k = 0; k < n_out; k++) {
       Request* r = reqs[q0 + k];
       int32_t t = tok[q0 + k];
-      const bool host_pick = !dev_pick && (r->samp.temperature > 0.f || has_penalties(r->samp));
+      const bool host_pick = !dev_pick && needs_chain(r);
       if (host_pick) t = sample_host(r, lg.data() + (size_t)k * n_vocab);
+      if (!mu_new.empty() && r->has_ext && r->ext.miro == 2) r->mu = mu_new[k];
       r->out.push_back(t);
       r->next_tok = t;
       if (r->lp_k >= 0) {
@@ -2201,6 +2327,7 @@ int mx_engine::prefill_embed(std::vector<Request*>& reqs) {
 // log-probabilities, on a whole bf16 model -- the path whose rows are bitwise independent of the row count.
 bool mx_engine::spec_eligible(const Request* r) const {
   return r->spec_d > 0 && spec_ctx && r->samp.temperature <= 0.f && !has_penalties(r->samp) && r->lp_k < 0 &&
+         !r->has_ext &&
          !embd_q8 && !out_q8 && !embd_kq_type && !out_kq_head;
 }
 
@@ -2343,10 +2470,9 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     ids[i] = rows[i]->next_tok;
     pos[i] = rows[i]->pos;
     slots[i] = rows[i]->slot;
-    const mx_sampling& sp = rows[i]->samp;
-    if (sp.temperature > 0.f || has_penalties(sp)) {
+    if (needs_chain(rows[i])) {
       all_greedy = false;
-      if (use_dev_topk && device_sampleable(sp)) ktop = std::max(ktop, std::min(sp.top_k, n_vocab));
+      if (use_dev_topk && dev_sampleable(rows[i])) ktop = std::max(ktop, chain_topk(rows[i], n_vocab));
       else all_dev = false;
     }
     room = std::min(room, n_ctx - rows[i]->pos);
@@ -2373,14 +2499,20 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     for (int i = 0; i < M; i++) samp_row(rows[i], &sr[i]);
     HIPC(hipMemcpyAsync(d_samp, sr.data(), M * sizeof(SampRow), hipMemcpyHostToDevice, s));
   }
+  struct Reset {
+    mx_engine* e;
+    ~Reset() {
+      e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1;
+      e->pick_ext = nullptr; e->pick_miro = false;
+    }
+  } reset_flags{this};
+  // rows with the extended settings: their SampExt and mu beside the SampRows; the level joins the graph key
+  const int xl = dev_chain ? upload_ext(rows.data(), M, s) : 0;
+  if (xl < 0) return fail(MX_ERR_HIP, "sampler settings copy");
   rows_distinct = true;  // one row per active request, each its own slot
   pick_samp = dev_chain ? d_samp : nullptr;
   pick_k = dev_chain ? ktop : 0;
   pick_lp = lpk;
-  struct Reset {
-    mx_engine* e;
-    ~Reset() { e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1; }
-  } reset_flags{this};
   auto step = [&]() -> int {
     return enqueue_forward(M, d_ids, d_pos, d_slot, nullptr, nullptr, true, nullptr, M, true, d_ids, d_pos,
                            sched_hist, SCHED_KMAX, sched_hist_count, SCHED_KMAX, s);
@@ -2388,7 +2520,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;  // per-round timing on stderr
   const auto t0 = std::chrono::steady_clock::now();
   bool captured = false;
-  const std::tuple<int, int, int> gkey(M, pick_k, pick_lp);
+  const std::tuple<int, int, int, int> gkey(M, pick_k, pick_lp, xl);
   auto it = sched_graphs.find(gkey);
   if (use_graphs && it == sched_graphs.end()) {
     captured = true;
@@ -2417,6 +2549,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   bool dev_topk = !all_greedy && !dev_chain && use_dev_topk;
   for (int i = 0; i < M && dev_topk; i++) {
     const mx_sampling& sp = rows[i]->samp;
+    if (rows[i]->has_ext) dev_topk = false;  // bias reorders the row, Mirostat reads all of it: whole rows
     if (sp.temperature <= 0.f && !has_penalties(sp)) continue;
     if (has_penalties(sp) || sp.top_k < 1 || sp.top_k > TOPK_MAX) dev_topk = false;
     else TK = std::max(TK, std::min(sp.top_k, n_vocab));
@@ -2443,11 +2576,18 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
       HIPC(hipMemcpyAsync(lpms.data(), lp_ms, lpms.size() * 4, hipMemcpyDeviceToHost, s));
     }
   }
+  // Mirostat rows: mu after each step, so a row keeps the mu of the last step whose token it keeps
+  std::vector<float> muh;
+  if (xl == 2) {
+    muh.resize((size_t)M * SCHED_KMAX);
+    HIPC(hipMemcpyAsync(muh.data(), d_mu_hist, muh.size() * 4, hipMemcpyDeviceToHost, s));
+  }
   HIPC(hipStreamSynchronize(s));
   if (trace) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr, "sched: decode M=%d K=%d %s%s%s%.3f ms\n", M, K, dev_chain ? "(device sampling) " : "",
-            lpk >= 0 ? "(logprobs) " : "", captured ? "(graph captured) " : "", ms);
+    fprintf(stderr, "sched: decode M=%d K=%d %s%s%s%s%.3f ms\n", M, K, dev_chain ? "(device sampling) " : "",
+            xl == 2 ? "(mirostat) " : xl == 1 ? "(extended chain) " : "", lpk >= 0 ? "(logprobs) " : "",
+            captured ? "(graph captured) " : "", ms);
   }
   std::lock_guard<std::mutex> lk(mu);
   for (int i = 0; i < M; i++) {
@@ -2456,7 +2596,8 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
       r->pos++;
       int32_t t = hist[(size_t)i * SCHED_KMAX + k];
       float raw = 0.f;  // host pick: the chosen token's raw logit (candidate list or copied row)
-      const bool host_pick = !dev_chain && (r->samp.temperature > 0.f || has_penalties(r->samp));
+      const bool host_pick = !dev_chain && needs_chain(r);
+      if (!muh.empty() && r->has_ext && r->ext.miro == 2) r->mu = muh[(size_t)i * SCHED_KMAX + k];
       if (host_pick) {
         if (!tkv.empty()) {
           std::vector<std::pair<float, int>> c(std::min(r->samp.top_k, n_vocab));
@@ -2992,6 +3133,203 @@ int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl
   std::vector<float> ent((size_t)n * est);
   HIPC(hipMemcpy(ent.data(), d_out, ent.size() * 4, hipMemcpyDeviceToHost));
   split_entries(ent, n, k, tgt_lp, top_lp, top_idx);
+  return 0;
+}
+
+void mx_sampling_ext_default(mx_sampling_ext* s) {
+  mx_sampling_default(&s->base);
+  s->typical_p = 1.0f;
+  s->tfs_z = 1.0f;
+  s->mirostat_mode = 0;
+  s->mirostat_tau = 5.0f;
+  s->mirostat_eta = 0.1f;
+  s->n_logit_bias = 0;
+  s->bias_tok = nullptr;
+  s->bias_val = nullptr;
+}
+
+// validates the extended settings against a vocabulary of V and restates them as a SampExt (the bias table
+// copied); *has: some setting is off its default, so the request / row takes the extended chain
+static int check_sampling_ext(const mx_sampling_ext* s, int V, SampExt* o, bool* has) {
+  if (s->mirostat_mode == 1)
+    return fail(MX_ERR_ARG, "mirostat_mode 1 is not supported (Mirostat v1 sorts the whole vocabulary); use 2");
+  if (s->mirostat_mode != 0 && s->mirostat_mode != 2) return fail(MX_ERR_ARG, "mirostat_mode must be 0 or 2");
+  if (std::isnan(s->typical_p) || std::isnan(s->tfs_z) || std::isnan(s->mirostat_tau) || std::isnan(s->mirostat_eta))
+    return fail(MX_ERR_ARG, "NaN sampler setting");
+  if (s->n_logit_bias < 0 || s->n_logit_bias > SAMP_BIAS_MAX)
+    return fail(MX_ERR_ARG, "logit_bias: at most " + std::to_string(SAMP_BIAS_MAX) + " entries");
+  if (s->n_logit_bias > 0 && (!s->bias_tok || !s->bias_val)) return fail(MX_ERR_ARG, "logit_bias: null table");
+  memset(o, 0, sizeof(*o));
+  std::vector<int32_t> seen(s->bias_tok, s->bias_tok + s->n_logit_bias);
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(MX_ERR_ARG, "logit_bias: duplicate token");
+  for (int j = 0; j < s->n_logit_bias; j++) {
+    const float b = s->bias_val[j];
+    if (s->bias_tok[j] < 0 || s->bias_tok[j] >= V) return fail(MX_ERR_ARG, "logit_bias: token id outside the vocabulary");
+    if (std::isnan(b) || b == INFINITY) return fail(MX_ERR_ARG, "logit_bias: NaN or +inf bias");
+    o->bias_tok[j] = s->bias_tok[j];
+    o->bias_val[j] = b;
+  }
+  o->n_bias = s->n_logit_bias;
+  o->typical_p = s->typical_p;
+  o->tfs_z = s->tfs_z;
+  o->miro = s->mirostat_mode == 2 && s->base.temperature > 0.f ? 2 : 0;
+  o->tau = s->mirostat_tau;
+  o->eta = s->mirostat_eta;
+  *has = o->typical_p < 1.0f || o->tfs_z < 1.0f || o->miro == 2 || o->n_bias > 0;
+  return 0;
+}
+
+int mx_submit_ext(mx_engine* e, const int32_t* ids, int n, const mx_sampling_ext* s, int max_tokens, int n_logprobs,
+                  int prompt_logprobs, uint64_t* req) {
+  if (!e || !ids || n < 1 || !req || !s) return fail(MX_ERR_ARG, "bad arguments");
+  if (n_logprobs < -1 || n_logprobs > TOPK_MAX) return fail(MX_ERR_ARG, "mx_submit_ext: n_logprobs must be -1..64");
+  if (n_logprobs < 0 && prompt_logprobs) return fail(MX_ERR_ARG, "mx_submit_ext: prompt_logprobs needs n_logprobs >= 0");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit needs a full-model engine");
+  std::unique_ptr<Request> r;
+  if (int rc = make_request(e, ids, n, &s->base, max_tokens, &r)) return rc;
+  if (int rc = check_sampling_ext(s, e->n_vocab, &r->ext, &r->has_ext)) return rc;
+  r->mu = 2.0f * s->mirostat_tau;
+  if (n_logprobs >= 0) {
+    r->lp_k = std::min(n_logprobs, e->n_vocab);
+    r->lp_prompt = prompt_logprobs != 0;
+  }
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->stop) return fail(MX_ERR_STATE, "engine shutting down");
+    Request* rp = r.get();
+    rp->id = e->next_id++;
+    *req = rp->id;
+    e->pending.push_back(rp);
+    e->requests[rp->id] = std::move(r);
+    if (!e->worker_started) {
+      e->worker_started = true;
+      e->worker = std::thread([e] { e->scheduler_loop(); });
+    }
+  }
+  e->cv.notify_all();
+  return 0;
+}
+
+int mx_submit_ext_batch(mx_engine* e, int n_req, const int32_t* const* ids, const int32_t* lens,
+                        const mx_sampling_ext* s, const int32_t* max_tokens, uint64_t* reqs) {
+  if (!e || n_req < 1 || !ids || !lens || !s || !max_tokens || !reqs) return fail(MX_ERR_ARG, "bad arguments");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit needs a full-model engine");
+  std::vector<std::unique_ptr<Request>> rs(n_req);
+  for (int i = 0; i < n_req; i++) {
+    if (int rc = make_request(e, ids[i], lens[i], &s[i].base, max_tokens[i], &rs[i])) return rc;
+    if (int rc = check_sampling_ext(&s[i], e->n_vocab, &rs[i]->ext, &rs[i]->has_ext)) return rc;
+    rs[i]->mu = 2.0f * s[i].mirostat_tau;
+  }
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->stop) return fail(MX_ERR_STATE, "engine shutting down");
+    for (int i = 0; i < n_req; i++) {
+      Request* r = rs[i].get();
+      r->id = e->next_id++;
+      reqs[i] = r->id;
+      e->pending.push_back(r);
+      e->requests[r->id] = std::move(rs[i]);
+    }
+    if (!e->worker_started) {
+      e->worker_started = true;
+      e->worker = std::thread([e] { e->scheduler_loop(); });
+    }
+  }
+  e->cv.notify_all();
+  return 0;
+}
+
+int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl, const mx_sampling_ext* samp,
+                    const uint64_t* seeds, const int32_t* n_drawn, const int32_t* win, const int32_t* n_win,
+                    const float* mu_in, int32_t* tok_out, float* mu_out, float* logits_out) {
+  if (tok_out && n >= 1 && n <= 4096) memset(tok_out, 0xFF, (size_t)n * 4);
+  if (mu_out && n >= 1 && n <= 4096) memset(mu_out, 0xFF, (size_t)n * 4);
+  if (!logits_host || !samp || !seeds || !n_drawn || !win || !n_win || !mu_in || !tok_out || !mu_out || n < 1 ||
+      n > MAX_ROWS || V < 1 || V > 262144 || ldl < V || device < -1)
+    return fail(MX_ERR_ARG, "mx_sample_probe: 1 <= n <= 64 rows, 1 <= V <= 262144, V <= ldl, device >= -1");
+  std::vector<SampExt> sx(n);
+  std::vector<SampRow> sr(n, SampRow{});
+  int ktop = 1;
+  bool any_miro = false;
+  for (int i = 0; i < n; i++) {
+    bool has = false;
+    if (int rc = check_sampling_ext(&samp[i], V, &sx[i], &has)) return rc;
+    const mx_sampling& sp = samp[i].base;
+    if (n_drawn[i] < 0 || n_win[i] < 0 || n_win[i] > SAMP_WIN) return fail(MX_ERR_ARG, "mx_sample_probe: n_drawn >= 0, n_win 0..64");
+    for (int j = 0; j < n_win[i]; j++)
+      if (win[i * SAMP_WIN + j] < 0 || win[i * SAMP_WIN + j] >= V) return fail(MX_ERR_ARG, "mx_sample_probe: window token outside the vocabulary");
+    if (std::isnan(sp.temperature) || std::isnan(mu_in[i])) return fail(MX_ERR_ARG, "mx_sample_probe: NaN setting");
+    if (device >= 0) {
+      mx_sampling d = sp;
+      if (sx[i].miro == 2 || sp.temperature <= 0.f) d.top_k = 1;
+      if (!mx_engine::device_sampleable(d))
+        return fail(MX_ERR_ARG, "mx_sample_probe: settings outside the device chain (top_k 1..64, repeat_last_n 0..64)");
+      SampRow& o = sr[i];
+      o.temp = sp.temperature, o.top_p = sp.top_p, o.min_p = sp.min_p;
+      o.repeat = sp.repeat_penalty, o.freq = sp.frequency_penalty, o.presence = sp.presence_penalty;
+      o.top_k = std::max(1, std::min(d.top_k, TOPK_MAX));
+      o.last_n = has_penalties(sp) ? std::min(sp.repeat_last_n, SAMP_WIN) : 0;
+      o.seed = seeds[i];
+      o.draw0 = n_drawn[i];
+      o.n_win = std::min(o.last_n, n_win[i]);
+      for (int j = 0; j < o.n_win; j++) o.win[j] = win[i * SAMP_WIN + n_win[i] - o.n_win + j];
+      ktop = std::max(ktop, std::min(o.top_k, V));
+      any_miro |= sx[i].miro == 2;
+    }
+  }
+  if (logits_out) memcpy(logits_out, logits_host, (size_t)n * ldl * 4);
+  if (device < 0) {  // the host sampler: no GPU touched
+    std::vector<float> x(V);
+    for (int i = 0; i < n; i++) {
+      memcpy(x.data(), logits_host + (size_t)i * ldl, (size_t)V * 4);
+      float mu = mu_in[i];
+      tok_out[i] = chain_host(samp[i].base, &sx[i], win + i * SAMP_WIN, n_win[i], V, x.data(),
+                              samp_u01(seeds[i], (uint64_t)n_drawn[i]), &mu);
+      mu_out[i] = mu;
+      if (logits_out) memcpy(logits_out + (size_t)i * ldl, x.data(), (size_t)V * 4);
+    }
+    return 0;
+  }
+  HIPC(hipSetDevice(device));
+  std::vector<void*> owned;
+  auto dalloc = [&](void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) != hipSuccess) return false;
+    owned.push_back(*p);
+    return true;
+  };
+  struct Free {
+    std::vector<void*>& v;
+    ~Free() { for (void* p : v) hipFree(p); }
+  } free_all{owned};
+  float *d_lg, *d_wsv, *d_tkv, *d_mu, *d_wf, *d_braw;
+  int *d_wsi, *d_tki, *d_tok, *d_wi;
+  double* d_wd;
+  SampRow* d_sr;
+  SampExt* d_sx;
+  if (!dalloc((void**)&d_lg, (size_t)n * ldl * 4) || !dalloc((void**)&d_wsv, (size_t)n * 64 * TOPK_MAX * 4) ||
+      !dalloc((void**)&d_wsi, (size_t)n * 64 * TOPK_MAX * 4) || !dalloc((void**)&d_tkv, (size_t)n * TOPK_MAX * 4) ||
+      !dalloc((void**)&d_tki, (size_t)n * TOPK_MAX * 4) || !dalloc((void**)&d_tok, (size_t)n * 4) ||
+      !dalloc((void**)&d_mu, (size_t)n * 4) || !dalloc((void**)&d_wf, miro_ws_floats(n) * 4) ||
+      !dalloc((void**)&d_wd, miro_ws_doubles(n) * 8) || !dalloc((void**)&d_wi, miro_ws_ints(n) * 4) ||
+      !dalloc((void**)&d_braw, (size_t)n * SAMP_BIAS_MAX * 4) || !dalloc((void**)&d_sr, (size_t)n * sizeof(SampRow)) ||
+      !dalloc((void**)&d_sx, (size_t)n * sizeof(SampExt)))
+    return fail(MX_ERR_HIP, "mx_sample_probe: device allocation");
+  HIPC(hipMemcpy(d_lg, logits_host, (size_t)n * ldl * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_sr, sr.data(), (size_t)n * sizeof(SampRow), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_sx, sx.data(), (size_t)n * sizeof(SampExt), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_mu, mu_in, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_tok, 0xFF, (size_t)n * 4));
+  SampExtArgs xa;
+  xa.ext = d_sx, xa.bias_raw = d_braw, xa.mu = d_mu, xa.ws_f = d_wf, xa.ws_d = d_wd, xa.ws_i = d_wi;
+  xa.any_miro = any_miro;
+  if (launch_sample_chain(d_lg, ldl, n, V, d_sr, ktop, d_wsv, d_wsi, d_tkv, d_tki, d_tok, nullptr, nullptr, nullptr, 0,
+                          nullptr, 0, nullptr, nullptr, nullptr, &xa))
+    return fail(MX_ERR_ARG, "mx_sample_probe: launch shape (V too large for the top-k slices)");
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(tok_out, d_tok, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(mu_out, d_mu, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (logits_out) HIPC(hipMemcpy(logits_out, d_lg, (size_t)n * ldl * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -8,6 +8,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
+
 namespace mx {
 
 // Weight matrices live in HBM as bf16 "MFMA tiles": tile (nt, kt) holds rows
@@ -295,11 +298,81 @@ __host__ __device__ inline double samp_u01(uint64_t seed, uint64_t draw) {
   z ^= z >> 31;
   return (double)(z >> 11) * (1.0 / 9007199254740992.0);
 }
-// top_p / min_p / temperature / draw over k candidates sorted by value (descending, ties lower id
-// first); p and w are scratch of k doubles.  The host sampler and sample_kernel both call this.
+// tail-free sampling (llama.cpp's tail_free sampler, min_keep 1) over k > 2 candidates sorted by value: the
+// |second differences| of the softmax, normalised (1 / (k - 2) each when their sum is <= 1e-6), summed in
+// order; the candidates before the first index i >= 1 whose running sum exceeds z stay.  Returns the count.
+__host__ __device__ inline int samp_tail_free(const float* vals, int k, float z, double* p, double* w) {
+#pragma clang fp contract(off)  // no fused multiply-adds: the host and the device round alike
+  const double mx = vals[0];
+  double sum = 0;
+  for (int i = 0; i < k; i++) sum += (p[i] = exp((double)vals[i] - mx));
+  for (int i = 0; i < k; i++) p[i] /= sum;
+  double s2 = 0;
+  for (int i = 0; i < k - 2; i++) s2 += (w[i] = fabs((p[i] - p[i + 1]) - (p[i + 1] - p[i + 2])));
+  for (int i = 0; i < k - 2; i++) w[i] = s2 > 1e-6 ? w[i] / s2 : 1.0 / (k - 2);
+  double cum = 0;
+  for (int i = 0; i < k - 2; i++) {
+    cum += w[i];
+    if (cum > z && i >= 1) return i;
+  }
+  return k;
+}
+// locally typical sampling (llama.cpp's typical sampler, min_keep 1): q = softmax, H its entropy (0 log 0 = 0),
+// the candidates in order of |-log q_i - H| ascending (ties by rank: a stable sort) stay through the first one
+// at which their running mass exceeds tp.  The kept ones go to cv / ci in value order again; returns the count.
+// ord: scratch of k ints.  Up to TOPK_MAX candidates the sort is the insertion sort the device runs too.
+__host__ __device__ inline int samp_typical(const float* vals, const int* ids, int k, float tp, double* p, double* w,
+                                            float* cv, int* ci, int* ord) {
+#pragma clang fp contract(off)
+  const double mx = vals[0];
+  double sum = 0;
+  for (int i = 0; i < k; i++) sum += (p[i] = exp((double)vals[i] - mx));
+  const double ls = log(sum);
+  double H = 0;
+  for (int i = 0; i < k; i++) {
+    p[i] /= sum;
+    if (p[i] > 0) H -= p[i] * (((double)vals[i] - mx) - ls);
+  }
+  for (int i = 0; i < k; i++) w[i] = fabs(-(((double)vals[i] - mx) - ls) - H), ord[i] = i;
+#ifndef __HIP_DEVICE_COMPILE__
+  if (k > 64) std::stable_sort(ord, ord + k, [w](int a, int b) { return w[a] < w[b]; });
+  else
+#endif
+    for (int i = 1; i < k; i++) {
+      const int o = ord[i];
+      int j = i;
+      for (; j > 0 && w[ord[j - 1]] > w[o]; j--) ord[j] = ord[j - 1];
+      ord[j] = o;
+    }
+  int n = k;
+  double cum = 0;
+  for (int j = 0; j < k; j++) {
+    cum += p[ord[j]];
+    if (cum > tp) { n = j + 1; break; }
+  }
+  for (int j = 0; j < n; j++) w[ord[j]] = -1.0;  // kept (every |.| is >= 0)
+  int m = 0;
+  for (int i = 0; i < k; i++)
+    if (w[i] < 0) cv[m] = vals[i], ci[m] = ids[i], m++;
+  return m;
+}
+// [tail-free -> typical ->] top_p / min_p / temperature / draw over k candidates sorted by value (descending,
+// ties lower id first); p and w are scratch of k doubles; cv, ci, ord scratch of k entries each, needed only
+// with tfs_z < 1 or typical_p < 1.  The host sampler and the sample kernels both call this.
 __host__ __device__ inline int samp_pick(const float* vals, const int* ids, int k, float temp, float top_p,
-                                         float min_p, double u01, double* p, double* w) {
+                                         float min_p, double u01, double* p, double* w, float tfs_z = 1.0f,
+                                         float typical_p = 1.0f, float* cv = nullptr, int* ci = nullptr,
+                                         int* ord = nullptr) {
   if (temp <= 0.f || k <= 1) return ids[0];
+  if (tfs_z < 1.0f || typical_p < 1.0f) {
+    if (!(vals[0] > -INFINITY)) return ids[0];  // every candidate banned (logit_bias): no distribution to cut
+    if (tfs_z < 1.0f && k > 2) k = samp_tail_free(vals, k, tfs_z, p, w);
+    if (typical_p < 1.0f) {
+      k = samp_typical(vals, ids, k, typical_p, p, w, cv, ci, ord);
+      vals = cv, ids = ci;
+    }
+    if (k <= 1) return ids[0];
+  }
   const double mx = vals[0];
   double sum = 0;
   for (int i = 0; i < k; i++) sum += (p[i] = exp((double)vals[i] - mx));
@@ -329,12 +402,44 @@ __host__ __device__ inline int samp_pick(const float* vals, const int* ids, int 
   }
   return ids[keep - 1];
 }
+// ---- the rest of llama-cpp-python's chain: one SampExt per logits row beside its SampRow.
+// logit_bias (x[t] += bias, ahead of the penalties; -inf bans), tail-free and locally typical between top_k and
+// top_p, or Mirostat v2 over the whole vocabulary in place of top_k .. draw (miro == 2, temperature > 0 only).
+constexpr int SAMP_BIAS_MAX = 256;
+struct SampExt {
+  float typical_p, tfs_z;  // 1 = off
+  int miro;                // 2: Mirostat v2; 0: the candidate chain
+  float tau, eta;
+  int n_bias;              // distinct tokens inside the vocabulary
+  int bias_tok[SAMP_BIAS_MAX];
+  float bias_val[SAMP_BIAS_MAX];
+};
+// Mirostat v2 of one row on the host, x = the row after bias and penalties: p = softmax(x / temp) over all V, kept =
+// surprise -log2 p_i <= mu (the argmax, ties to the lowest id, when none is), the draw u01 over the kept mass walks
+// the kept tokens by ascending id, mu -= eta (-log2 p'_tok - tau) with p' renormalised over the kept set.
+int miro_pick_host(const float* x, int V, float temp, float tau, float eta, double u01, float* mu);
+// workspace of the Mirostat kernels for M rows: floats / doubles / ints
+inline size_t miro_ws_floats(int M) { return (size_t)M * 64 * 2 + (size_t)M * 2; }
+inline size_t miro_ws_doubles(int M) { return (size_t)M * 64; }
+inline size_t miro_ws_ints(int M) { return (size_t)M * 64; }
+struct SampExtArgs {
+  const SampExt* ext = nullptr;  // [M]; null: the chain as launch_sample_chain always ran it
+  float* bias_raw = nullptr;     // [M][SAMP_BIAS_MAX] raw logits of the biased tokens (log-prob gather)
+  float* mu = nullptr;           // [M] Mirostat state, updated in place ...
+  float* mu_hist = nullptr;      // ... and [M][mu_stride] its value after each step of a run (step 0 without a history)
+  int mu_stride = 1;
+  float* ws_f = nullptr;         // miro_ws_floats(M)
+  double* ws_d = nullptr;        // miro_ws_doubles(M)
+  int* ws_i = nullptr;           // miro_ws_ints(M)
+  bool any_miro = false;         // some row has miro == 2: the Mirostat launches run
+};
 // penalties (in place on the logits rows), top-k of K = max top_k of the rows, the draw, then the
 // same token bookkeeping as launch_argmax (tok_out, ids_next, pos_next, history)
 int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* samp, int K, float* ws_val, int* ws_idx,
                         float* tk_val, int* tk_idx, int* tok_out, int* ids_next, int* pos_next, int* hist,
                         int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok = nullptr,
-                        float* side_val = nullptr);  // side_*: [M][SAMP_WIN] raw logits the penalties rewrote
+                        float* side_val = nullptr,  // side_*: [M][SAMP_WIN] raw logits the penalties rewrote
+                        const SampExtArgs* x = nullptr);  // with x->ext: bias first, tail-free / typical, Mirostat rows
 // ---- per-token log-probabilities, logprob(i) = (x_i - m) - log(sum exp(x - m)) over the raw logits row
 // (DESIGN.md §9).  K = 0..min(TOPK_MAX, V) top entries per row (value descending, ties lower id first).
 // stats: one read of the rows -> part [M][64][2] slice (max, sum) partials, ms [M][2] = (m, log s) and the
@@ -345,7 +450,8 @@ int launch_logprob_stats(const float* logits, int ldl, int M, int V, int K, floa
                          float* ms, float* top_lp, int* top_idx, hipStream_t s);
 int launch_logprob_gather(const float* logits, int ldl, int M, int V, int K, const int* toks, const int* hist_count,
                           int max_steps, const int* side_tok, const float* side_val, const float* ms,
-                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s);
+                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s,
+                          const SampExt* ext = nullptr, const float* bias_raw = nullptr);  // as SampExtArgs
 // both, for given target tokens: out [M][1 + 2K]
 int launch_logprobs(const float* logits, int ldl, int M, int V, int K, const int* targets, float* ws_val, int* ws_idx,
                     float* part, float* ms, float* top_lp, int* top_idx, float* out, hipStream_t s);

@@ -1727,7 +1727,9 @@ __global__ __launch_bounds__(64) void penalty_kernel(float* logits, int ldl, con
     float v = *lp;
     if (side_tok) side_tok[c * SAMP_WIN + lane] = t, side_val[c * SAMP_WIN + lane] = v;
     if (sp.repeat != 1.0f) v = v <= 0.f ? v * sp.repeat : v / sp.repeat;
-    *lp = v - ((float)count * sp.freq + sp.presence);
+    // one fused multiply-add, as this line always compiled for the device: said explicitly so that the host
+    // sampler's rewrite_host (fmaf) and the device agree to the bit
+    *lp = v - __fmaf_rn((float)count, sp.freq, sp.presence);
   }
 }
 
@@ -1753,15 +1755,282 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* tk_val, const i
   }
 }
 
+__global__ void logprob_finish_kernel(const float* part, int nb, float* ms, float* top, int K);  // below
+
+// ---------------------------------------------------------------------------
+// The rest of llama-cpp-python's chain, for rounds in which some row has a SampExt setting.
+// These kernels are templates (LATE, always 0) for their place in the code object alone: a template kernel is
+// emitted where it is first launched, after the GEMV and attention templates above.  Emitted ahead of them, as
+// plain kernels are, they moved the decode GEMVs to other page offsets and the 32-row greedy decode of bench.py
+// ran 0.4 % slower than before with byte-identical kernels (profiles/sampler_chain.txt).
+// bias_kernel, ahead of the penalties: thread j adds entry j of the row's table to its logit (one f32 add; the
+// table's tokens are distinct, so no two threads share an address) and first saves the raw value to
+// bias_raw[c][j] for the log-prob gather.
+// ---------------------------------------------------------------------------
+template <int LATE = 0>
+__global__ __launch_bounds__(SAMP_BIAS_MAX) void bias_kernel(float* logits, int ldl, int V, const SampExt* ext,
+                                                             float* bias_raw) {
+  const int c = blockIdx.x, j = threadIdx.x;
+  const SampExt& x = ext[c];
+  if (j >= min(x.n_bias, SAMP_BIAS_MAX)) return;
+  const int t = x.bias_tok[j];
+  if (t < 0 || t >= V) return;
+  float* lp = logits + (size_t)c * ldl + t;
+  const float v = *lp;
+  if (bias_raw) bias_raw[c * SAMP_BIAS_MAX + j] = v;
+  *lp = v + x.bias_val[j];
+}
+
+// sample_kernel with the tail-free and typical cuts of samp_pick; rows of Mirostat requests are left to
+// miro_pick_kernel (token and bookkeeping)
+template <int LATE = 0>
+__global__ __launch_bounds__(64) void sample_ext_kernel(const float* tk_val, const int* tk_idx, int K,
+                                                        const SampRow* samp, const SampExt* ext, int* tok_out,
+                                                        int* ids_next, int* pos_next, int* hist, int hist_stride,
+                                                        int* hist_count, int max_hist) {
+  const int c = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  const SampRow& sp = samp[c];
+  const SampExt& x = ext[c];
+  if (x.miro == 2) return;
+  const int nh = hist ? hist_count[c] : 0;
+  double p[TOPK_MAX], w[TOPK_MAX];
+  float cv[TOPK_MAX];
+  int ci[TOPK_MAX], ord[TOPK_MAX];
+  const int k = max(1, min(sp.top_k, K));
+  const int tok = samp_pick(tk_val + (size_t)c * K, tk_idx + (size_t)c * K, k, sp.temp, sp.top_p, sp.min_p,
+                            samp_u01(sp.seed, (uint64_t)(sp.draw0 + nh)), p, w, x.tfs_z, x.typical_p, cv, ci, ord);
+  if (tok_out) tok_out[c] = tok;
+  if (ids_next) ids_next[c] = tok;
+  if (pos_next) pos_next[c] += 1;
+  if (hist) {
+    if (nh < max_hist) hist[(size_t)c * hist_stride + nh] = tok;
+    hist_count[c] = nh + 1;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Mirostat v2 over the whole vocabulary.  With y_i = x_i / temp (one f32 division, x the row after bias and
+// penalties), m = max y and s = sum exp(y_i - m): log p_i = (y_i - m) - log s, the token's surprise is
+// -log2 p_i.  Three passes in the slice structure of lse_topk_stage1 (nb <= 64 slices of <= 4096 columns):
+//   miro_stage1        per slice (m_b, s_b) in f32; logprob_finish_kernel folds them to (m, log s)
+//   miro_mass_kernel   per slice the f64 mass and the count of the tokens with surprise <= mu
+//   miro_pick_kernel   one wave per row: folds the slice masses in slice order, finds the slice holding u S,
+//                      then the token by an ordered scan of that slice (kept tokens by ascending id), and
+//                      writes the token, its bookkeeping and the new mu (in place and into the step history)
+// log p_i and the masses are f64 from the f32 inputs, and every sum has a fixed order (a thread's strided
+// terms, the wave64 butterfly, the 4 waves; slices by index; the scan by id), so the pick of a row depends
+// neither on M nor on its batch-mates.  Rows with miro != 2 are skipped by every pass.
+// ---------------------------------------------------------------------------
+template <int LATE = 0>
+__global__ __launch_bounds__(256) void miro_stage1(const float* logits, int ldl, int V, const SampRow* samp,
+                                                   const SampExt* ext, float* part) {
+  __shared__ float red[4];
+  const int c = blockIdx.y, b = blockIdx.x, nb = gridDim.x;
+  float* po = part + ((size_t)c * nb + b) * 2;
+  if (ext[c].miro != 2) {
+    if (threadIdx.x == 0) po[0] = -INFINITY, po[1] = 0.f;
+    return;
+  }
+  const float temp = samp[c].temp;
+  const int lo = (int)((long long)V * b / nb), hi = (int)((long long)V * (b + 1) / nb);
+  const float* lr = logits + (size_t)c * ldl;
+  float m = -INFINITY;
+  for (int j = lo + threadIdx.x; j < hi; j += 256) m = fmaxf(m, lr[j] / temp);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  if (m > -INFINITY)
+    for (int j = lo + threadIdx.x; j < hi; j += 256) sum += expf(lr[j] / temp - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) po[0] = m, po[1] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// log p of one entry (f64) and whether Mirostat keeps it; the two kernels below share it, so they agree on
+// every token
+__device__ __forceinline__ bool miro_kept(float x, float temp, float m, float ls, float mu, double* p) {
+  const double lp = ((double)(x / temp) - (double)m) - (double)ls;
+  const bool kept = -lp * 1.4426950408889634 <= (double)mu;  // false for a NaN
+  *p = kept ? exp(lp) : 0.0;
+  return kept;
+}
+
+template <int LATE = 0>
+__global__ __launch_bounds__(256) void miro_mass_kernel(const float* logits, int ldl, int V, const SampRow* samp,
+                                                        const SampExt* ext, const float* ms, const float* mu,
+                                                        double* mass, int* cnt) {
+  __shared__ double red[4];
+  __shared__ int redn[4];
+  const int c = blockIdx.y, b = blockIdx.x, nb = gridDim.x;
+  if (ext[c].miro != 2) return;
+  const float temp = samp[c].temp, m = ms[c * 2], ls = ms[c * 2 + 1], muc = mu[c];
+  const int lo = (int)((long long)V * b / nb), hi = (int)((long long)V * (b + 1) / nb);
+  const float* lr = logits + (size_t)c * ldl;
+  double sum = 0.0;
+  int n = 0;
+  if (m > -INFINITY)
+    for (int j = lo + threadIdx.x; j < hi; j += 256) {
+      double p;
+      n += miro_kept(lr[j], temp, m, ls, muc, &p) ? 1 : 0;
+      sum += p;
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o), n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum, redn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mass[c * 64 + b] = ((red[0] + red[1]) + red[2]) + red[3];
+    cnt[c * 64 + b] = redn[0] + redn[1] + redn[2] + redn[3];
+  }
+}
+
+template <int LATE = 0>
+__global__ __launch_bounds__(64) void miro_pick_kernel(const float* logits, int ldl, int V, int nb, const SampRow* samp,
+                                                       const SampExt* ext, const float* ms, const double* mass,
+                                                       const int* cnt, float* mu, float* mu_hist, int mu_stride,
+                                                       int* tok_out, int* ids_next, int* pos_next, int* hist,
+                                                       int hist_stride, int* hist_count, int max_hist) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const SampExt& x = ext[c];
+  if (x.miro != 2) return;
+  const SampRow& sp = samp[c];
+  const float temp = sp.temp, m = ms[c * 2], ls = ms[c * 2 + 1], muc = mu[c];
+  const float* lr = logits + (size_t)c * ldl;
+  const int nh = hist ? hist_count[c] : 0;
+  const double mb = lane < nb ? mass[c * 64 + lane] : 0.0;
+  const int cb = lane < nb ? cnt[c * 64 + lane] : 0;
+  double S = 0.0;
+  int total = 0;
+  for (int b = 0; b < nb; ++b) S += __shfl(mb, b), total += __shfl(cb, b);
+  int tok = 0;
+  double pp = 1.0;  // renormalised probability of the pick
+  if (total == 0 || !(S > 0.0)) {
+    // nothing within mu: the argmax alone, ties to the lowest id
+    int best = 0x7fffffff;
+    for (int j = lane; j < V; j += 64)
+      if (lr[j] / temp == m) best = min(best, j);
+    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
+    tok = best == 0x7fffffff ? 0 : best;
+  } else {
+    const double u = samp_u01(sp.seed, (uint64_t)(sp.draw0 + nh)) * S;
+    int sb = -1, last = 0;
+    double base = 0.0, last_base = 0.0, cum = 0.0;
+    for (int b = 0; b < nb; ++b) {
+      const double mbb = __shfl(mb, b);
+      if (__shfl(cb, b) > 0) {
+        last = b, last_base = cum;
+        if (sb < 0 && u < cum + mbb) sb = b, base = cum;
+      }
+      cum += mbb;
+    }
+    if (sb < 0) sb = last, base = last_base;  // u S rounded past the last boundary: the last kept token
+    const int lo = (int)((long long)V * sb / nb), hi = (int)((long long)V * (sb + 1) / nb);
+    int found = -1, lastk = -1;
+    double pf = 0.0, pl = 0.0, run = base;
+    for (int j0 = lo; j0 < hi && found < 0; j0 += 64) {
+      const int j = j0 + lane;
+      double p = 0.0;
+      const bool kept = j < hi && miro_kept(lr[j], temp, m, ls, muc, &p);
+      double incl = p;
+      for (int o = 1; o < 64; o <<= 1) {
+        const double y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+      }
+      const unsigned long long hit = __ballot(kept && u < run + incl), km = __ballot(kept);
+      if (hit) {
+        const int l = __ffsll((long long)hit) - 1;
+        found = j0 + l, pf = __shfl(p, l);
+      }
+      if (km) {
+        const int l = 63 - __clzll((long long)km);
+        lastk = j0 + l, pl = __shfl(p, l);
+      }
+      run += __shfl(incl, 63);
+    }
+    if (found < 0) found = lastk, pf = pl;
+    tok = max(found, 0);
+    pp = pf / S;
+  }
+  if (lane == 0) {
+    const float mun = (float)((double)muc - (double)x.eta * (-log2(pp) - (double)x.tau));
+    mu[c] = mun;
+    if (mu_hist && nh < mu_stride) mu_hist[(size_t)c * mu_stride + nh] = mun;
+    if (tok_out) tok_out[c] = tok;
+    if (ids_next) ids_next[c] = tok;
+    if (pos_next) pos_next[c] += 1;
+    if (hist) {
+      if (nh < max_hist) hist[(size_t)c * hist_stride + nh] = tok;
+      hist_count[c] = nh + 1;
+    }
+  }
+}
+
+int miro_pick_host(const float* x, int V, float temp, float tau, float eta, double u01, float* mu) {
+  float m = -INFINITY;
+  for (int i = 0; i < V; i++) m = fmaxf(m, x[i] / temp);
+  double s = 0.0;
+  if (m > -INFINITY)
+    for (int i = 0; i < V; i++) s += exp((double)(x[i] / temp) - (double)m);
+  const double ls = log(s);
+  double S = 0.0;
+  int n = 0, first_max = -1;
+  for (int i = 0; i < V; i++) {
+    if (first_max < 0 && x[i] / temp == m) first_max = i;
+    const double lp = ((double)(x[i] / temp) - (double)m) - ls;
+    if (m > -INFINITY && -lp * 1.4426950408889634 <= (double)*mu) S += exp(lp), n++;
+  }
+  int tok = std::max(first_max, 0);
+  double pp = 1.0;
+  if (n > 0 && S > 0.0) {
+    const double u = u01 * S;
+    double cum = 0.0;
+    for (int i = 0; i < V; i++) {
+      const double lp = ((double)(x[i] / temp) - (double)m) - ls;
+      if (!(-lp * 1.4426950408889634 <= (double)*mu)) continue;
+      cum += exp(lp);
+      tok = i, pp = exp(lp) / S;
+      if (u < cum) break;
+    }
+  }
+  *mu = (float)((double)*mu - (double)eta * (-log2(pp) - (double)tau));
+  return tok;
+}
+
 int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* samp, int K, float* ws_val, int* ws_idx,
                         float* tk_val, int* tk_idx, int* tok_out, int* ids_next, int* pos_next, int* hist,
                         int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok,
-                        float* side_val) {
+                        float* side_val, const SampExtArgs* x) {
   if (K < 1 || K > TOPK_MAX || M < 1) return -1;
+  const SampExt* ext = x ? x->ext : nullptr;
+  const int nb = std::min(64, std::max(1, (V + 2047) / 2048));
+  if (ext && x->any_miro && (!x->mu || !x->ws_f || !x->ws_d || !x->ws_i || (V + nb - 1) / nb > 4096)) return -1;
+  if (ext) bias_kernel<0><<<M, SAMP_BIAS_MAX, 0, s>>>(logits, ldl, V, ext, x->bias_raw);
   penalty_kernel<<<M, 64, 0, s>>>(logits, ldl, samp, hist, hist_stride, hist_count, side_tok, side_val);
   if (launch_topk(logits, ldl, M, V, K, ws_val, ws_idx, tk_val, tk_idx, s)) return -1;
-  sample_kernel<<<M, 64, 0, s>>>(tk_val, tk_idx, K, samp, tok_out, ids_next, pos_next, hist, hist_stride, hist_count,
-                                 max_hist);
+  if (!ext) {
+    sample_kernel<<<M, 64, 0, s>>>(tk_val, tk_idx, K, samp, tok_out, ids_next, pos_next, hist, hist_stride, hist_count,
+                                   max_hist);
+    return 0;
+  }
+  sample_ext_kernel<0><<<M, 64, 0, s>>>(tk_val, tk_idx, K, samp, ext, tok_out, ids_next, pos_next, hist, hist_stride,
+                                     hist_count, max_hist);
+  if (x->any_miro) {
+    float* part = x->ws_f;
+    float* ms = x->ws_f + (size_t)M * 64 * 2;
+    miro_stage1<0><<<dim3(nb, M), 256, 0, s>>>(logits, ldl, V, samp, ext, part);
+    logprob_finish_kernel<<<M, 64, 0, s>>>(part, nb, ms, nullptr, 0);
+    miro_mass_kernel<0><<<dim3(nb, M), 256, 0, s>>>(logits, ldl, V, samp, ext, ms, x->mu, x->ws_d, x->ws_i);
+    miro_pick_kernel<0><<<M, 64, 0, s>>>(logits, ldl, V, nb, samp, ext, ms, x->ws_d, x->ws_i, x->mu, x->mu_hist,
+                                      x->mu_stride, tok_out, ids_next, pos_next, hist, hist_stride, hist_count,
+                                      max_hist);
+  }
   return 0;
 }
 
@@ -1833,7 +2102,8 @@ __global__ __launch_bounds__(64) void logprob_finish_kernel(const float* part, i
 __global__ __launch_bounds__(64) void logprob_gather_kernel(const float* logits, int ldl, int V, int K, const int* toks,
                                                             const int* hist_count, int max_steps, const int* side_tok,
                                                             const float* side_val, const float* ms, const float* top,
-                                                            const int* top_idx, float* out, size_t row_stride) {
+                                                            const int* top_idx, float* out, size_t row_stride,
+                                                            const SampExt* ext, const float* bias_raw) {
   const int c = blockIdx.x, lane = threadIdx.x;
   const int step = hist_count ? hist_count[c] - 1 : 0;
   if (step < 0 || step >= max_steps) return;
@@ -1845,6 +2115,16 @@ __global__ __launch_bounds__(64) void logprob_gather_kernel(const float* logits,
     const float sv = hit ? side_val[c * SAMP_WIN + lane] : 0.f;
     const unsigned long long mask = __ballot(hit);
     if (mask) raw = __shfl(sv, __ffsll((long long)mask) - 1);
+  }
+  if (ext) {  // a biased token: its value from before the bias (what the penalties saved was already biased)
+    const int nbias = min(ext[c].n_bias, SAMP_BIAS_MAX);
+    for (int j0 = 0; j0 < nbias; j0 += 64) {
+      const int j = j0 + lane;
+      const bool hit = j < nbias && ext[c].bias_tok[j] == tok;
+      const float bv = hit ? bias_raw[c * SAMP_BIAS_MAX + j] : 0.f;
+      const unsigned long long mask = __ballot(hit);
+      if (mask) raw = __shfl(bv, __ffsll((long long)mask) - 1);
+    }
   }
   if (lane == 0) o[0] = (raw - ms[c * 2]) - ms[c * 2 + 1];
   if (lane < K) {
@@ -1866,10 +2146,12 @@ int launch_logprob_stats(const float* logits, int ldl, int M, int V, int K, floa
 
 int launch_logprob_gather(const float* logits, int ldl, int M, int V, int K, const int* toks, const int* hist_count,
                           int max_steps, const int* side_tok, const float* side_val, const float* ms,
-                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s) {
+                          const float* top_lp, const int* top_idx, float* out, size_t row_stride, hipStream_t s,
+                          const SampExt* ext, const float* bias_raw) {
   if (K < 0 || K > TOPK_MAX || M < 1 || max_steps < 1 || row_stride < (size_t)max_steps * (1 + 2 * K)) return -1;
+  if (ext && !bias_raw) ext = nullptr;
   logprob_gather_kernel<<<M, 64, 0, s>>>(logits, ldl, V, K, toks, hist_count, max_steps, side_tok, side_val, ms,
-                                         top_lp, top_idx, out, row_stride);
+                                         top_lp, top_idx, out, row_stride, ext, bias_raw);
   return 0;
 }
 

@@ -34,7 +34,9 @@ EXPORTS = [
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
+    "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
 ]
+LOGIT_BIAS_MAX = 256  # kernels.h SAMP_BIAS_MAX: most logit_bias entries per request
 POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3  # mx_engine.h MX_POOL_*: how embed() pools a sequence's rows
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
 SPEC_MAX_DRAFT = 15  # kernels.h: most draft tokens per speculating step (1 + 15 rows of the <= 16-row path)
@@ -66,6 +68,40 @@ class MxSampling(ctypes.Structure):
                 ("min_p", ctypes.c_float), ("repeat_penalty", ctypes.c_float), ("repeat_last_n", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("ignore_eos", ctypes.c_int32),
                 ("frequency_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float)]
+
+
+class MxSamplingExt(ctypes.Structure):
+    _fields_ = [("base", MxSampling), ("typical_p", ctypes.c_float), ("tfs_z", ctypes.c_float),
+                ("mirostat_mode", ctypes.c_int32), ("mirostat_tau", ctypes.c_float), ("mirostat_eta", ctypes.c_float),
+                ("n_logit_bias", ctypes.c_int32), ("bias_tok", ctypes.POINTER(ctypes.c_int32)),
+                ("bias_val", ctypes.POINTER(ctypes.c_float))]
+
+
+_EXT_KEYS = ("typical_p", "tfs_z", "mirostat_mode", "mirostat_tau", "mirostat_eta", "logit_bias")
+
+
+def sampling_ext(base: "MxSampling", typical_p: float = 1.0, tfs_z: float = 1.0, mirostat_mode: int = 0,
+                 mirostat_tau: float = 5.0, mirostat_eta: float = 0.1, logit_bias=None, into=None):
+    """An mx_sampling_ext over `base`; logit_bias: {token id: bias} or (ids, values).  Returns (struct, keepalive):
+    the struct points into the keepalive arrays, which must outlive the call that reads it."""
+    s = into if into is not None else MxSamplingExt()
+    lib().mx_sampling_ext_default(ctypes.byref(s))
+    s.base = base
+    s.typical_p, s.tfs_z, s.mirostat_mode = typical_p, tfs_z, int(mirostat_mode)
+    s.mirostat_tau, s.mirostat_eta = mirostat_tau, mirostat_eta
+    keep = None
+    if logit_bias is not None and len(logit_bias):
+        if isinstance(logit_bias, dict):
+            toks, vals = list(logit_bias.keys()), list(logit_bias.values())
+        else:
+            toks, vals = logit_bias
+        bt = np.ascontiguousarray(toks, dtype=np.int32)
+        bv = np.ascontiguousarray(vals, dtype=np.float32)
+        s.n_logit_bias = len(bt)
+        s.bias_tok = bt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        s.bias_val = bv.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        keep = (bt, bv)
+    return s, keep
 
 
 class MxRowSampler(ctypes.Structure):
@@ -208,8 +244,13 @@ def lib() -> ctypes.CDLL:
         L.mx_engine_set_prefix_sharing.argtypes = [vp, i32]
         L.mx_prefix_sharing_stats.argtypes = [vp, P(MxSharingStats)]
         L.mx_kv_copy_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.mx_sampling_ext_default.argtypes = [P(MxSamplingExt)]
+        L.mx_submit_ext.argtypes = [vp, vp, i32, P(MxSamplingExt), i32, i32, i32, P(u64)]
+        L.mx_submit_ext_batch.argtypes = [vp, i32, vp, vp, vp, vp, P(u64)]
+        L.mx_sample_probe.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for name in EXPORTS:
-            if name not in ("mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_destroy",
+            if name not in ("mx_opts_default", "mx_sampling_default", "mx_sampling_ext_default", "mx_last_error",
+                            "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
                 getattr(L, name).restype = i32
         _lib = L
@@ -258,6 +299,48 @@ def logprob_probe(logits, targets, k: int, V: Optional[int] = None, device: int 
     _check(lib().mx_logprob_probe(device, lg.ctypes.data, n, V, ldl, tg.ctypes.data, k, tgt.ctypes.data,
                                   top.ctypes.data if ke else None, idx.ctypes.data if ke else None))
     return tgt, top, idx
+
+
+def sample_probe(logits, settings, seeds, n_drawn, windows=None, mu_in=None, V: Optional[int] = None,
+                 device: int = 0, want_logits: bool = False):
+    """The sampler chain on caller-supplied f32 rows (no engine; include/mx_engine.h mx_sample_probe): logits
+    [n][ldl] with V <= ldl valid columns, settings: one keyword dict per row (those of Engine.submit: temperature,
+    top_k, ..., typical_p, tfs_z, mirostat_*, logit_bias), seeds / n_drawn [n], windows: the rows' penalty windows
+    (<= 64 tokens each), mu_in [n] (default 2 tau).  device >= 0: the production kernels; -1: the host sampler,
+    no GPU.  Returns (tokens [n], mu_out [n]) and, with want_logits, the rows as the chain left them."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    n, ldl = lg.shape
+    V = ldl if V is None else V
+    arr = (MxSamplingExt * max(n, 1))()
+    keep = []
+    for i in range(min(n, len(arr))):
+        kw = dict(settings[i])
+        ext = {k: kw.pop(k) for k in _EXT_KEYS if k in kw}
+        kw.pop("seed", None)
+        keep.append(sampling_ext(sampling(**kw), into=arr[i], **ext)[1])
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+    nd = _i32(n_drawn)
+    win = np.zeros((max(n, 1), 64), dtype=np.int32)
+    nw = np.zeros(max(n, 1), dtype=np.int32)
+    for i, w in enumerate(windows or []):
+        w = list(w)[-64:]
+        win[i, :len(w)] = w
+        nw[i] = len(w)
+    mu = np.ascontiguousarray(mu_in if mu_in is not None else [2.0 * arr[i].mirostat_tau for i in range(n)],
+                              dtype=np.float32)
+    if len(sd) != n or len(nd) != n or len(mu) != n:
+        raise ValueError("one seed, draw index and mu per row")
+    tok = np.zeros(n, dtype=np.int32)
+    mu_out = np.zeros(n, dtype=np.float32)
+    out = np.empty_like(lg) if want_logits else None
+    rc = lib().mx_sample_probe(device, lg.ctypes.data, n, V, ldl, arr, sd.ctypes.data, nd.ctypes.data, win.ctypes.data,
+                               nw.ctypes.data, mu.ctypes.data, tok.ctypes.data, mu_out.ctypes.data,
+                               out.ctypes.data if out is not None else None)
+    if rc != MX_OK:
+        err = MxError(rc, lib().mx_last_error().decode(errors="replace"))
+        err.outputs = (tok, mu_out)  # still 0xFF bytes after a refusal
+        raise err
+    return (tok, mu_out, out) if want_logits else (tok, mu_out)
 
 
 def draft_probe(seqs, num_pred_tokens: int, max_ngram_size: int, pos0=None, slot0=None, device: int = 0):
@@ -576,6 +659,7 @@ class Engine:
     supports_draft = True  # submit(draft=) / spec_stats(): what Llama(draft_model=LlamaPromptLookupDecoding()) needs
     supports_embeddings = True  # embed(): what Llama(embedding=True).embed / create_embedding need
     supports_prefix_sharing = True  # set_prefix_sharing() / sharing_stats(): what Llama.set_cache needs
+    supports_sampler_ext = True  # submit(typical_p=, tfs_z=, mirostat_*=, logit_bias=): the whole sampler chain
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
@@ -682,8 +766,12 @@ class Engine:
                top_p: float = 0.95, min_p: float = 0.05, repeat_penalty: float = 1.0, repeat_last_n: int = 64,
                seed: Optional[int] = None, ignore_eos: bool = False, frequency_penalty: float = 0.0,
                presence_penalty: float = 0.0, logprobs: Optional[int] = None, prompt_logprobs: bool = False,
-               draft: Optional[Sequence[int]] = None) -> int:
-        """draft=(num_pred_tokens 1..15, max_ngram_size >= 1): prompt-lookup speculative decoding on the device --
+               draft: Optional[Sequence[int]] = None, typical_p: float = 1.0, tfs_z: float = 1.0,
+               mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1, logit_bias=None) -> int:
+        """typical_p / tfs_z / mirostat_mode=2 (mirostat_tau, mirostat_eta) / logit_bias={id: bias}: the rest of
+        llama-cpp-python's sampler chain, on the device (mx_submit_ext); such a request never
+        speculates.
+        draft=(num_pred_tokens 1..15, max_ngram_size >= 1): prompt-lookup speculative decoding on the device --
         the same tokens, several per weight pass where the context repeats itself; only greedy requests without
         penalties or logprobs on a bf16 model ever speculate (spec_stats() tells), the others decode as always.
         logprobs=k (0..64): the request also records each generated token's log-probability and the k
@@ -697,7 +785,14 @@ class Engine:
         if seed is not None and seed >= 0:
             s.seed = seed
         req = ctypes.c_uint64()
-        if draft is not None and logprobs is None:
+        if typical_p != 1.0 or tfs_z != 1.0 or mirostat_mode != 0 or logit_bias:
+            if prompt_logprobs and logprobs is None:
+                raise ValueError("prompt_logprobs needs logprobs=k")
+            x, keep = sampling_ext(s, typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
+            _check(lib().mx_submit_ext(self._h, ids.ctypes.data, len(ids), ctypes.byref(x), max_tokens,
+                                       -1 if logprobs is None else int(logprobs), int(bool(prompt_logprobs)),
+                                       ctypes.byref(req)))
+        elif draft is not None and logprobs is None:
             if prompt_logprobs:
                 raise ValueError("prompt_logprobs needs logprobs=k")
             d, ng = draft
@@ -745,6 +840,19 @@ class Engine:
         mts = _i32(list(max_tokens) if hasattr(max_tokens, "__len__") else [max_tokens] * n)
         samp = (MxSampling * n)()
         base = kw
+        kws = [dict(base, **per_request[i]) if per_request is not None else base for i in range(n)]
+        if any(k in kwi for kwi in kws for k in _EXT_KEYS):
+            # some request has a setting of the extended chain: one mx_sampling_ext each, queued atomically too
+            xs = (MxSamplingExt * n)()
+            keep = []
+            for i in range(n):
+                kwi = dict(kws[i])
+                ext = {k: kwi.pop(k) for k in _EXT_KEYS if k in kwi}
+                sd = kwi.pop("seed", seeds[i] if seeds is not None else None)
+                keep.append(sampling_ext(sampling(seed=sd, **kwi), into=xs[i], **ext)[1])
+            reqs = (ctypes.c_uint64 * n)()
+            _check(lib().mx_submit_ext_batch(self._h, n, ptrs, lens.ctypes.data, xs, mts.ctypes.data, reqs))
+            return list(reqs)
         for i in range(n):
             kw = dict(base, **per_request[i]) if per_request is not None else base
             if per_request is not None and "seed" in kw:

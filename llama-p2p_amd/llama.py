@@ -23,6 +23,7 @@ dict of ``create_embedding``.  The final norm, the pooling and the L2 normalisat
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 import time
@@ -190,8 +191,11 @@ class Llama:
                           logprobs: Optional[int] = None, echo: bool = False,
                           stop: Optional[Union[str, List[str]]] = [], frequency_penalty: float = 0.0,
                           presence_penalty: float = 0.0, repeat_penalty: float = 1.0, top_k: int = 40,
-                          stream: bool = False, seed: Optional[int] = None,
+                          stream: bool = False, seed: Optional[int] = None, tfs_z: float = 1.0,
+                          mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1,
+                          logit_bias: Optional[Dict[int, float]] = None,
                           **kwargs: Any) -> Union[Dict[str, Any], Iterator[Dict[str, Any]]]:
+        ext_kw = self._sampler_ext_kw(typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
         if logprobs is not None:
             if logprobs < 0 or logprobs > _engine.TOPK_MAX:
                 raise ValueError(f"logprobs must be 0..{_engine.TOPK_MAX} (llama-cpp-python has no cap; the "
@@ -200,8 +204,6 @@ class Llama:
                 raise NotImplementedError("logprobs with stream=True are not supported")
             if not getattr(self._engine, "supports_logprobs", False):
                 raise NotImplementedError("logprobs are not supported by this engine front")
-        if typical_p != 1.0:
-            raise NotImplementedError("typical_p != 1.0 is not supported (llama-cpp-python's default 1.0 is)")
         created = int(time.time())
         cid = f"cmpl-{uuid.uuid4()}"
         if isinstance(prompt, str):
@@ -218,6 +220,7 @@ class Llama:
         draft = getattr(self, "_draft", None)
         if draft is not None:  # only when set: engine fronts without the keyword keep working
             lp_kw["draft"] = draft
+        lp_kw.update(ext_kw)  # only the non-default ones, as draft
         req = self._engine.submit(prompt_tokens, max_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
                                   min_p=min_p, repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty,
                                   presence_penalty=presence_penalty, seed=None if sd == LLAMA_DEFAULT_SEED else sd,
@@ -274,6 +277,45 @@ class Llama:
             "usage": {"prompt_tokens": len(prompt_tokens), "completion_tokens": len(toks),
                       "total_tokens": len(prompt_tokens) + len(toks)},
         }
+
+    def _sampler_ext_kw(self, typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias) -> Dict[str, Any]:
+        """The keywords of the extended sampler chain (typical_p, tfs_z, Mirostat v2, logit_bias) that are off
+        llama-cpp-python's defaults, validated: only those are passed to the engine's submit(), so a front
+        without them keeps working with default settings and raises NotImplementedError otherwise."""
+        for name, v in (("typical_p", typical_p), ("tfs_z", tfs_z), ("mirostat_tau", mirostat_tau),
+                        ("mirostat_eta", mirostat_eta)):
+            if math.isnan(float(v)):
+                raise ValueError(f"{name} is NaN")
+        if mirostat_mode == 1:
+            raise NotImplementedError("mirostat_mode=1 (Mirostat v1) is not supported; mirostat_mode=2 is")
+        if mirostat_mode not in (0, 2):
+            raise ValueError("mirostat_mode must be 0, 1 or 2")
+        kw: Dict[str, Any] = {}
+        if typical_p != 1.0:
+            kw["typical_p"] = float(typical_p)
+        if tfs_z != 1.0:
+            kw["tfs_z"] = float(tfs_z)
+        if mirostat_mode != 0:
+            kw["mirostat_mode"] = int(mirostat_mode)
+        if mirostat_mode != 0 and mirostat_tau != 5.0:  # tau / eta mean nothing without Mirostat
+            kw["mirostat_tau"] = float(mirostat_tau)
+        if mirostat_mode != 0 and mirostat_eta != 0.1:
+            kw["mirostat_eta"] = float(mirostat_eta)
+        if logit_bias:
+            if len(logit_bias) > _engine.LOGIT_BIAS_MAX:
+                raise ValueError(f"logit_bias holds more than {_engine.LOGIT_BIAS_MAX} entries")
+            bias = {}
+            for t, b in logit_bias.items():
+                t, b = int(t), float(b)
+                if t < 0 or t >= self.n_vocab():
+                    raise ValueError(f"logit_bias: token id {t} is outside the vocabulary")
+                if math.isnan(b) or b == math.inf:
+                    raise ValueError("logit_bias: a bias must not be NaN or +inf (-inf bans a token)")
+                bias[t] = b
+            kw["logit_bias"] = bias
+        if kw and not getattr(self._engine, "supports_sampler_ext", False):
+            raise NotImplementedError(f"{', '.join(sorted(kw))}: not supported by this engine front")
+        return kw
 
     def _logprobs_dict(self, prompt_tokens: List[int], toks: List[int], lp, k: int, echo: bool,
                        prompt_len: int) -> Dict[str, Any]:
