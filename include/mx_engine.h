@@ -335,6 +335,44 @@ typedef struct {
 int mx_kv_copy_probe(int device, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx, int n_copies,
                      const mx_kv_copy* copies, void* kcache, void* vcache);
 
+/* Host-RAM tier behind the KV slots (llama-cpp-python's LlamaRAMCache(capacity_bytes)), DESIGN.md §14.  Off by
+ * default (capacity 0).  On: when a request is admitted into a slot whose recorded tokens (at least 32) are held
+ * to within 31 positions by nothing else -- the request's own prompt, another slot, a host entry -- the slot's
+ * K/V are first packed on the device and written to pinned host memory in the background; a later prompt that
+ * matches a host entry by at least 32 positions more than any device source gets those positions back by one
+ * host-to-device transfer and one kernel instead of a prefill.  The entries' bytes never exceed capacity_bytes:
+ * least recently used entries are evicted, an entry above the capacity is not stored.  Lowering the capacity
+ * evicts at once, 0 drops every entry and switches the tier off.  Requests with prompt log-probabilities and
+ * embedding requests are not restored (their slots are spilled like any other).  Takes effect at the next
+ * admission; a pipeline-stage engine returns MX_ERR_STATE. */
+int mx_engine_set_host_cache(mx_engine* e, uint64_t capacity_bytes);
+/* entries / bytes: what the store holds now; spills / spilled_bytes: entries written to host memory;
+ * restores / restored_bytes: host-to-device transfers and their bytes; restored_prompt_tokens: prompt positions
+ * requests received from host entries beyond what their slot held (mx_stats.reused_prompt_tokens keeps counting
+ * only those); evictions: entries dropped for the budget; skipped: records larger than the capacity. */
+typedef struct {
+  uint64_t entries, bytes, capacity_bytes, spills, spilled_bytes, restores, restored_prompt_tokens, restored_bytes,
+      evictions, skipped;
+} mx_host_cache_counts;
+int mx_host_cache_stats(mx_engine* e, mx_host_cache_counts* out);
+/* The pack / unpack kernels on caller-supplied caches, no engine.  kcache / vcache as for mx_kv_copy_probe.  The
+ * packed form of entry i is packed[t][layer][K|V][kv head][32 * head_dim] f16, t = 0 .. P/32 - 1, P = n_pos
+ * rounded up to 32, starting at 16-byte word offset16 of `packed`; one tile t is n_layer * 2 * n_head_kv * 32 *
+ * head_dim * 2 bytes.  dir 0 packs: `packed` (packed_bytes + MX_KV_PACK_GUARD_BYTES bytes, output only) is filled
+ * with 0xFF on the device before the launch and copied back with its guard; the caches are copied back too and
+ * must come back unchanged.  dir 1 unpacks `packed` (packed_bytes bytes, input) into the caches: positions [0, P)
+ * of slot `slot` change, every other byte stays.  Slots in range, 1 <= n_pos <= n_ctx, offsets a whole number of
+ * tiles, every entry inside packed_bytes, no two packed ranges overlapping, (dir 1) no slot twice, packed_bytes a
+ * multiple of 16 and at most 1 GiB.  Anything else is MX_ERR_ARG and nothing is launched. */
+#define MX_KV_PACK_GUARD_BYTES 4096
+typedef struct {
+  int32_t slot, n_pos;
+  uint64_t offset16;
+} mx_kv_pack;
+int mx_kv_pack_probe(int device, int dir, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx,
+                     int n_entries, const mx_kv_pack* entries, void* kcache, void* vcache, void* packed,
+                     uint64_t packed_bytes);
+
 /* The production bf16 matmul launchers on caller-supplied W / X, no engine (tests on shapes no model has).
  * path 0 launch_mm (M 1..64), 1 launch_mm_pers (M 1..16, shapes of mx_matmul_plan's pers_ok), 2 launch_mm_wide
  * (M 1..64), 3 launch_mm_wide with full_chain, 4 launch_gemm_split (M 65..4096 as in the engine, `target`

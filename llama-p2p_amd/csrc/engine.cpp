@@ -470,6 +470,41 @@ struct mx_engine {
   // destination rule would have taken it), and a slot a copy fills never matches better than the slot it is
   // filled from, which wins the tie -- so no slot is both
   int run_kv_copies(const std::vector<KvCopy>& tab);
+  // host-RAM tier behind the slots (mx_engine_set_host_cache).  A slot record about to be
+  // destroyed is packed into pack_stage on the engine stream and leaves for pinned host memory on stream2; a
+  // prompt that matches a host entry HOST_MIN positions better than any device source gets them back through
+  // unpack_stage.  HOST_MIN is one packed tile.  The store is the scheduler thread's alone (under mu where the
+  // admission loop reads it); host_cap_req is the API's side of the capacity, applied at the top of the loop.
+  static constexpr int HOST_MIN = 32;
+  struct HostEntry {
+    std::vector<int32_t> tokens;  // the record it was spilled from
+    void* pinned = nullptr;       // packed K/V of ceil32(tokens.size()) positions
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;  // its device-to-host transfer
+    uint64_t used = 0, born = 0;  // LRU clock; the admission round that made it (visible from the next one on)
+  };
+  struct HostSpill { std::shared_ptr<HostEntry> e; int slot; };
+  struct HostRestore { std::shared_ptr<HostEntry> e; int slot, n_pos; };
+  std::vector<std::shared_ptr<HostEntry>> host_entries, host_trash;  // trash: evicted, freed after the round
+  uint64_t host_cap = 0, host_cap_req = 0, host_bytes = 0, host_clock = 0, host_round = 0;
+  bool host_failed = false;  // the staging could not be allocated
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_packed = nullptr, ev_stage_free = nullptr;
+  char *pack_stage = nullptr, *unpack_stage = nullptr;
+  size_t stage_bytes = 0, host_tile_bytes = 0;
+  KvPack *d_pack_tab = nullptr, *d_unpack_tab = nullptr, *h_pack_tab = nullptr;  // [n_seq_max] each; h: pinned, both
+  uint64_t stat_host_spills = 0, stat_host_spilled_bytes = 0, stat_host_restores = 0, stat_host_restored_tokens = 0,
+           stat_host_restored_bytes = 0, stat_host_evictions = 0, stat_host_skipped = 0;
+  void host_apply_capacity();                                  // under mu, scheduler thread
+  void host_drop(size_t i) {                                   // under mu: entry i leaves the store
+    host_bytes -= host_entries[i]->bytes;
+    host_trash.push_back(std::move(host_entries[i]));
+    host_entries.erase(host_entries.begin() + i);
+  }
+  void host_insert(const std::vector<int32_t>& st, int slot, std::vector<HostSpill>& spills);  // under mu
+  void host_free_trash();
+  int run_host_spills(std::vector<HostSpill>& spills);
+  int run_host_restores(const std::vector<HostRestore>& restores);
   uint64_t stat_prompt_tokens = 0, stat_reused_tokens = 0, stat_generated_tokens = 0;
   uint64_t next_id = 1;
   bool stop = false;
@@ -581,6 +616,14 @@ mx_engine::~mx_engine() {
   for (auto& kv : sched_graphs) hipGraphExecDestroy(kv.second);
   for (auto& kv : spec_graphs) hipGraphExecDestroy(kv.second);
   if (stream) hipStreamSynchronize(stream);
+  // the host tier: its transfers end before the pinned memory and the staging they use are freed
+  if (stream2) hipStreamSynchronize(stream2);
+  while (!host_entries.empty()) host_drop(host_entries.size() - 1);
+  host_free_trash();
+  if (h_pack_tab) hipHostFree(h_pack_tab);
+  if (ev_packed) hipEventDestroy(ev_packed);
+  if (ev_stage_free) hipEventDestroy(ev_stage_free);
+  if (stream2) hipStreamDestroy(stream2);
 
   for (void* p : allocations) hipFree(p);
   if (h_idx) hipHostFree(h_idx);
@@ -1829,6 +1872,210 @@ int mx_engine::run_kv_copies(const std::vector<KvCopy>& tab) {
   return 0;
 }
 
+// ---- host-RAM tier
+// The capacity the API asked for becomes the store's (scheduler thread, under mu): evict down to it, 0 drops
+// everything; the first capacity above 0 allocates the second stream, the events, the two staging areas (one
+// slot's whole K/V each) and the tables.
+void mx_engine::host_apply_capacity() {
+  if (host_cap_req > 0 && !pack_stage && !host_failed) {
+    host_tile_bytes = kv_pack_tile_bytes(le - lb, n_head_kv, head_dim);
+    stage_bytes = (size_t)(ctx_stride / 32) * host_tile_bytes;
+    const bool ok = hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&ev_packed, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&ev_stage_free, hipEventDisableTiming) == hipSuccess &&
+                    hipHostMalloc((void**)&h_pack_tab, (size_t)2 * n_seq_max * sizeof(KvPack), hipHostMallocDefault) ==
+                        hipSuccess &&
+                    !alloc((void**)&d_pack_tab, (size_t)n_seq_max * sizeof(KvPack)) &&
+                    !alloc((void**)&d_unpack_tab, (size_t)n_seq_max * sizeof(KvPack)) &&
+                    !alloc((void**)&unpack_stage, stage_bytes) && !alloc((void**)&pack_stage, stage_bytes);
+    if (!ok) {
+      pack_stage = nullptr;
+      host_failed = true;
+    }
+  }
+  if (host_failed) host_cap_req = 0;
+  host_cap = host_cap_req;
+  while (!host_entries.empty() && (host_cap == 0 || host_bytes > host_cap)) {
+    size_t lru = 0;
+    for (size_t i = 1; i < host_entries.size(); i++)
+      if (host_entries[i]->used < host_entries[lru]->used) lru = i;
+    if (host_cap) stat_host_evictions++;
+    host_drop(lru);
+  }
+}
+
+// A record that nothing else covers enters the store (under mu): entries whose tokens are a prefix of it leave,
+// least recently used ones until it fits; its memory and its transfer follow in run_host_spills.
+void mx_engine::host_insert(const std::vector<int32_t>& st, int slot, std::vector<HostSpill>& spills) {
+  const size_t bytes = (size_t)(((int)st.size() + 31) / 32) * host_tile_bytes;
+  if (bytes > host_cap) {
+    stat_host_skipped++;
+    return;
+  }
+  for (size_t i = host_entries.size(); i-- > 0;) {
+    const std::vector<int32_t>& t = host_entries[i]->tokens;
+    if (t.size() <= st.size() && std::equal(t.begin(), t.end(), st.begin())) host_drop(i);
+  }
+  while (host_bytes + bytes > host_cap) {
+    size_t lru = 0;
+    for (size_t i = 1; i < host_entries.size(); i++)
+      if (host_entries[i]->used < host_entries[lru]->used) lru = i;
+    stat_host_evictions++;
+    host_drop(lru);
+  }
+  auto e = std::make_shared<HostEntry>();
+  e->tokens = st;
+  e->bytes = bytes;
+  e->used = ++host_clock;
+  e->born = host_round;
+  host_bytes += bytes;
+  host_entries.push_back(e);
+  spills.push_back({e, slot});
+}
+
+// Evicted entries: their pinned memory goes once their transfer has ended (never under mu: the wait may be long)
+void mx_engine::host_free_trash() {
+  for (auto& e : host_trash) {
+    if (e->done) {
+      hipEventSynchronize(e->done);
+      hipEventDestroy(e->done);
+    }
+    if (e->pinned) hipHostFree(e->pinned);
+    e->pinned = nullptr;
+    e->done = nullptr;
+  }
+  host_trash.clear();
+}
+
+// The round's spills: pack launches on the engine stream -- the first thing of the round on it, so they read the
+// slots as they stand -- each followed by its entries' device-to-host transfers on stream2.  A launch takes as
+// many entries as pack_stage holds; the next one waits on the stream for the transfers that still read it.
+int mx_engine::run_host_spills(std::vector<HostSpill>& spills) {
+  static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
+  if (spills.empty()) return 0;
+  if ((int)spills.size() > n_seq_max) return fail(MX_ERR_STATE, "more KV spills than slots in one round");
+  // an entry evicted again in the same admission round is not written; one whose memory cannot be had is dropped
+  std::vector<HostSpill> live;
+  for (HostSpill& sp : spills) {
+    const bool kept = std::find(host_entries.begin(), host_entries.end(), sp.e) != host_entries.end();
+    if (kept && (hipHostMalloc(&sp.e->pinned, sp.e->bytes, hipHostMallocDefault) != hipSuccess ||
+                 hipEventCreateWithFlags(&sp.e->done, hipEventDisableTiming) != hipSuccess)) {
+      (void)hipGetLastError();
+      std::lock_guard<std::mutex> lk(mu);
+      stat_host_skipped++;
+      host_drop(std::find(host_entries.begin(), host_entries.end(), sp.e) - host_entries.begin());
+    } else if (kept) {
+      live.push_back(sp);
+    }
+  }
+  size_t done = 0, total = 0;
+  while (done < live.size()) {
+    size_t n = 0, off = 0;
+    while (done + n < live.size() && off + live[done + n].e->bytes <= stage_bytes) {
+      h_pack_tab[done + n] = {live[done + n].slot, (int32_t)live[done + n].e->tokens.size(), (int64_t)(off / 16)};
+      off += live[done + n].e->bytes;
+      n++;
+    }
+    if (!n) return fail(MX_ERR_STATE, "a KV spill larger than the staging area");
+    HIPC(hipStreamWaitEvent(stream, ev_stage_free, 0));  // (a no-op before the first record)
+    HIPC(hipMemcpyAsync(d_pack_tab + done, h_pack_tab + done, n * sizeof(KvPack), hipMemcpyHostToDevice, stream));
+    std::chrono::steady_clock::time_point t0;
+    if (trace) {
+      hipStreamSynchronize(stream);
+      t0 = std::chrono::steady_clock::now();
+    }
+    if (launch_kv_pack(kcache, vcache, pack_stage, stage_bytes, h_pack_tab + done, d_pack_tab + done, (int)n, le - lb,
+                       n_seq_max, n_head_kv, head_dim, n_ctx, ctx_stride, slot_stride, layer_kv_stride, stream)) {
+      hipStreamSynchronize(stream);
+      return fail(MX_ERR_STATE, "KV pack table refused");
+    }
+    HIPC(hipEventRecord(ev_packed, stream));
+    std::chrono::steady_clock::time_point t1;
+    if (trace) {
+      hipStreamSynchronize(stream);
+      t1 = std::chrono::steady_clock::now();
+    }
+    HIPC(hipStreamWaitEvent(stream2, ev_packed, 0));
+    for (size_t i = 0; i < n; i++) {
+      HostEntry& e = *live[done + i].e;
+      HIPC(hipMemcpyAsync(e.pinned, pack_stage + (size_t)h_pack_tab[done + i].off16 * 16, e.bytes,
+                          hipMemcpyDeviceToHost, stream2));
+      HIPC(hipEventRecord(e.done, stream2));
+    }
+    HIPC(hipEventRecord(ev_stage_free, stream2));
+    if (trace) {
+      hipStreamSynchronize(stream2);
+      const auto t2 = std::chrono::steady_clock::now();
+      fprintf(stderr, "sched: host spill %zu entries %zu bytes pack %.3f ms d2h %.3f ms\n", n, off,
+              std::chrono::duration<double, std::milli>(t1 - t0).count(),
+              std::chrono::duration<double, std::milli>(t2 - t1).count());
+    }
+    total += off;
+    done += n;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  stat_host_spills += live.size();
+  stat_host_spilled_bytes += total;
+  return 0;
+}
+
+// The round's restores, all on the engine stream ahead of the round's copies and prefill: each entry's first
+// ceil32(n_pos)/32 tiles -- one contiguous prefix of its pinned memory -- to unpack_stage once its own transfer
+// out has ended (its event), then one unpack launch for as many as the staging holds.
+int mx_engine::run_host_restores(const std::vector<HostRestore>& restores) {
+  static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
+  if (restores.empty()) return 0;
+  if ((int)restores.size() > n_seq_max) return fail(MX_ERR_STATE, "more KV restores than slots in one round");
+  KvPack* h_tab = h_pack_tab + n_seq_max;
+  size_t done = 0, total = 0;
+  while (done < restores.size()) {
+    std::chrono::steady_clock::time_point t0;
+    if (trace) {
+      hipStreamSynchronize(stream);
+      for (size_t i = done; i < restores.size(); i++) hipEventSynchronize(restores[i].e->done);
+      t0 = std::chrono::steady_clock::now();
+    }
+    size_t n = 0, off = 0;
+    while (done + n < restores.size()) {
+      const HostRestore& rs = restores[done + n];
+      const size_t bytes = (size_t)((rs.n_pos + 31) / 32) * host_tile_bytes;
+      if (!rs.e->pinned || !rs.e->done || bytes > rs.e->bytes)
+        return fail(MX_ERR_STATE, "a KV restore from an entry that does not hold it");
+      if (off + bytes > stage_bytes) break;
+      h_tab[done + n] = {rs.slot, rs.n_pos, (int64_t)(off / 16)};
+      HIPC(hipStreamWaitEvent(stream, rs.e->done, 0));
+      HIPC(hipMemcpyAsync(unpack_stage + off, rs.e->pinned, bytes, hipMemcpyHostToDevice, stream));
+      off += bytes;
+      n++;
+    }
+    if (!n) return fail(MX_ERR_STATE, "a KV restore larger than the staging area");
+    HIPC(hipMemcpyAsync(d_unpack_tab + done, h_tab + done, n * sizeof(KvPack), hipMemcpyHostToDevice, stream));
+    std::chrono::steady_clock::time_point t1;
+    if (trace) {
+      hipStreamSynchronize(stream);
+      t1 = std::chrono::steady_clock::now();
+    }
+    if (launch_kv_unpack(kcache, vcache, unpack_stage, stage_bytes, h_tab + done, d_unpack_tab + done, (int)n, le - lb,
+                         n_seq_max, n_head_kv, head_dim, n_ctx, ctx_stride, slot_stride, layer_kv_stride, stream)) {
+      hipStreamSynchronize(stream);
+      return fail(MX_ERR_STATE, "KV unpack table refused");
+    }
+    if (trace) {
+      hipStreamSynchronize(stream);
+      const auto t2 = std::chrono::steady_clock::now();
+      fprintf(stderr, "sched: host restore %zu entries %zu bytes h2d %.3f ms unpack %.3f ms\n", n, off,
+              std::chrono::duration<double, std::milli>(t1 - t0).count(),
+              std::chrono::duration<double, std::milli>(t2 - t1).count());
+    }
+    total += off;
+    done += n;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  stat_host_restores += restores.size();
+  stat_host_restored_bytes += total;
+  return 0;
+}
+
 void mx_engine::finish(Request* r, int why) {
   r->finish = why;
   r->done = true;
@@ -2633,7 +2880,10 @@ void mx_engine::scheduler_loop() {
     // round to their followers (post); all empty while the switch is off
     std::vector<Request*> followers;
     std::vector<KvCopy> pre, post;
-    auto lcp = [](const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
+    // host tier: records leaving for host memory and prefixes coming back; empty while it is off
+    std::vector<HostSpill> spills;
+    std::vector<HostRestore> restores;
+    auto lcp =[](const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
       int l = 0;
       const int lim = (int)std::min(a.size(), b.size());
       while (l < lim && a[l] == b[l]) l++;
@@ -2641,7 +2891,12 @@ void mx_engine::scheduler_loop() {
     };
     {
       std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return stop || !pending.empty() || !active.empty(); });
+      cv.wait(lk, [&] { return stop || !pending.empty() || !active.empty() || host_cap_req != host_cap; });
+      if (!stop && host_cap_req != host_cap) {  // mx_engine_set_host_cache waits on cv_done for this
+        host_apply_capacity();
+        cv_done.notify_all();
+      }
+      if (host_cap && !pending.empty() && !free_slots.empty()) host_round++;
       if (stop) {
         for (Request* r : pending) { r->error = "engine shutting down"; finish(r, MX_FINISH_ERROR); }
         for (Request* r : active) { r->error = "engine shutting down"; finish(r, MX_FINISH_ERROR); }
@@ -2674,6 +2929,33 @@ void mx_engine::scheduler_loop() {
         r->reuse = (r->lp_prompt || r->embd) ? 0 : std::min(best_lcp, n - 1);
         stat_prompt_tokens += r->prompt.size();
         stat_reused_tokens += r->reuse;
+        // the longest match over the host entries of earlier rounds: worth a restore when it beats every device
+        // source -- the slot's own record, a copy, a leader of this round -- by HOST_MIN (a device source of
+        // equal length is cheaper and wins)
+        std::shared_ptr<HostEntry> hsrc;
+        int h = -1;
+        if (host_cap && !r->lp_prompt && !r->embd)
+          for (auto& e : host_entries) {
+            const int l = e->born < host_round ? lcp(e->tokens, r->prompt) : -1;
+            if (l > h) h = l, hsrc = e;
+          }
+        bool restore = hsrc && h - best_lcp >= HOST_MIN;
+        if (restore) hsrc->used = ++host_clock;  // before the spill below looks for the least recently used
+        if (host_cap && (int)slot_tokens[r->slot].size() >= HOST_MIN) {
+          // the slot's record is about to be cut to what this request keeps of it: it goes to host memory unless
+          // the prompt, another slot's record or a host entry holds it to within HOST_MIN positions
+          const std::vector<int32_t>& st = slot_tokens[r->slot];
+          const int L = (int)st.size();
+          int cover = lcp(st, r->prompt);
+          for (int s = 0; s < n_seq_max; s++)
+            if (s != r->slot) cover = std::max(cover, lcp(st, slot_tokens[s]));
+          for (auto& e : host_entries) {
+            const int l = lcp(st, e->tokens);
+            cover = std::max(cover, l);
+            if (l == L) e->used = ++host_clock;  // it holds the record whole: as good as spilled again
+          }
+          if (L - cover >= HOST_MIN) host_insert(st, r->slot, spills);
+        }
         if (prefix_sharing && !r->lp_prompt && !r->embd) {
           // the longest match over every other slot's record, free or busy (ties: a slot no copy of this round
           // writes, so no slot is both a source and a destination); worth a copy when it beats the slot's own by
@@ -2683,7 +2965,9 @@ void mx_engine::scheduler_loop() {
           for (int s = 0; s < n_seq_max; s++) {
             if (s == r->slot) continue;
             const int l = lcp(slot_tokens[s], r->prompt);
-            const bool written = std::any_of(pre.begin(), pre.end(), [&](const KvCopy& c) { return c.dst == s; });
+            const bool written =
+                std::any_of(pre.begin(), pre.end(), [&](const KvCopy& c) { return c.dst == s; }) ||
+                std::any_of(restores.begin(), restores.end(), [&](const HostRestore& c) { return c.slot == s; });
             if (l > src || (l == src && src_written && !written)) src = l, src_slot = s, src_written = written;
           }
           const bool copy = src_slot >= 0 && src - cur >= SHARE_MIN;
@@ -2696,7 +2980,11 @@ void mx_engine::scheduler_loop() {
             const int l = lcp(a->prompt, r->prompt);
             if (l > fl) fl = l, lead = a;
           }
-          if (lead && fl - cur >= SHARE_MIN) {
+          const bool follow = lead && fl - cur >= SHARE_MIN;
+          restore = hsrc && h - (follow ? fl : cur) >= HOST_MIN;
+          if (restore) {
+            // no copy and no leader for this request: the host entry serves it (below)
+          } else if (follow) {
             cur = fl;
             r->reuse = std::min(cur, n - 1);
             post.push_back({lead->slot, r->slot, r->reuse});
@@ -2707,6 +2995,12 @@ void mx_engine::scheduler_loop() {
             pre.push_back({src_slot, r->slot, r->reuse});
           }
           stat_shared_tokens += r->reuse - std::min(best_lcp, n - 1);
+        }
+        if (restore) {
+          r->reuse = std::min(h, n - 1);
+          restores.push_back({hsrc, r->slot, r->reuse});
+          hsrc->used = ++host_clock;
+          stat_host_restored_tokens += r->reuse - std::min(best_lcp, n - 1);
         }
         // the record of the now busy slot: what it holds once the copies from slots as they stand have run (a
         // follower's copy runs after the others' prefill: until then its slot holds its own match only)
@@ -2720,7 +3014,19 @@ void mx_engine::scheduler_loop() {
     if (!admit.empty()) {
       // copies from slots as they stand, then the prefill -- with followers: the others' prefill, one copy launch
       // from their slots, the followers' prefill.  Without sharing this is prefill_batch(admit), as ever.
-      int rc = run_kv_copies(pre);
+      // With the host tier on, ahead of all that and in this order on the engine stream: the packs of the records
+      // this round destroys (they read the slots before anything of the round writes them), the restores, then
+      // the copies -- a slot a restore filled may be a copy's source.
+      int rc = run_host_spills(spills);
+      if (rc) {  // none of the round's entries may serve a later restore
+        std::lock_guard<std::mutex> lk(mu);
+        for (HostSpill& sp : spills) {
+          const auto it = std::find(host_entries.begin(), host_entries.end(), sp.e);
+          if (it != host_entries.end()) host_drop(it - host_entries.begin());
+        }
+      }
+      if (!rc) rc = run_host_restores(restores);
+      if (!rc) rc = run_kv_copies(pre);
       if (!rc && followers.empty()) {
         rc = prefill_batch(admit);
       } else if (!rc) {
@@ -2734,7 +3040,8 @@ void mx_engine::scheduler_loop() {
       std::lock_guard<std::mutex> lk(mu);
       for (Request* r : admit) {
         if (rc) {
-          if (!pre.empty() || !post.empty()) r->pos = 0;  // a copy or a prefill may not have run: the slot keeps no record
+          // a copy, a restore or a prefill may not have run: the slot keeps no record
+          if (!pre.empty() || !post.empty() || !restores.empty()) r->pos = 0;
           r->error = g_err;
           finish(r, MX_FINISH_ERROR);
           continue;
@@ -2749,6 +3056,11 @@ void mx_engine::scheduler_loop() {
         else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
         else active.push_back(r);
       }
+    }
+    if (!host_trash.empty()) {  // evicted entries: a restore of this round may still have read one
+      if (!restores.empty()) hipStreamSynchronize(stream);
+      restores.clear();
+      host_free_trash();
     }
     std::vector<Request*> rows;
     {
@@ -4317,6 +4629,90 @@ int mx_kv_copy_probe(int device, int n_layer, int n_slots, int n_head_kv, int he
   HIPC(hipDeviceSynchronize());
   HIPC(hipMemcpy(kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
   HIPC(hipMemcpy(vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mx_engine_set_host_cache(mx_engine* e, uint64_t capacity_bytes) {
+  if (!e) return fail(MX_ERR_ARG, "null engine");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "the host cache needs a whole-model engine");
+  std::unique_lock<std::mutex> lk(e->mu);
+  e->host_cap_req = capacity_bytes;
+  if (!e->worker_started) return 0;  // nothing is stored yet: the scheduler takes it up before its first admission
+  // the scheduler thread owns the store: it evicts down to the new capacity now, and this call returns after that
+  e->cv.notify_all();
+  e->cv_done.wait(lk, [&] { return e->stop || e->host_cap == e->host_cap_req; });
+  if (capacity_bytes && e->host_failed) return fail(MX_ERR_HIP, "the host cache's device staging could not be allocated");
+  return 0;
+}
+
+int mx_host_cache_stats(mx_engine* e, mx_host_cache_counts* out) {
+  if (!e || !out) return fail(MX_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  out->entries = e->host_entries.size();
+  out->bytes = e->host_bytes;
+  out->capacity_bytes = e->host_cap_req;
+  out->spills = e->stat_host_spills;
+  out->spilled_bytes = e->stat_host_spilled_bytes;
+  out->restores = e->stat_host_restores;
+  out->restored_prompt_tokens = e->stat_host_restored_tokens;
+  out->restored_bytes = e->stat_host_restored_bytes;
+  out->evictions = e->stat_host_evictions;
+  out->skipped = e->stat_host_skipped;
+  return 0;
+}
+
+int mx_kv_pack_probe(int device, int dir, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx,
+                     int n_entries, const mx_kv_pack* entries, void* kcache, void* vcache, void* packed,
+                     uint64_t packed_bytes) {
+  // as mx_kv_copy_probe: the geometry is checked here, the table by the launchers, before anything is launched
+  if (!entries || !kcache || !vcache || !packed)
+    return fail(MX_ERR_ARG, "mx_kv_pack_probe: non-null entries / caches / packed");
+  if (dir != 0 && dir != 1) return fail(MX_ERR_ARG, "mx_kv_pack_probe: dir 0 (pack) or 1 (unpack)");
+  if (n_layer < 1 || n_layer > 256 || n_slots < 1 || n_slots > 4096 || n_head_kv < 1 || n_head_kv > 64 ||
+      (head_dim != 64 && head_dim != 128) || n_ctx < 1 || n_ctx > (1 << 20))
+    return fail(MX_ERR_ARG, "mx_kv_pack_probe: n_layer 1..256, n_slots 1..4096, n_head_kv 1..64, head_dim 64 or 128, "
+                            "n_ctx 1..2^20");
+  if (n_entries < 1 || n_entries > 4096) return fail(MX_ERR_ARG, "mx_kv_pack_probe: 1 <= n_entries <= 4096");
+  if (packed_bytes < 16 || packed_bytes % 16 || packed_bytes > ((uint64_t)1 << 30))
+    return fail(MX_ERR_ARG, "mx_kv_pack_probe: packed_bytes a multiple of 16, 16..2^30");
+  const int ctx_stride = (n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+  const size_t slot_stride = (size_t)n_head_kv * ctx_stride * head_dim, layer_kv_stride = slot_stride * n_slots;
+  const size_t cache_elems = layer_kv_stride * n_layer;
+  if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_kv_pack_probe: caches above 1 GiB each");
+  std::vector<KvPack> tab(n_entries);
+  for (int i = 0; i < n_entries; i++) {
+    if (entries[i].offset16 > ((uint64_t)1 << 40)) return fail(MX_ERR_ARG, "mx_kv_pack_probe: an offset past the buffer");
+    tab[i] = {entries[i].slot, entries[i].n_pos, (int64_t)entries[i].offset16};
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const size_t guard = dir == 0 ? MX_KV_PACK_GUARD_BYTES : 0;
+  DevBufs bufs;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  char* d_p = nullptr;
+  KvPack* d_tab = nullptr;
+  if (!bufs.alloc(&d_k, cache_elems * 2) || !bufs.alloc(&d_v, cache_elems * 2) ||
+      !bufs.alloc(&d_p, packed_bytes + guard) || !bufs.alloc(&d_tab, tab.size() * sizeof(KvPack)))
+    return fail(MX_ERR_HIP, "mx_kv_pack_probe: device allocation");
+  HIPC(hipMemcpy(d_k, kcache, cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_v, vcache, cache_elems * 2, hipMemcpyHostToDevice));
+  if (dir == 0) HIPC(hipMemset(d_p, 0xFF, packed_bytes + guard));
+  else HIPC(hipMemcpy(d_p, packed, packed_bytes, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(KvPack), hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  const int rc = dir == 0 ? launch_kv_pack(d_k, d_v, d_p, packed_bytes, tab.data(), d_tab, n_entries, n_layer, n_slots,
+                                           n_head_kv, head_dim, n_ctx, ctx_stride, slot_stride, layer_kv_stride, nullptr)
+                          : launch_kv_unpack(d_k, d_v, d_p, packed_bytes, tab.data(), d_tab, n_entries, n_layer,
+                                             n_slots, n_head_kv, head_dim, n_ctx, ctx_stride, slot_stride,
+                                             layer_kv_stride, nullptr);
+  if (rc)
+    return fail(MX_ERR_ARG, "mx_kv_pack_probe: the launcher refused the table (a slot out of range, n_pos outside "
+                            "[1, n_ctx], an offset off a tile, an entry past the buffer, overlapping packed ranges or a "
+                            "slot a destination twice)");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
+  if (dir == 0) HIPC(hipMemcpy(packed, d_p, packed_bytes + guard, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -478,6 +478,27 @@ int launch_kv_copy(_Float16* kc, _Float16* vc, const KvCopy* tab, const KvCopy* 
 // bytes the launch reads (= bytes it writes)
 size_t kv_copy_bytes(const KvCopy* tab, int n, int n_layer, int n_head_kv, int head_dim, int ctx_stride);
 
+// Host-RAM tier: the first P = min(ceil32(n_pos), ctx_stride) positions of slot `slot`, every
+// layer, K and V, to or from the packed form packed[t][layer][K|V][kv head][32 * D] f16, t = 0 .. P/32 - 1, that
+// starts at 16-byte word off16 of the packed buffer.  Each 32 * D block is the region's bytes [32t * D,
+// 32(t+1) * D) verbatim, so the first P' positions of an entry (P' a multiple of 32) are its first P'/32 tiles of
+// kv_pack_tile_bytes() each: one contiguous prefix.
+struct KvPack {
+  int32_t slot, n_pos;
+  int64_t off16;
+};
+size_t kv_pack_tile_bytes(int n_layer, int n_head_kv, int head_dim);
+// All entries of `tab` (host, n of them; tab_dev: its device copy, already enqueued on s) in one launch: slot ->
+// packed (pack) or packed -> slot (unpack).  Returns -1 and launches nothing unless 1 <= n, every slot is in
+// [0, n_slots), 1 <= n_pos <= n_ctx, every offset is a whole number of tiles, every entry ends inside the
+// packed_bytes of the buffer, no two packed ranges overlap and (unpack) no slot is a destination twice.
+int launch_kv_pack(const _Float16* kc, const _Float16* vc, void* packed, size_t packed_bytes, const KvPack* tab,
+                   const KvPack* tab_dev, int n, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx,
+                   int ctx_stride, size_t slot_stride, size_t layer_kv_stride, hipStream_t s);
+int launch_kv_unpack(_Float16* kc, _Float16* vc, const void* packed, size_t packed_bytes, const KvPack* tab,
+                     const KvPack* tab_dev, int n, int n_layer, int n_slots, int n_head_kv, int head_dim, int n_ctx,
+                     int ctx_stride, size_t slot_stride, size_t layer_kv_stride, hipStream_t s);
+
 // HBM streaming probes: variant v of probe_variants() (loads in flight, grid, non-temporal) of a
 // read-only (XOR fold) or copy stream over n16 16-byte words (n16 % 4096 == 0); desc describes it
 int probe_variants();

@@ -34,6 +34,7 @@ EXPORTS = [
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
+    "mx_engine_set_host_cache", "mx_host_cache_stats", "mx_kv_pack_probe",
     "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
 ]
 LOGIT_BIAS_MAX = 256  # kernels.h SAMP_BIAS_MAX: most logit_bias entries per request
@@ -120,6 +121,16 @@ class MxSharingStats(ctypes.Structure):
 
 class MxKvCopy(ctypes.Structure):
     _fields_ = [("src_slot", ctypes.c_int32), ("dst_slot", ctypes.c_int32), ("n_pos", ctypes.c_int32)]
+
+
+class MxHostCacheCounts(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in (
+        "entries", "bytes", "capacity_bytes", "spills", "spilled_bytes", "restores", "restored_prompt_tokens",
+        "restored_bytes", "evictions", "skipped")]
+
+
+class MxKvPack(ctypes.Structure):
+    _fields_ = [("slot", ctypes.c_int32), ("n_pos", ctypes.c_int32), ("offset16", ctypes.c_uint64)]
 
 
 class MxMatmulArgs(ctypes.Structure):
@@ -244,6 +255,9 @@ def lib() -> ctypes.CDLL:
         L.mx_engine_set_prefix_sharing.argtypes = [vp, i32]
         L.mx_prefix_sharing_stats.argtypes = [vp, P(MxSharingStats)]
         L.mx_kv_copy_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.mx_engine_set_host_cache.argtypes = [vp, ctypes.c_uint64]
+        L.mx_host_cache_stats.argtypes = [vp, P(MxHostCacheCounts)]
+        L.mx_kv_pack_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, ctypes.c_uint64]
         L.mx_sampling_ext_default.argtypes = [P(MxSamplingExt)]
         L.mx_submit_ext.argtypes = [vp, vp, i32, P(MxSamplingExt), i32, i32, i32, P(u64)]
         L.mx_submit_ext_batch.argtypes = [vp, i32, vp, vp, vp, vp, P(u64)]
@@ -454,6 +468,49 @@ def kv_copy_probe(n_layer: int, n_slots: int, n_head_kv: int, head_dim: int, n_c
     return kc, vc
 
 
+KV_PACK_GUARD_BYTES = 4096  # mx_engine.h MX_KV_PACK_GUARD_BYTES: 0xFF bytes behind a packed output
+
+
+def kv_pack_probe(direction: int, n_layer: int, n_slots: int, n_head_kv: int, head_dim: int, n_ctx: int, entries,
+                  kcache, vcache, packed=None, packed_bytes: int = 0, device: int = 0, inplace: bool = False):
+    """The host tier's pack (direction 0) and unpack (1) kernels on caller-supplied caches (no engine;
+    include/mx_engine.h mx_kv_pack_probe).  kcache / vcache as for kv_copy_probe; entries: [(slot, n_pos, offset in
+    16-byte words)].  Packing returns (packed bytes [packed_bytes + KV_PACK_GUARD_BYTES] uint8, kcache after, vcache
+    after): the buffer starts as 0xFF bytes.  Unpacking takes `packed` (uint8) and returns (kcache after, vcache
+    after).  With `inplace` the flat uint16 caches -- and, packing, a flat uint8 `packed` of packed_bytes +
+    KV_PACK_GUARD_BYTES -- are worked on directly (what a test of a refusal reads afterwards).  A refused table
+    raises MxError(MX_ERR_ARG)."""
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    elems = max(n_layer, 0) * max(n_slots, 0) * max(n_head_kv, 0) * ctx_stride * max(head_dim, 0)
+    if inplace:
+        kc, vc = kcache, vcache
+        if any(a.dtype != np.uint16 or a.ndim != 1 or not a.flags.c_contiguous for a in (kc, vc)):
+            raise ValueError("inplace takes flat contiguous uint16 arrays")
+    else:
+        kc = np.array(kcache, dtype=np.uint16, copy=True).reshape(-1)
+        vc = np.array(vcache, dtype=np.uint16, copy=True).reshape(-1)
+    if kc.size != elems or vc.size != elems:
+        raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+    if direction == 0:
+        if inplace and packed is not None:
+            pk = packed
+            if pk.dtype != np.uint8 or pk.ndim != 1 or not pk.flags.c_contiguous:
+                raise ValueError("inplace takes a flat contiguous uint8 packed buffer")
+        else:
+            pk = np.zeros(max(int(packed_bytes), 0) + KV_PACK_GUARD_BYTES, dtype=np.uint8)
+        if pk.size != packed_bytes + KV_PACK_GUARD_BYTES:
+            raise ValueError("the packed output holds packed_bytes + KV_PACK_GUARD_BYTES bytes")
+    else:
+        pk = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
+        packed_bytes = pk.size
+    tab = (MxKvPack * max(len(entries), 1))()
+    for i, (s, n, o) in enumerate(entries):
+        tab[i].slot, tab[i].n_pos, tab[i].offset16 = int(s), int(n), int(o)
+    _check(lib().mx_kv_pack_probe(device, int(direction), n_layer, n_slots, n_head_kv, head_dim, n_ctx, len(entries),
+                                  tab, kc.ctypes.data, vc.ctypes.data, pk.ctypes.data, int(packed_bytes)))
+    return (pk, kc, vc) if direction == 0 else (kc, vc)
+
+
 EPI_F32, EPI_RESID, EPI_QKV, EPI_SWIGLU = 0, 1, 2, 3  # kernels.h Epilogue
 PROBE_GUARD_ROWS = 64  # rows of 0xFF bytes the probes return after every output
 
@@ -660,10 +717,11 @@ class Engine:
     supports_embeddings = True  # embed(): what Llama(embedding=True).embed / create_embedding need
     supports_prefix_sharing = True  # set_prefix_sharing() / sharing_stats(): what Llama.set_cache needs
     supports_sampler_ext = True  # submit(typical_p=, tfs_z=, mirostat_*=, logit_bias=): the whole sampler chain
+    supports_host_cache = True  # set_host_cache() / host_cache_stats(): the host-RAM tier of Llama.set_cache
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
-                 handoff_bf16: bool = False, prefix_sharing: bool = False):
+                 handoff_bf16: bool = False, prefix_sharing: bool = False, host_cache_bytes: int = 0):
         L = lib()
         opts = MxOpts()
         L.mx_opts_default(ctypes.byref(opts))
@@ -683,6 +741,25 @@ class Engine:
         self.n_ctx = info.n_ctx
         if prefix_sharing:
             self.set_prefix_sharing(True)
+        if host_cache_bytes:
+            self.set_host_cache(host_cache_bytes)
+
+    def set_host_cache(self, capacity_bytes: int):
+        """The host-RAM tier behind the KV slots (off by default): slot records about to be
+        overwritten are kept in pinned host memory up to `capacity_bytes`, least recently used first out, and a
+        prompt that matches one gets its K/V back by a transfer instead of a prefill.  Lowering the capacity
+        evicts at once; 0 drops everything and switches the tier off.  A pipeline-stage engine raises
+        MxError(MX_ERR_STATE)."""
+        if capacity_bytes < 0:
+            raise ValueError("capacity_bytes must be >= 0")
+        _check(lib().mx_engine_set_host_cache(self._h, int(capacity_bytes)))
+
+    def host_cache_stats(self) -> dict:
+        """entries, bytes, capacity_bytes, spills, spilled_bytes, restores, restored_prompt_tokens, restored_bytes,
+        evictions, skipped (include/mx_engine.h mx_host_cache_counts)."""
+        st = MxHostCacheCounts()
+        _check(lib().mx_host_cache_stats(self._h, ctypes.byref(st)))
+        return {k: getattr(st, k) for k, _ in MxHostCacheCounts._fields_}
 
     def set_prefix_sharing(self, on: bool):
         """Share prompt prefixes across KV slots by device copies (off by default): from the next

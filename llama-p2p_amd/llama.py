@@ -146,8 +146,11 @@ class Llama:
         """llama-cpp-python's ``Llama.set_cache``: with a ``BaseLlamaCache`` (``LlamaRAMCache()``) later prompts
         start from the longest prefix whose K/V the engine already holds -- in any KV slot, free or busy, or being
         evaluated by another request of the same round -- copied between slots on the device (llama_cache.py,
-        DESIGN.md §12); ``None`` switches that off.  The object is kept in ``Llama.cache``; its ``capacity_bytes``
-        is not used (the cache is the device's KV slots).  ``LlamaDiskCache``, and an engine front without
+        DESIGN.md §12); ``None`` switches that off.  On an engine with ``supports_host_cache`` the cache's
+        ``capacity_bytes`` becomes the budget of the host-RAM tier behind the slots: the K/V of a
+        slot that is about to be overwritten are kept in pinned host memory and come back by a transfer when a
+        later prompt matches them; ``cache.cache_size`` then reports the bytes held, and ``None`` empties the
+        tier.  The object is kept in ``Llama.cache``.  ``LlamaDiskCache``, and an engine front without
         ``supports_prefix_sharing`` (the pipeline server's), raise ``NotImplementedError``."""
         if cache is not None and not isinstance(cache, BaseLlamaCache):
             raise TypeError("set_cache takes a BaseLlamaCache (LlamaRAMCache()) or None")
@@ -156,6 +159,12 @@ class Llama:
         if not getattr(self._engine, "supports_prefix_sharing", False):
             raise NotImplementedError("this engine front has no prefix sharing (the pipeline server)")
         self._engine.set_prefix_sharing(cache is not None)
+        if getattr(self._engine, "supports_host_cache", False):
+            self._engine.set_host_cache(cache.capacity_bytes if cache is not None else 0)
+            if self.cache is not None:
+                self.cache._bind(None)
+            if cache is not None:
+                cache._bind(self._engine)
         self.cache = cache
 
     # ---------------------------------------------------------------- info

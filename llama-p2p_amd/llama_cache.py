@@ -6,13 +6,16 @@ llama_cpp is not installed here, so the contract is pinned as read from its 0.3 
 capacity_bytes=2 << 30)``, ``LlamaRAMCache(capacity_bytes=2 << 30)``, ``LlamaCache = LlamaRAMCache`` and
 ``LlamaDiskCache(cache_dir=".cache/llama_cache", capacity_bytes=2 << 30)``.
 
-Here the cache is the device's own KV slots: ``Llama.set_cache`` with a ``BaseLlamaCache``
-switches the engine's prefix sharing on -- a prompt whose prefix any slot holds, or another request of the same
-round evaluates, receives those positions by a device copy -- and ``None`` switches it off.  Nothing is kept
-in host RAM, so ``capacity_bytes`` is accepted and not used: the capacity is the engine's ``n_seq_max`` slots of
-``n_ctx`` positions, reused in the scheduler's order.  ``LlamaDiskCache`` raises ``NotImplementedError`` (when
-constructed, and in ``set_cache``): no state leaves the device.  The classes hold no ``LlamaState``; indexing one raises
-``KeyError`` as an empty upstream cache does.
+Here the cache is the device's own KV slots with a host-RAM tier behind them (§14):
+``Llama.set_cache`` with a ``BaseLlamaCache`` switches the engine's prefix sharing on -- a prompt whose prefix any
+slot holds, or another request of the same round evaluates, receives those positions by a device copy -- and
+``None`` switches it off.  ``capacity_bytes`` is the budget of the host tier: when a slot is handed to a prompt
+that does not match what it holds, its K/V first go to pinned host memory, least recently used entries leaving
+when the budget is full, and a later prompt that matches an entry gets those positions back by one transfer
+instead of a prefill.  ``cache_size`` is the host bytes held by the engine the cache is bound to (0 for a cache no
+``Llama`` uses).  ``LlamaDiskCache`` raises ``NotImplementedError`` (when constructed, and in ``set_cache``): no
+state goes to disk.  The classes hold no ``LlamaState``; indexing one raises ``KeyError`` as an empty upstream
+cache does.
 """
 from __future__ import annotations
 
@@ -24,10 +27,17 @@ class BaseLlamaCache:
 
     def __init__(self, capacity_bytes: int = (2 << 30)):
         self.capacity_bytes = capacity_bytes
+        self._engine = None
+
+    def _bind(self, engine) -> None:
+        """``Llama.set_cache``: the engine whose host tier this object stands for (None: none any more)."""
+        self._engine = engine
 
     @property
     def cache_size(self) -> int:
-        return 0  # host bytes held: the state lives in the device's KV slots
+        """Host bytes held for this cache: the engine's host tier; 0 while no ``Llama`` uses the object."""
+        eng = getattr(self, "_engine", None)
+        return int(eng.host_cache_stats()["bytes"]) if eng is not None else 0
 
     def __contains__(self, key: Sequence[int]) -> bool:
         return False
@@ -40,7 +50,8 @@ class BaseLlamaCache:
 
 
 class LlamaRAMCache(BaseLlamaCache):
-    """``Llama.set_cache(LlamaRAMCache())``: prefix sharing across the engine's KV slots."""
+    """``Llama.set_cache(LlamaRAMCache(capacity_bytes))``: prefix sharing across the engine's KV slots, and up to
+    ``capacity_bytes`` of evicted slots' K/V kept in host RAM."""
 
     def __init__(self, capacity_bytes: int = (2 << 30)):
         super().__init__(capacity_bytes)
