@@ -425,6 +425,77 @@ int mx_matmul_probe(int device, const mx_matmul_args* a);
  * *norm_on_load_ok = mm_can_norm_on_load(M, K), *gemm_ok = gemm_supported(N, K).  Any pointer may be NULL. */
 int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers_ok, int32_t* norm_on_load_ok,
                    int32_t* gemm_ok);
+/* The production Q8_0 / Q4_0 launchers on caller-supplied operands, no engine.
+ * path 0 launch_mq8 (whatever it dispatches, M 1..4096); path 1 launch_mq8_slab (17..32 rows, RESID or QKV)
+ * finished as the engine finishes it: RESID slabs folded by the next launch_rmsnorm_q8 (weights fold_w [N]; out
+ * receives x, nxq_out / nxd_out that norm's Q8_0 rows [M + 64][N] / [M + 64][N/32]), QKV slabs by
+ * launch_qkv_finish; path -1: the activation step alone (no weights, no matmul).
+ * w: raw GGUF blocks, row-major [N][K/32]: Q8_0 (34 bytes) or, wq4 = 1, Q4_0 (18 bytes); N % 16, K % 64; SWIGLU:
+ * rows [0, N/2) ffn_gate, [N/2, N) ffn_up.  Packed on the device with launch_pack_q8 / launch_pack_q4 as at model
+ * load (packed_out, optional, receives the packed bytes).
+ * Activations (act), from f32 rows xf as enqueue_forward_q8's operand makes them: 0 launch_quantize_q8 of xf
+ * [M][ldx] (ldx >= K, 0 = K); 1 launch_rmsnorm_q8 of xf [xrows][K] with norm_w [K], eps, optional row_map [M]
+ * (entries in [0, xrows); without it xrows = M) or fold_slabs [nslab][xrows][K], nslab 0..8, folded into x first
+ * (x_out, optional, receives the folded rows); 2 quantise on load (path 0, mq8_can_quantize_on_load(M, K, norm)):
+ * xf [M][K], optional norm_w with the sum-of-squares partials from launch_ssq.  Device rows past the caller's hold
+ * 0xFF bytes (f32 NaN).  xq_out [M + 64][K] (int8, in q8_perm order) and xd_out [M + 64][K/32] (optional) receive
+ * the device's Q8_0 rows of acts 0 / 1, rows >= M still 0xFF.
+ * out: [M + 64][ld] f32, filled with 0xFF bytes before any launch (rows >= M: a guard): F32 ld N; RESID ld N,
+ * rows < M start as resid; SWIGLU ld N/2, act_f32 must be set (Q8_0 models use the f32 act; without it the
+ * launcher refuses); QKV as mx_matmul_probe.  ssq_out (want_ssq: RESID, path 0): the partials, [M + 64][N/16], rows
+ * >= M a guard that starts as 0xFF.
+ * slabs_out (path 1, slabs_cap >= 8 * M * N floats): the raw partials [ks][M][N]; *split_out: the launcher's
+ * return (ks).  Everything a kernel indexes with is checked before any launch (MX_ERR_ARG, nothing launched); a
+ * launcher that refuses the shape gives MX_ERR_ARG with its name in mx_last_error(). */
+typedef struct {
+  int32_t path, epi, M, N, K, wq4, act;
+  const void* w;
+  const float* xf;
+  int32_t xrows, ldx;
+  const float* norm_w;
+  float eps;
+  const int32_t* row_map;
+  const float* fold_slabs;
+  int32_t nslab;
+  int32_t want_ssq, act_f32;
+  int32_t n_head, n_head_kv, head_dim, n_ctx, n_slots;
+  const int32_t* pos;
+  const int32_t* slot;
+  const float* rope_cs;
+  void* kcache;
+  void* vcache;
+  const float* resid;
+  const float* fold_w;
+  void* out;
+  float* ssq_out;
+  float* slabs_out;
+  uint64_t slabs_cap;
+  int32_t* split_out;
+  void* packed_out;
+  void* xq_out;
+  float* xd_out;
+  float* x_out;
+  void* nxq_out;
+  float* nxd_out;
+  int32_t np; /* leave 0 (np = K / 16, the only value launch_mq8 accepts).  A test hook, not an operand: with act 2 and
+                 norm_w, a multiple of 4 in [4, K / 16) is handed to launch_mq8 as MMArgs.np to show that it refuses
+                 np * 16 != K; no kernel ever runs with it */
+} mx_q8_matmul_args;
+int mx_q8_matmul_probe(int device, const mx_q8_matmul_args* a);
+/* The kernel a Q8_0 / Q4_0 shape reaches, no GPU needed (the launchers dispatch on the same host functions).
+ * kind: 0 launch_mq8 refuses, 1 mq8_kernel quantising on load (qp, qm, bd), 2 mq8_pers_ql_kernel (tpw), 3
+ * mq8_kernel<ks, rt, nb> (bd: the block-diagonal one-token form; grid_y), 4 mq8_wide_kernel<w>, 5
+ * mq8_wsw_kernel<w>, 6 q8gemm_kernel (grid).  slab_ks: launch_mq8_slab's split for pre-quantised rows, -1 = it
+ * refuses.  can_on_load: mq8_can_quantize_on_load(M, K, norm). */
+typedef struct {
+  int32_t kind, qp, qm, tpw, ks, rt, nb, bd, grid_y, w, grid, slab_ks, can_on_load;
+} mx_q8_plan;
+int mx_q8_matmul_plan(int epi, int M, int N, int K, int wq4, int on_load, int norm, mx_q8_plan* out);
+/* mode 0 launch_dequant_q8_tiles: Q8_0 blocks [N][K/32] (N % 16) packed as at load -> packed bf16 tiles, out
+ * [(N + 64) * K] uint16; mode 1 launch_embed_q8: rows ids [M] (in [0, N)) of the blocks -> out f32 [M + 64][K]
+ * and, optionally, ssq_out [M + 64][K/16].  Outputs start as 0xFF bytes. */
+int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, const int32_t* ids, int M, void* out,
+                     float* ssq_out);
 /* launch_resid_norm (row_map NULL) / launch_rmsnorm (row_map given, nslab 0) on caller-supplied rows, no
  * engine.  x f32 [rows][n] (n % 64, n <= 16384, rows 1..4096); slabs [nslab][rows][n] (0 <= nslab <= 16) are
  * folded into x in slab order; w f32 [n] (optional): y = bf16(rmsnorm(x, eps) * w) [M][n]; row_map [M] (entries

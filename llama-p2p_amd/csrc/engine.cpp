@@ -3747,6 +3747,7 @@ struct DevBufs {  // device allocations of a probe call, freed on every return p
   }
 };
 constexpr int PROBE_GUARD_ROWS = 64;  // rows of 0xFF after every probe output, returned to the caller
+constexpr int XQ_ON_LOAD_ROWS = 4;    // f32 source rows of a quantise-on-load GEMV (its QM = 4 image)
 }  // namespace
 
 int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers_ok, int32_t* norm_on_load_ok,
@@ -4007,6 +4008,289 @@ int mx_norm_probe(int device, int rows, int n, int M, const float* x, const floa
   HIPC(hipDeviceSynchronize());
   HIPC(hipMemcpy(x_out, d_x, xb, hipMemcpyDeviceToHost));
   if (w) HIPC(hipMemcpy(y_out, d_y, yb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mx_q8_matmul_plan(int epi, int M, int N, int K, int wq4, int on_load, int norm, mx_q8_plan* out) {
+  if (!out) return fail(MX_ERR_ARG, "mx_q8_matmul_plan: null plan");
+  if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || N < TILE_N || N % TILE_N || K < Q8_TILE_K || K % Q8_TILE_K)
+    return fail(MX_ERR_ARG, "mx_q8_matmul_plan: epi 0..3, M >= 1, N a multiple of 16, K a multiple of 64");
+  const Mq8Plan p = mq8_plan(epi, M, N, K, wq4 != 0, on_load != 0, norm != 0);
+  *out = mx_q8_plan{p.kind, p.qp, p.qm, p.tpw, p.ks, p.rt, p.nb, p.bd, p.grid_y, p.w, p.grid,
+                    on_load ? -1 : mq8_slab_ks(M, N, K), mq8_can_quantize_on_load(M, K, norm != 0) ? 1 : 0};
+  return 0;
+}
+
+int mx_q8_matmul_probe(int device, const mx_q8_matmul_args* pa) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (!pa) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: null arguments");
+  const mx_q8_matmul_args& p = *pa;
+  const int path = p.path, epi = p.epi, M = p.M, N = p.N, K = p.K, act = p.act;
+  const bool mm = path >= 0;  // path -1: quantise only
+  if (path < -1 || path > 1 || act < 0 || act > 2 || (p.wq4 != 0 && p.wq4 != 1))
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: path -1..1, act 0..2, wq4 0 / 1");
+  if (mm && (epi < EPI_F32 || epi > EPI_SWIGLU)) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: epi 0..3");
+  if (K < Q8_TILE_K || K % Q8_TILE_K || K > 32768)
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: K a multiple of 64, <= 32768");
+  if (mm && (N < TILE_N || N % TILE_N || N > (1 << 18) || (size_t)N * K > ((size_t)1 << 30) || !p.w || !p.out))
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: N a multiple of 16 (<= 2^18), N*K <= 2^30, w and out required");
+  if (mm && epi == EPI_SWIGLU && N % 32) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: SWIGLU: N a multiple of 32");
+  if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: 1 <= M <= PREFILL_ROWS rows");
+  if (path == 1 && (M <= 16 || M > 32 || act == 2 || (epi != EPI_RESID && epi != EPI_QKV)))
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: path 1 (slabs): 17..32 pre-quantised rows, RESID or QKV");
+  if (!p.xf) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: xf is required");
+  int xrows = M, ldx = K;
+  if (act == 0) {
+    ldx = p.ldx ? p.ldx : K;
+    if (ldx < K || ldx % 4 || ldx > 65536) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 0: K <= ldx <= 65536, ldx % 4 == 0");
+    if (p.norm_w || p.row_map || p.nslab) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 0 takes no norm_w / row_map / slabs");
+  } else if (act == 1) {
+    xrows = p.xrows ? p.xrows : M;
+    if (!p.norm_w || xrows < 1 || xrows > PREFILL_ROWS || (p.ldx && p.ldx != K))
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 1: norm_w given, 1 <= xrows <= PREFILL_ROWS, ldx = K");
+    if (p.nslab < 0 || p.nslab > 8 || (p.nslab > 0 && (!p.fold_slabs || p.row_map || K > 16384)))
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 1: nslab 0..8 with fold_slabs, no row_map, K <= 16384");
+    if (p.row_map) {
+      for (int i = 0; i < M; i++)
+        if (p.row_map[i] < 0 || p.row_map[i] >= xrows) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: row_map entry out of range");
+    } else if (xrows != M) {
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 1 without row_map: xrows = M");
+    }
+  } else {
+    if (path != 0 || p.row_map || p.nslab || (p.ldx && p.ldx != K))
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: act 2 (quantise on load): path 0, no row_map / slabs, ldx = K");
+    if (!mq8_can_quantize_on_load(M, K, p.norm_w != nullptr))
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: mq8_can_quantize_on_load refuses M / K");
+  }
+  if (p.np && (act != 2 || !p.norm_w || p.np < 4 || p.np % 4 || p.np * 16 >= K))
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: np: act 2 with norm_w, a multiple of 4 in [4, K / 16)");
+  if (p.want_ssq && (!mm || epi != EPI_RESID || path != 0 || !p.ssq_out || (act == 2 && p.norm_w)))
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: want_ssq: RESID on path 0, with ssq_out, no norm on load");
+  if (mm && epi == EPI_RESID) {
+    if (!p.resid) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: RESID takes resid [M][N]");
+    if (path == 1 && (!p.fold_w || N % 64 || N > 16384))
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: RESID slabs: fold_w [N], N a multiple of 64, <= 16384");
+  }
+  int n_q = 0, n_kv = 0, ctx_stride = 0;
+  size_t slot_stride = 0, cache_elems = 0;
+  if (mm && epi == EPI_QKV) {
+    if (!p.pos || !p.slot || !p.rope_cs || !p.kcache || !p.vcache)
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: QKV takes pos, slot, rope_cs and both caches");
+    if ((p.head_dim != 64 && p.head_dim != 128) || p.n_head < 1 || p.n_head_kv < 1 || p.n_head > 1024 ||
+        p.n_head_kv > 1024 || (long long)(p.n_head + 2 * p.n_head_kv) * p.head_dim != N)
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: head_dim 64 or 128, N = (n_head + 2 n_head_kv) * head_dim");
+    if (p.n_ctx < 1 || p.n_ctx > (1 << 20) || p.n_slots < 1 || p.n_slots > 4096)
+      return fail(MX_ERR_ARG, "mx_q8_matmul_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+    n_q = p.n_head * p.head_dim;
+    n_kv = p.n_head_kv * p.head_dim;
+    ctx_stride = (p.n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+    slot_stride = (size_t)p.n_head_kv * ctx_stride * p.head_dim;
+    cache_elems = slot_stride * p.n_slots;
+    if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: caches above 1 GiB each");
+    for (int i = 0; i < M; i++) {
+      if (p.slot[i] < 0 || p.slot[i] >= p.n_slots) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: slot out of range");
+      if (p.pos[i] < 0 || p.pos[i] > p.n_ctx) return fail(MX_ERR_ARG, "mx_q8_matmul_probe: position outside [0, n_ctx]");
+    }
+  }
+  const size_t slab_stride = (size_t)MAX_ROWS * (mm ? N : 0), slab_total = path == 1 ? slab_stride * 8 : 0;  // ks <= 8
+  if (path == 1 && p.slabs_out && p.slabs_cap < (uint64_t)8 * M * N)
+    return fail(MX_ERR_ARG, "mx_q8_matmul_probe: slabs_out holds fewer than 8 * M * N floats");
+  if (device >= 0) HIPC(hipSetDevice(device));
+
+  DevBufs dev;
+  const size_t bb = p.wq4 ? 18 : 34;
+  const size_t raw_bytes = mm ? (size_t)N * (K / 32) * bb : 0;
+  const size_t wbytes = mm ? (p.wq4 ? q4_matrix_bytes(N, K) : q8_matrix_bytes(N, K)) : 0;
+  uint8_t *d_src = nullptr, *d_w = nullptr, *d_out = nullptr;
+  float *d_xf = nullptr, *d_nw = nullptr, *d_ssq = nullptr, *d_slabs = nullptr, *d_cs = nullptr, *d_fs = nullptr;
+  float *d_xd = nullptr, *d_fw = nullptr, *d_nxd = nullptr;
+  int8_t *d_xq = nullptr, *d_nxq = nullptr;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr, *d_map = nullptr;
+  const int ld = !mm ? 0 : epi == EPI_SWIGLU ? N / 2 : epi == EPI_QKV ? n_q : N;
+  const size_t out_bytes = (size_t)(M + PROBE_GUARD_ROWS) * ld * 4;
+  const int xalloc = (act == 2 ? XQ_ON_LOAD_ROWS : xrows) + 16;  // f32 source rows; those past the caller's are NaN
+  const size_t xf_bytes = (size_t)xalloc * ldx * 4;
+  const int qrows = (M + 127) / 128 * 128 + PROBE_GUARD_ROWS;  // Q8_0 rows; those past M stay 0xFF (d_x NaN)
+  const size_t xq_bytes = (size_t)qrows * K, xd_bytes = (size_t)qrows * (K / 32) * 4;
+  const bool nol = act == 2 && p.norm_w;
+  const int np = nol ? K / 16 : N / 16;
+  const size_t ssq_bytes = (size_t)(nol ? XQ_ON_LOAD_ROWS : M + PROBE_GUARD_ROWS) * np * 4;
+  const size_t fs_stride = (size_t)xrows * K;
+  if (!dev.alloc(&d_xf, xf_bytes) || !dev.alloc(&d_xq, xq_bytes) || !dev.alloc(&d_xd, xd_bytes) ||
+      (p.norm_w && !dev.alloc(&d_nw, (size_t)K * 4)) || (p.row_map && !dev.alloc(&d_map, (size_t)M * 4)) ||
+      (p.nslab && !dev.alloc(&d_fs, fs_stride * p.nslab * 4)))
+    return fail(MX_ERR_HIP, "mx_q8_matmul_probe: device allocation");
+  if (mm && (!dev.alloc(&d_src, raw_bytes) || !dev.alloc(&d_w, wbytes) || !dev.alloc(&d_out, out_bytes) ||
+             ((nol || p.want_ssq) && !dev.alloc(&d_ssq, ssq_bytes)) || (slab_total && !dev.alloc(&d_slabs, slab_total * 4))))
+    return fail(MX_ERR_HIP, "mx_q8_matmul_probe: device allocation");
+  if (path == 1 && epi == EPI_RESID &&
+      (!dev.alloc(&d_fw, (size_t)N * 4) || !dev.alloc(&d_nxq, (size_t)(M + PROBE_GUARD_ROWS) * N) ||
+       !dev.alloc(&d_nxd, (size_t)(M + PROBE_GUARD_ROWS) * (N / 32) * 4)))
+    return fail(MX_ERR_HIP, "mx_q8_matmul_probe: device allocation");
+  if (mm && epi == EPI_QKV &&
+      (!dev.alloc(&d_k, cache_elems * 2) || !dev.alloc(&d_v, cache_elems * 2) || !dev.alloc(&d_pos, (size_t)M * 4) ||
+       !dev.alloc(&d_slot, (size_t)M * 4) || !dev.alloc(&d_cs, (size_t)p.n_ctx * p.head_dim * 4)))
+    return fail(MX_ERR_HIP, "mx_q8_matmul_probe: device allocation");
+
+  MMArgs a{};
+  if (mm) {  // weights: packed on the device exactly as at model load
+    HIPC(hipMemcpy(d_src, p.w, raw_bytes, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_w, 0xFF, wbytes));
+    auto pack = p.wq4 ? launch_pack_q4 : launch_pack_q8;
+    if (epi == EPI_SWIGLU) {
+      pack(d_w, d_src, N / 2, K, PACK_GATE, 0, nullptr);
+      pack(d_w, d_src + (size_t)(N / 2) * (K / 32) * bb, N / 2, K, PACK_UP, 0, nullptr);
+    } else {
+      pack(d_w, d_src, N, K, PACK_ROWS, 0, nullptr);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemset(d_out, 0xFF, out_bytes));
+    if (epi == EPI_RESID) HIPC(hipMemcpy(d_out, p.resid, (size_t)M * N * 4, hipMemcpyHostToDevice));
+    if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, ssq_bytes));
+    if (d_slabs) HIPC(hipMemset(d_slabs, 0xFF, slab_total * 4));
+    a.W = reinterpret_cast<const uint16_t*>(d_w); a.N = N; a.K = K; a.M = M; a.eps = p.eps; a.wq4 = p.wq4;
+  }
+  HIPC(hipMemset(d_xf, 0xFF, xf_bytes));
+  HIPC(hipMemcpy(d_xf, p.xf, (size_t)(act == 2 ? M : xrows) * ldx * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_xq, 0xFF, xq_bytes));
+  HIPC(hipMemset(d_xd, 0xFF, xd_bytes));
+  if (p.norm_w) HIPC(hipMemcpy(d_nw, p.norm_w, (size_t)K * 4, hipMemcpyHostToDevice));
+  if (p.row_map) HIPC(hipMemcpy(d_map, p.row_map, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (p.nslab) HIPC(hipMemcpy(d_fs, p.fold_slabs, fs_stride * p.nslab * 4, hipMemcpyHostToDevice));
+  if (d_fw) {
+    HIPC(hipMemcpy(d_fw, p.fold_w, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_nxq, 0xFF, (size_t)(M + PROBE_GUARD_ROWS) * N));
+    HIPC(hipMemset(d_nxd, 0xFF, (size_t)(M + PROBE_GUARD_ROWS) * (N / 32) * 4));
+  }
+  if (mm && epi == EPI_QKV) {
+    HIPC(hipMemcpy(d_k, p.kcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_v, p.vcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_pos, p.pos, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_slot, p.slot, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_cs, p.rope_cs, (size_t)p.n_ctx * p.head_dim * 4, hipMemcpyHostToDevice));
+    a.n_q = n_q; a.n_kv = n_kv; a.head_dim = p.head_dim; a.pos = d_pos; a.slot = d_slot; a.rope_cs = d_cs;
+    a.kc = d_k; a.vc = d_v; a.n_ctx = p.n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = p.n_head_kv;
+    a.slot_stride = slot_stride;
+  }
+  HIPC(hipDeviceSynchronize());
+
+  // the operand, as enqueue_forward_q8's `operand` makes it
+  if (act == 2) {
+    a.xq = nullptr; a.xf = d_xf; a.norm_w = d_nw; a.np = p.np ? p.np : K / 16;
+    if (nol) {
+      launch_ssq(d_xf, M, K, d_ssq, nullptr);  // the partials as the embedding / the residual writers leave them
+      a.ssq = d_ssq;
+    }
+  } else {
+    if (act == 1) launch_rmsnorm_q8(d_xq, d_xd, d_xf, d_nw, d_map, M, K, p.eps, nullptr, d_fs, p.nslab, fs_stride);
+    else launch_quantize_q8(d_xq, d_xd, d_xf, ldx, M, K, nullptr);
+    HIPC(hipGetLastError());
+    a.xq = d_xq; a.xd = d_xd;
+  }
+  if (mm) {
+    if (epi == EPI_SWIGLU) {
+      if (p.act_f32) a.actf = (float*)d_out;
+      a.lda = ld;
+    } else {
+      a.out = (float*)d_out; a.ldo = ld;
+    }
+    if (p.want_ssq) a.ssq = d_ssq, a.np = np;
+  }
+  int rc = 0;
+  const char* who = "";
+  std::vector<float> slab_host;  // the raw partials, taken before anything folds or finishes them
+  if (path == 0) {
+    who = "launch_mq8";
+    rc = launch_mq8(epi, a, nullptr);
+  } else if (path == 1) {
+    who = "launch_mq8_slab";
+    rc = launch_mq8_slab(a, d_slabs, slab_stride, nullptr);
+    if (rc > 8) {
+      hipDeviceSynchronize();
+      return fail(MX_ERR_STATE, "launch_mq8_slab split " + std::to_string(rc) + " above 8");
+    }
+    if (rc > 0) {
+      if (p.slabs_out) {
+        HIPC(hipDeviceSynchronize());
+        slab_host.resize((size_t)rc * M * N);
+        for (int k = 0; k < rc; k++)
+          HIPC(hipMemcpy(slab_host.data() + (size_t)k * M * N, d_slabs + k * slab_stride, (size_t)M * N * 4,
+                         hipMemcpyDeviceToHost));
+      }
+      if (epi == EPI_QKV) launch_qkv_finish(a, d_slabs, rc, slab_stride, nullptr);
+      else launch_rmsnorm_q8(d_nxq, d_nxd, (float*)d_out, d_fw, nullptr, M, N, p.eps, nullptr, d_slabs, rc, slab_stride);
+    }
+  }
+  if (rc < 0) {
+    hipDeviceSynchronize();
+    return fail(MX_ERR_ARG, std::string("mx_q8_matmul_probe: ") + who + " refused the shape");
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (mm) HIPC(hipMemcpy(p.out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  if (p.want_ssq) HIPC(hipMemcpy(p.ssq_out, d_ssq, (size_t)(M + PROBE_GUARD_ROWS) * np * 4, hipMemcpyDeviceToHost));
+  if (p.slabs_out && !slab_host.empty()) memcpy(p.slabs_out, slab_host.data(), slab_host.size() * 4);
+  if (p.split_out) *p.split_out = rc;
+  if (p.packed_out && mm) HIPC(hipMemcpy(p.packed_out, d_w, wbytes, hipMemcpyDeviceToHost));
+  if (p.xq_out) HIPC(hipMemcpy(p.xq_out, d_xq, (size_t)(M + PROBE_GUARD_ROWS) * K, hipMemcpyDeviceToHost));
+  if (p.xd_out) HIPC(hipMemcpy(p.xd_out, d_xd, (size_t)(M + PROBE_GUARD_ROWS) * (K / 32) * 4, hipMemcpyDeviceToHost));
+  if (p.x_out) HIPC(hipMemcpy(p.x_out, d_xf, (size_t)xrows * ldx * 4, hipMemcpyDeviceToHost));
+  if (p.nxq_out && d_nxq) HIPC(hipMemcpy(p.nxq_out, d_nxq, (size_t)(M + PROBE_GUARD_ROWS) * N, hipMemcpyDeviceToHost));
+  if (p.nxd_out && d_nxd)
+    HIPC(hipMemcpy(p.nxd_out, d_nxd, (size_t)(M + PROBE_GUARD_ROWS) * (N / 32) * 4, hipMemcpyDeviceToHost));
+  if (mm && epi == EPI_QKV) {
+    HIPC(hipMemcpy(p.kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(p.vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, const int32_t* ids, int M, void* out,
+                     float* ssq_out) {
+  if (mode < 0 || mode > 1 || !blocks || !out) return fail(MX_ERR_ARG, "mx_q8_side_probe: mode 0 / 1, blocks and out required");
+  if (N < 1 || N > (1 << 18) || K < Q8_TILE_K || K % Q8_TILE_K || K > 32768 || (size_t)N * K > ((size_t)1 << 28))
+    return fail(MX_ERR_ARG, "mx_q8_side_probe: 1 <= N <= 2^18, K a multiple of 64 (<= 32768), N*K <= 2^28");
+  if (mode == 0 && N % TILE_N) return fail(MX_ERR_ARG, "mx_q8_side_probe: mode 0: N a multiple of 16");
+  if (mode == 1) {
+    if (!ids || M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_q8_side_probe: mode 1: ids [M], 1 <= M <= PREFILL_ROWS");
+    for (int i = 0; i < M; i++)
+      if (ids[i] < 0 || ids[i] >= N) return fail(MX_ERR_ARG, "mx_q8_side_probe: id out of range");
+  }
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  uint8_t *d_src = nullptr, *d_w = nullptr, *d_out = nullptr;
+  float* d_ssq = nullptr;
+  int* d_ids = nullptr;
+  const size_t raw = (size_t)N * (K / 32) * 34;
+  if (!dev.alloc(&d_src, raw)) return fail(MX_ERR_HIP, "mx_q8_side_probe: device allocation");
+  HIPC(hipMemcpy(d_src, blocks, raw, hipMemcpyHostToDevice));
+  if (mode == 0) {  // packed Q8 tiles -> packed bf16 tiles
+    const size_t ob = (size_t)(N + PROBE_GUARD_ROWS) * K * 2;
+    if (!dev.alloc(&d_w, q8_matrix_bytes(N, K)) || !dev.alloc(&d_out, ob)) return fail(MX_ERR_HIP, "mx_q8_side_probe: device allocation");
+    HIPC(hipMemset(d_w, 0xFF, q8_matrix_bytes(N, K)));
+    HIPC(hipMemset(d_out, 0xFF, ob));
+    launch_pack_q8(d_w, d_src, N, K, PACK_ROWS, 0, nullptr);
+    if (launch_dequant_q8_tiles((uint16_t*)d_out, d_w, N, K, nullptr)) {
+      hipDeviceSynchronize();
+      return fail(MX_ERR_ARG, "mx_q8_side_probe: launch_dequant_q8_tiles refused the shape");
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  const size_t ob = (size_t)(M + PROBE_GUARD_ROWS) * K * 4, sb = (size_t)(M + PROBE_GUARD_ROWS) * (K / 16) * 4;
+  if (!dev.alloc(&d_out, ob) || !dev.alloc(&d_ids, (size_t)M * 4) || (ssq_out && !dev.alloc(&d_ssq, sb)))
+    return fail(MX_ERR_HIP, "mx_q8_side_probe: device allocation");
+  HIPC(hipMemset(d_out, 0xFF, ob));
+  if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, sb));
+  HIPC(hipMemcpy(d_ids, ids, (size_t)M * 4, hipMemcpyHostToDevice));
+  launch_embed_q8((float*)d_out, d_src, d_ids, M, K, d_ssq, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost));
+  if (ssq_out) HIPC(hipMemcpy(ssq_out, d_ssq, sb, hipMemcpyDeviceToHost));
   return 0;
 }
 

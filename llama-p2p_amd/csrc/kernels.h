@@ -213,6 +213,23 @@ int launch_mq8(int epi, const MMArgs& a, hipStream_t s);
 // ffn_down) or the attention / launch_qkv_finish to finish (q|k|v); ks, or -1 (use launch_mq8)
 int launch_mq8_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s);
 bool mq8_can_quantize_on_load(int M, int K, bool norm);
+// The kernel launch_mq8 reaches for a shape (a pure host function: launch_mq8 dispatches on its result).
+// on_load: a.xq == nullptr; norm: a.norm_w given.  kind MQ8_NONE: launch_mq8 refuses the shape.
+enum Mq8Kind : int {
+  MQ8_NONE = 0,
+  MQ8_QL = 1,       // mq8_kernel quantising on load: qp (float4 per lane and row), qm (row slots), bd (M == 1)
+  MQ8_PERS_QL = 2,  // mq8_pers_ql_kernel: tpw tiles per work-group
+  MQ8_GEMV = 3,     // mq8_kernel<ks, rt, nb> on Q8_0 rows, bd = the block-diagonal one-token form, grid_y
+  MQ8_WIDE = 4,     // mq8_wide_kernel<w> (Q8_0 weights)
+  MQ8_WSW = 5,      // mq8_wsw_kernel<w> (Q4_0 weights)
+  MQ8_GEMM = 6,     // q8gemm_kernel on `grid` work-groups
+};
+struct Mq8Plan {
+  int kind, qp, qm, tpw, ks, rt, nb, bd, grid_y, w, grid;
+};
+Mq8Plan mq8_plan(int epi, int M, int N, int K, bool wq4, bool on_load, bool norm);
+// split of launch_mq8_slab for a shape, -1 = it refuses (the conditions on the shape alone)
+int mq8_slab_ks(int M, int N, int K);
 
 // ---- K-quant weights (GGUF Q4_K 12, Q5_K 13, Q6_K 14), kquant.hip.  Packed tile =
 // 16 rows x 256 k (one super-block per row) in MFMA operand lane order: kq_tile_bytes(type) bytes

@@ -3460,9 +3460,9 @@ static void launch_mq8_ql(const MMArgs& a, hipStream_t s) {
 }
 
 template <int EPI, int QP, bool Q4>
-static void launch_mq8_ql_m(const MMArgs& a, hipStream_t s) {
-  if (a.M == 1) launch_mq8_ql<EPI, QP, 1, Q4>(a, s);
-  else if (a.M == 2) launch_mq8_ql<EPI, QP, 2, Q4>(a, s);
+static void launch_mq8_ql_m(const MMArgs& a, int qm, hipStream_t s) {
+  if (qm == 1) launch_mq8_ql<EPI, QP, 1, Q4>(a, s);
+  else if (qm == 2) launch_mq8_ql<EPI, QP, 2, Q4>(a, s);
   else launch_mq8_ql<EPI, QP, 4, Q4>(a, s);
 }
 
@@ -3588,40 +3588,66 @@ bool mq8_can_quantize_on_load(int M, int K, bool norm) {
 // <= 16 tokens: 8 waves split K, one row tile each (tools/gpu/q8_probe.sh); 17..32 tokens: per
 // epilogue, from tools/gpu/q8_probe32.sh (Llama-3-8B, 32 rows): more row tiles per wave for the wide
 // matrices (each B fragment loaded from L2 feeds RT MFMAs), one for the 4096-row ones; more: 4 tiles
+// (the shapes' configurations: mq8_gemv_cfg)
+struct Mq8Cfg {
+  int ks, rt, nb, bd;
+};
+static Mq8Cfg mq8_gemv_cfg(int epi, int M, int ntiles) {
+  if (M == 1) return {8, 1, 1, 1};
+  if (M <= 16) return {8, 1, 1, 0};
+  if (M <= 32) {
+    const int cfg = ntiles % 4 ? 0 : epi == EPI_QKV ? 1 : (epi == EPI_SWIGLU || epi == EPI_F32) ? 3 : 0;
+    if (cfg == 1) return {8, 2, 2, 0};
+    if (cfg == 3) return {4, 4, 2, 0};
+    return {8, 1, 2, 0};
+  }
+  return {8, 1, 4, 0};
+}
+
 template <int EPI, bool Q4>
-static int launch_mq8_epi(const MMArgs& a, hipStream_t s) {
+static int launch_mq8_epi(const MMArgs& a, const Mq8Plan& p, hipStream_t s) {
   const int ntiles = a.N / TILE_N;
-  if (a.M == 1) {
+  if (p.bd) {
     mq8_kernel<8, 1, 1, EPI, 4, 0, 1, Q4, true><<<dim3(ntiles, 1), 512, 0, s>>>(a);
-  } else if (a.M <= 16) {
+  } else if (p.nb == 1) {
     mq8_kernel<8, 1, 1, EPI, 4, 0, 1, Q4><<<dim3(ntiles, 1), 512, 0, s>>>(a);
-  } else if (a.M <= 32) {
-    const int cfg = ntiles % 4 ? 0 : EPI == EPI_QKV ? 1 : (EPI == EPI_SWIGLU || EPI == EPI_F32) ? 3 : 0;
-    if (cfg == 1) mq8_kernel<8, 2, 2, EPI, 2, 0, 1, Q4><<<dim3(ntiles / 2, 1), 512, 0, s>>>(a);
-    else if (cfg == 3) mq8_kernel<4, 4, 2, EPI, 2, 0, 1, Q4><<<dim3(ntiles / 4, 1), 256, 0, s>>>(a);
+  } else if (p.nb == 2) {
+    if (p.rt == 2) mq8_kernel<8, 2, 2, EPI, 2, 0, 1, Q4><<<dim3(ntiles / 2, 1), 512, 0, s>>>(a);
+    else if (p.rt == 4) mq8_kernel<4, 4, 2, EPI, 2, 0, 1, Q4><<<dim3(ntiles / 4, 1), 256, 0, s>>>(a);
     else mq8_kernel<8, 1, 2, EPI, 4, 0, 1, Q4><<<dim3(ntiles, 1), 512, 0, s>>>(a);
   } else {
-    mq8_kernel<8, 1, 4, EPI, 2, 0, 1, Q4><<<dim3(ntiles, (a.M + 63) / 64), 512, 0, s>>>(a);
+    mq8_kernel<8, 1, 4, EPI, 2, 0, 1, Q4><<<dim3(ntiles, p.grid_y), 512, 0, s>>>(a);
   }
   return 0;
 }
 
-template <int EPI, bool Q4>
-static int launch_mq8_ql_epi(const MMArgs& a, hipStream_t s) {
+// quantise on load, one token: tiles per work-group of mq8_pers_ql_kernel, 0 = the one-tile form.
+// gate/up 7 tiles per group (1792 = 256 x 7); Q4_0 q|k|v 2 (384 = 192 x 2, as the bf16 mm_pers_kernel:
+// 8.76 -> 7.85 us; Q8_0's measured 9.03 -> 9.23 us and keeps one tile per group)
+static int mq8_pers_ql_tpw(int epi, bool q4, int M, int N, int K, bool norm) {
   static const bool pers = getenv("MX_NO_Q8_PERS_QL") == nullptr;  // MX_NO_Q8_PERS_QL=1: one tile per group (A/B)
+  if (!(epi == EPI_SWIGLU || (epi == EPI_QKV && q4))) return 0;
+  const int tpw = epi == EPI_SWIGLU ? 7 : 2;
+  return pers && M == 1 && K == 4096 && norm && (N / TILE_N) % tpw == 0 ? tpw : 0;
+}
+// float4 per lane and row of the quantise-on-load prologue (a wave's K slice <= 256 * QP)
+static int mq8_ql_qp(int K) {
+  const int slice = (K / Q8_TILE_K + 7) / 8 * Q8_TILE_K;
+  return slice <= 512 ? 2 : slice <= 1024 ? 4 : 8;
+}
+
+template <int EPI, bool Q4>
+static int launch_mq8_ql_epi(const MMArgs& a, const Mq8Plan& p, hipStream_t s) {
   if constexpr (EPI == EPI_SWIGLU || (EPI == EPI_QKV && Q4)) {
-    // gate/up 7 tiles per group (1792 = 256 x 7); Q4_0 q|k|v 2 (384 = 192 x 2, as the bf16 mm_pers_kernel:
-    // 8.76 -> 7.85 us; Q8_0's measured 9.03 -> 9.23 us and keeps one tile per group)
     constexpr int TPW = EPI == EPI_SWIGLU ? 7 : 2;
-    if (pers && a.M == 1 && a.K == 4096 && a.norm_w && a.ssq && a.np == 256 && (a.N / TILE_N) % TPW == 0) {
+    if (p.kind == MQ8_PERS_QL) {  // (norm on load: launch_mq8 has checked a.ssq and a.np == K / 16 = 256)
       mq8_pers_ql_kernel<TPW, EPI, Q4><<<a.N / TILE_N / TPW, 512, 0, s>>>(a);
       return 0;
     }
   }
-  const int slice = (a.K / Q8_TILE_K + 7) / 8 * Q8_TILE_K;
-  if (slice <= 512) launch_mq8_ql_m<EPI, 2, Q4>(a, s);
-  else if (slice <= 1024) launch_mq8_ql_m<EPI, 4, Q4>(a, s);
-  else launch_mq8_ql_m<EPI, 8, Q4>(a, s);
+  if (p.qp == 2) launch_mq8_ql_m<EPI, 2, Q4>(a, p.qm, s);
+  else if (p.qp == 4) launch_mq8_ql_m<EPI, 4, Q4>(a, p.qm, s);
+  else launch_mq8_ql_m<EPI, 8, Q4>(a, p.qm, s);
   return 0;
 }
 
@@ -3997,13 +4023,23 @@ __global__ __launch_bounds__(64 * W) void mq8_wsw_kernel(MMArgs a) {
 // 17..32 tokens, attn_output / ffn_down / q|k|v of a Q8_0 file: 4-wave groups, K split over grid.y
 // until ~256 work-groups, partial slabs [ks][token][N] (folded by launch_rmsnorm_q8's FOLD form, or
 // finished by the decode attention / launch_qkv_finish).  Returns ks, or -1 (use launch_mq8).
-int launch_mq8_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s) {
+static bool mq8_wide_off() {
   static const bool off = getenv("MX_NO_Q8_WIDE") != nullptr;
-  if (off || a.M <= 16 || a.M > 32 || !a.xq || !a.xd || a.K % 256 || a.N % 64) return -1;
-  const int ntiles = a.N / TILE_N, NCH = a.K / 256;
+  return off;
+}
+int mq8_slab_ks(int M, int N, int K) {
+  if (mq8_wide_off() || M <= 16 || M > 32 || K < 256 || K % 256 || N < 64 || N % 64) return -1;
+  const int ntiles = N / TILE_N, NCH = K / 256;
   int ks = 1;
   static const int tgt = getenv("MX_SLAB_TARGET") ? atoi(getenv("MX_SLAB_TARGET")) : 256;  // A/B
   while (ks < 8 && (ntiles / 4) * ks * 2 <= tgt && NCH / (ks * 2) >= 4) ks *= 2;
+  return ks;
+}
+int launch_mq8_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s) {
+  if (!a.xq || !a.xd) return -1;
+  const int ks = mq8_slab_ks(a.M, a.N, a.K);
+  if (ks < 0) return -1;
+  const int ntiles = a.N / TILE_N;
   MMArgs p = a;
   p.out = slabs;
   p.ldo = a.N;
@@ -4014,11 +4050,18 @@ int launch_mq8_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream
 }
 
 // 17..32 tokens, gate/up or lm_head of a Q8_0 file: the LDS-shared form (MX_NO_Q8_WIDE=1: mq8_kernel)
-static int launch_mq8_wide(int epi, const MMArgs& a, hipStream_t s) {
-  static const bool off = getenv("MX_NO_Q8_WIDE") != nullptr;
+// row tiles (waves) per work-group of the LDS-shared form, 0 = the shape has none
+static int mq8_wide_w(int epi, int M, int N, int K) {
+  const int ntiles = N / TILE_N;
+  if (mq8_wide_off() || M <= 16 || M > 32 || K % 256) return 0;
+  if (epi != EPI_SWIGLU && epi != EPI_F32) return 0;
+  if (ntiles % 7 == 0 && ntiles / 7 >= 200) return 7;
+  if (ntiles % 8 == 0 && ntiles / 8 >= 200) return 8;
+  if (ntiles % 4 == 0) return 4;
+  return 0;
+}
+static int launch_mq8_wide(int epi, const MMArgs& a, int w, hipStream_t s) {
   const int ntiles = a.N / TILE_N;
-  if (off || a.M <= 16 || a.M > 32 || !a.xq || !a.xd || a.K % 256) return -1;
-  if (epi != EPI_SWIGLU && epi != EPI_F32) return -1;
   auto go = [&](auto wc) {
     constexpr int W = decltype(wc)::value;
     if (a.wq4) {  // Q4_0: the swapped-operand form
@@ -4030,9 +4073,9 @@ static int launch_mq8_wide(int epi, const MMArgs& a, hipStream_t s) {
     }
     return 0;
   };
-  if (ntiles % 7 == 0 && ntiles / 7 >= 200) return go(std::integral_constant<int, 7>{});
-  if (ntiles % 8 == 0 && ntiles / 8 >= 200) return go(std::integral_constant<int, 8>{});
-  if (ntiles % 4 == 0) return go(std::integral_constant<int, 4>{});
+  if (w == 7) return go(std::integral_constant<int, 7>{});
+  if (w == 8) return go(std::integral_constant<int, 8>{});
+  if (w == 4) return go(std::integral_constant<int, 4>{});
   return -1;
 }
 
@@ -4242,10 +4285,13 @@ __global__ __launch_bounds__(512, 1) void q8gemm_kernel(MMArgs a) {
 // the GEMVs (one weight pass per 64 tokens, every CU busy) are then faster (Llama-3-8B attn_output /
 // ffn_down at 256 rows: 32 blocks)
 constexpr int QG_MIN_GRID = 64;
-static int launch_q8gemm(int epi, const MMArgs& a, hipStream_t s) {
-  if (a.M < Q8_GEMM_MIN_M || a.N % 256 || a.K % Q8_TILE_K || !a.xq || !a.xd) return -1;
-  const int grid = (a.N / 256) * ((a.M + QG_M - 1) / QG_M);
-  if (grid < QG_MIN_GRID) return -1;
+// work-groups of the blocked GEMM, 0 = the shape goes to the GEMVs
+static int q8gemm_grid(int M, int N, int K) {
+  if (M < Q8_GEMM_MIN_M || N % 256 || K % Q8_TILE_K) return 0;
+  const int grid = (N / 256) * ((M + QG_M - 1) / QG_M);
+  return grid < QG_MIN_GRID ? 0 : grid;
+}
+static int launch_q8gemm(int epi, const MMArgs& a, int grid, hipStream_t s) {
   auto go = [&](auto q4c) {
     constexpr bool Q4 = decltype(q4c)::value;
     switch (epi) {
@@ -4259,35 +4305,50 @@ static int launch_q8gemm(int epi, const MMArgs& a, hipStream_t s) {
   return a.wq4 ? go(std::true_type{}) : go(std::false_type{});
 }
 
-int launch_mq8(int epi, const MMArgs& a, hipStream_t s) {
-  if (a.M < 1 || a.K % Q8_TILE_K || a.N % TILE_N) return -1;
-  if (epi == EPI_SWIGLU && !a.actf && !a.act) return -1;
-  if (!a.xq) {  // quantise on load from a.xf (+ RMS_NORM when norm_w)
-    if (!a.xf || !mq8_can_quantize_on_load(a.M, a.K, a.norm_w != nullptr) ||
-        (a.norm_w && (!a.ssq || a.np * 16 != a.K)))
-      return -1;
-    auto ql = [&](auto q4c) {
-      constexpr bool Q4 = decltype(q4c)::value;
-      switch (epi) {
-        case EPI_F32: return launch_mq8_ql_epi<EPI_F32, Q4>(a, s);
-        case EPI_RESID: return launch_mq8_ql_epi<EPI_RESID, Q4>(a, s);
-        case EPI_QKV: return launch_mq8_ql_epi<EPI_QKV, Q4>(a, s);
-        case EPI_SWIGLU: return launch_mq8_ql_epi<EPI_SWIGLU, Q4>(a, s);
-      }
-      return -1;
-    };
-    return a.wq4 ? ql(std::true_type{}) : ql(std::false_type{});
+// The kernel a shape reaches: quantise on load (one tile per group, or mq8_pers_ql_kernel), else the blocked
+// GEMM, else the LDS-shared 17..32-row form, else mq8_kernel.  launch_mq8 dispatches on this and on nothing else.
+Mq8Plan mq8_plan(int epi, int M, int N, int K, bool wq4, bool on_load, bool norm) {
+  Mq8Plan p{};
+  if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || K < Q8_TILE_K || K % Q8_TILE_K || N < TILE_N || N % TILE_N) return p;
+  if (on_load) {  // quantise on load from a.xf (+ RMS_NORM when norm_w)
+    if (!mq8_can_quantize_on_load(M, K, norm)) return p;
+    p.ks = 8, p.rt = 1, p.nb = 1, p.grid_y = 1;
+    if ((p.tpw = mq8_pers_ql_tpw(epi, wq4, M, N, K, norm)) > 0) {
+      p.kind = MQ8_PERS_QL, p.qp = 2, p.qm = 1, p.bd = 1;
+      return p;
+    }
+    p.kind = MQ8_QL, p.qp = mq8_ql_qp(K), p.qm = M == 1 ? 1 : M == 2 ? 2 : 4, p.bd = M == 1;
+    return p;
   }
-  if (!a.xd) return -1;
-  if (launch_q8gemm(epi, a, s) == 0) return 0;
-  if (launch_mq8_wide(epi, a, s) == 0) return 0;
+  if ((p.grid = q8gemm_grid(M, N, K)) > 0) {
+    p.kind = MQ8_GEMM;
+    return p;
+  }
+  if ((p.w = mq8_wide_w(epi, M, N, K)) > 0) {
+    p.kind = wq4 ? MQ8_WSW : MQ8_WIDE;
+    return p;
+  }
+  const Mq8Cfg c = mq8_gemv_cfg(epi, M, N / TILE_N);
+  p.kind = MQ8_GEMV, p.ks = c.ks, p.rt = c.rt, p.nb = c.nb, p.bd = c.bd, p.grid_y = c.nb == 4 ? (M + 63) / 64 : 1;
+  return p;
+}
+
+int launch_mq8(int epi, const MMArgs& a, hipStream_t s) {
+  if (epi == EPI_SWIGLU && !a.actf && !a.act) return -1;
+  const bool on_load = !a.xq;
+  if (on_load ? (!a.xf || (a.norm_w && (!a.ssq || a.np * 16 != a.K))) : !a.xd) return -1;
+  const Mq8Plan p = mq8_plan(epi, a.M, a.N, a.K, a.wq4 != 0, on_load, a.norm_w != nullptr);
+  if (p.kind == MQ8_NONE) return -1;
+  if (p.kind == MQ8_GEMM) return launch_q8gemm(epi, a, p.grid, s);
+  if (p.kind == MQ8_WIDE || p.kind == MQ8_WSW) return launch_mq8_wide(epi, a, p.w, s);
   auto go = [&](auto q4c) {
     constexpr bool Q4 = decltype(q4c)::value;
+    const bool ql = p.kind != MQ8_GEMV;
     switch (epi) {
-      case EPI_F32: return launch_mq8_epi<EPI_F32, Q4>(a, s);
-      case EPI_RESID: return launch_mq8_epi<EPI_RESID, Q4>(a, s);
-      case EPI_QKV: return launch_mq8_epi<EPI_QKV, Q4>(a, s);
-      case EPI_SWIGLU: return launch_mq8_epi<EPI_SWIGLU, Q4>(a, s);
+      case EPI_F32: return ql ? launch_mq8_ql_epi<EPI_F32, Q4>(a, p, s) : launch_mq8_epi<EPI_F32, Q4>(a, p, s);
+      case EPI_RESID: return ql ? launch_mq8_ql_epi<EPI_RESID, Q4>(a, p, s) : launch_mq8_epi<EPI_RESID, Q4>(a, p, s);
+      case EPI_QKV: return ql ? launch_mq8_ql_epi<EPI_QKV, Q4>(a, p, s) : launch_mq8_epi<EPI_QKV, Q4>(a, p, s);
+      case EPI_SWIGLU: return ql ? launch_mq8_ql_epi<EPI_SWIGLU, Q4>(a, p, s) : launch_mq8_epi<EPI_SWIGLU, Q4>(a, p, s);
     }
     return -1;
   };

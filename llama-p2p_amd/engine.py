@@ -37,6 +37,8 @@ EXPORTS = [
     "mx_engine_set_host_cache", "mx_host_cache_stats", "mx_kv_pack_probe",
     "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
 ]
+# the Q8_0 / Q4_0 kernel probes: names with a digit, listed apart (tests/test_gguf_abi.py checks both lists)
+EXPORTS_Q8 = ["mx_q8_matmul_probe", "mx_q8_matmul_plan", "mx_q8_side_probe"]
 LOGIT_BIAS_MAX = 256  # kernels.h SAMP_BIAS_MAX: most logit_bias entries per request
 POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3  # mx_engine.h MX_POOL_*: how embed() pools a sequence's rows
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
@@ -144,6 +146,25 @@ class MxMatmulArgs(ctypes.Structure):
                [("slabs_cap", ctypes.c_uint64), ("split_out", ctypes.c_void_p), ("packed_out", ctypes.c_void_p)]
 
 
+class MxQ8MatmulArgs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "epi", "M", "N", "K", "wq4", "act")] + \
+               [("w", ctypes.c_void_p), ("xf", ctypes.c_void_p), ("xrows", ctypes.c_int32), ("ldx", ctypes.c_int32),
+                ("norm_w", ctypes.c_void_p), ("eps", ctypes.c_float), ("row_map", ctypes.c_void_p),
+                ("fold_slabs", ctypes.c_void_p), ("nslab", ctypes.c_int32), ("want_ssq", ctypes.c_int32),
+                ("act_f32", ctypes.c_int32)] + \
+               [(n, ctypes.c_int32) for n in ("n_head", "n_head_kv", "head_dim", "n_ctx", "n_slots")] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "slot", "rope_cs", "kcache", "vcache", "resid", "fold_w", "out",
+                                               "ssq_out", "slabs_out")] + \
+               [("slabs_cap", ctypes.c_uint64)] + \
+               [(n, ctypes.c_void_p) for n in ("split_out", "packed_out", "xq_out", "xd_out", "x_out", "nxq_out",
+                                               "nxd_out")] + [("np", ctypes.c_int32)]
+
+
+class MxQ8Plan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "qp", "qm", "tpw", "ks", "rt", "nb", "bd", "grid_y", "w", "grid",
+                                              "slab_ks", "can_on_load")]
+
+
 def sampling(temperature: float = 0.0, top_k: int = 40, top_p: float = 0.95, min_p: float = 0.05,
              repeat_penalty: float = 1.0, repeat_last_n: int = 64, seed: Optional[int] = None,
              ignore_eos: bool = False, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> MxSampling:
@@ -245,6 +266,9 @@ def lib() -> ctypes.CDLL:
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
         L.mx_matmul_plan.argtypes = [i32, i32, i32, i32, P(i32), P(i32), P(i32), P(i32)]
         L.mx_norm_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_float, vp, vp]
+        L.mx_q8_matmul_probe.argtypes = [i32, P(MxQ8MatmulArgs)]
+        L.mx_q8_matmul_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, P(MxQ8Plan)]
+        L.mx_q8_side_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp]
         L.mx_submit_spec.argtypes = [vp, vp, i32, P(MxSampling), i32, i32, i32, P(u64)]
         L.mx_spec_stats.argtypes = [vp, u64, P(MxSpecCounts)]
         L.mx_draft_probe.argtypes = [i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -262,7 +286,7 @@ def lib() -> ctypes.CDLL:
         L.mx_submit_ext.argtypes = [vp, vp, i32, P(MxSamplingExt), i32, i32, i32, P(u64)]
         L.mx_submit_ext_batch.argtypes = [vp, i32, vp, vp, vp, vp, P(u64)]
         L.mx_sample_probe.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        for name in EXPORTS:
+        for name in EXPORTS + EXPORTS_Q8:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_sampling_ext_default", "mx_last_error",
                             "mx_engine_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
@@ -670,6 +694,205 @@ def norm_probe(x, slabs=None, w=None, row_map=None, eps: float = 0.0, device: in
                                eps, xo.ctypes.data, yo.ctypes.data if yo is not None else None))
     return (xo[:rows], xo[rows:].view(np.uint32), yo[:M] if yo is not None else None,
             yo[M:] if yo is not None else None)
+
+
+Q8_KIND = {0: "none", 1: "ql", 2: "pers_ql", 3: "mq8", 4: "wide", 5: "wsw", 6: "gemm"}
+
+
+def q8_matmul_plan(epi: int, M: int, N: int, K: int, wq4: bool = False, on_load: bool = False,
+                   norm: bool = False) -> dict:
+    """The kernel a Q8_0 / Q4_0 shape reaches (mx_q8_matmul_plan; no GPU): kind (a Q8_KIND name) and the
+    fields of mx_q8_plan."""
+    pl = MxQ8Plan()
+    _check(lib().mx_q8_matmul_plan(epi, M, N, K, int(bool(wq4)), int(bool(on_load)), int(bool(norm)), ctypes.byref(pl)))
+    d = {n: getattr(pl, n) for n, _ in MxQ8Plan._fields_}
+    d["kind"] = Q8_KIND[d["kind"]]
+    d["can_on_load"] = bool(d["can_on_load"])
+    return d
+
+
+class Q8Result:
+    """out / guard as MatmulResult (always f32); xq int8 [M][K] (q8_perm order) / xd f32 [M][K/32] with their
+    guards xq_guard / xd_guard; x (act 1: the rows after the fold); split, ssq [M][N/16] + ssq_guard [64][N/16], slabs [ks][M][N], packed (uint8);
+    nxq / nxd (+ guards): the folding norm's Q8_0 rows on path 1 RESID; kcache / vcache."""
+    out = guard = ssq = ssq_guard = slabs = packed = kcache = vcache = xq = xd = xq_guard = xd_guard = x = None
+    nxq = nxd = nxq_guard = nxd_guard = None
+    split = 0
+
+
+def q8_matmul_probe(path: int, epi: int, w, xf, *, wq4: bool = False, act: int = 0, N: Optional[int] = None,
+                    K: Optional[int] = None, M: Optional[int] = None, ldx: int = 0, norm_w=None, eps: float = 0.0,
+                    row_map=None, fold_slabs=None, resid=None, fold_w=None, qkv=None, want_ssq: bool = False,
+                    act_f32: bool = True, want_slabs: bool = False, want_packed: bool = False, want_x: bool = True,
+                    np_partials: int = 0, out=None, device: int = 0) -> Q8Result:
+    """A production Q8_0 / Q4_0 launcher on caller-supplied operands (include/mx_engine.h mx_q8_matmul_probe).
+    w: raw GGUF blocks uint8 [N][K/32 * 34] (wq4: [N][K/32 * 18]), None on path -1; xf f32 rows; act 0 quantise
+    (xf [M][ldx]), 1 RMS_NORM + quantise (norm_w, row_map, fold_slabs [nslab][rows][K]), 2 quantise on load.  N /
+    K / M override what the arrays imply (tests of refusals)."""
+    fa = np.ascontiguousarray(xf, dtype=np.float32)
+    if fa.ndim != 2:
+        raise ValueError("xf [rows][ld] expected")
+    wa = None
+    if w is not None:
+        wa = np.ascontiguousarray(w, dtype=np.uint8)
+        bb = 18 if wq4 else 34
+        if wa.ndim != 2 or wa.shape[1] % bb:
+            raise ValueError("w [N][K/32 * block bytes] expected")
+        if N is None:
+            N = wa.shape[0]
+        if K is None:
+            K = wa.shape[1] // bb * 32
+    if K is None:
+        if ldx:
+            raise ValueError("K is required when ldx is given without w")
+        K = fa.shape[1]
+    if N is None:
+        N = 0
+    a = MxQ8MatmulArgs()
+    ma = None
+    if row_map is not None:
+        ma = _i32(row_map)
+        a.row_map = ma.ctypes.data
+    m_given = M is not None
+    if M is None:
+        M = len(ma) if ma is not None else fa.shape[0]
+    a.path, a.epi, a.M, a.N, a.K, a.wq4, a.act = path, epi, M, N, K, int(bool(wq4)), act
+    a.w = wa.ctypes.data if wa is not None else None
+    a.xf, a.xrows, a.ldx = fa.ctypes.data, (fa.shape[0] if act == 1 else 0), ldx
+    if act != 1 and fa.shape[0] < M and not m_given:
+        raise ValueError("xf holds fewer than M rows")
+    if fa.shape[1] != (ldx or K):
+        raise ValueError("xf row length")
+    keep = [wa, fa, ma]
+    if norm_w is not None:
+        na = np.ascontiguousarray(norm_w, dtype=np.float32)
+        if na.size != K:
+            raise ValueError("norm_w [K] expected")
+        a.norm_w = na.ctypes.data
+        keep.append(na)
+    a.eps = eps
+    if fold_slabs is not None:
+        sa = np.ascontiguousarray(fold_slabs, dtype=np.float32)
+        if sa.ndim != 3 or sa.shape[1:] != fa.shape:
+            raise ValueError("fold_slabs [nslab][rows][K] expected")
+        a.nslab = sa.shape[0]
+        if a.nslab:
+            a.fold_slabs = sa.ctypes.data
+        keep.append(sa)
+    a.want_ssq, a.act_f32, a.np = int(bool(want_ssq)), int(bool(act_f32)), np_partials
+    if resid is not None:
+        ra = np.ascontiguousarray(resid, dtype=np.float32)
+        if ra.shape != (M, N):
+            raise ValueError("resid [M][N] expected")
+        a.resid = ra.ctypes.data
+        keep.append(ra)
+    if fold_w is not None:
+        fw = np.ascontiguousarray(fold_w, dtype=np.float32)
+        if fw.size != N:
+            raise ValueError("fold_w [N] expected")
+        a.fold_w = fw.ctypes.data
+        keep.append(fw)
+    ld = N // 2 if epi == EPI_SWIGLU else N
+    kc = vc = None
+    if qkv is not None:
+        g = qkv
+        a.n_head, a.n_head_kv, a.head_dim = g["n_head"], g["n_head_kv"], g["head_dim"]
+        a.n_ctx, a.n_slots = g["n_ctx"], g["n_slots"]
+        ld = max(g["n_head"] * g["head_dim"], 1)
+        for name in ("pos", "slot"):
+            if g.get(name) is not None:
+                arr = _i32(g[name])
+                if len(arr) != M:
+                    raise ValueError(f"one {name} per row")
+                setattr(a, name, arr.ctypes.data)
+                keep.append(arr)
+        if g.get("rope_cs") is not None:
+            cs = np.ascontiguousarray(g["rope_cs"], dtype=np.float32)
+            if cs.size != max(g["n_ctx"], 0) * g["head_dim"]:
+                raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
+            a.rope_cs = cs.ctypes.data
+            keep.append(cs)
+        stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+        elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
+        if g.get("kcache") is not None and g.get("vcache") is not None:
+            kc = np.array(g["kcache"], dtype=np.uint16, copy=True).reshape(-1)
+            vc = np.array(g["vcache"], dtype=np.uint16, copy=True).reshape(-1)
+            if kc.size != elems or vc.size != elems:
+                raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+            a.kcache, a.vcache = kc.ctypes.data, vc.ctypes.data
+    Mr = max(M, 0)
+    rows = Mr + PROBE_GUARD_ROWS
+    ld = max(ld, 0)
+    if out is None:
+        ob = np.zeros((rows, max(ld, 1)), dtype=np.float32)
+    else:
+        ob = out
+        if not ob.flags.c_contiguous or ob.nbytes < rows * ld * 4:
+            raise ValueError("out too small")
+    a.out = ob.ctypes.data
+    r = Q8Result()
+    split = ctypes.c_int32(0)
+    a.split_out = ctypes.addressof(split)
+    ssq = slabs = packed = xq = xd = xo = nxq = nxd = None
+    if want_ssq:
+        ssq = np.zeros((rows, max(N // 16, 1)), dtype=np.float32)
+        a.ssq_out = ssq.ctypes.data
+    if want_slabs:
+        slabs = np.zeros(max(8 * Mr * N, 1), dtype=np.float32)
+        a.slabs_out, a.slabs_cap = slabs.ctypes.data, 8 * Mr * N
+    if want_packed and wa is not None:
+        packed = np.zeros(N // 16 * (K // 64) * (576 if wq4 else 1088), dtype=np.uint8)
+        a.packed_out = packed.ctypes.data
+    if act != 2 and want_x and K > 0:
+        xq = np.zeros((rows, K), dtype=np.int8)
+        xd = np.zeros((rows, max(K // 32, 1)), dtype=np.float32)
+        a.xq_out, a.xd_out = xq.ctypes.data, xd.ctypes.data
+        if act == 1:
+            xo = np.zeros(fa.shape, dtype=np.float32)
+            a.x_out = xo.ctypes.data
+    if path == 1 and epi == EPI_RESID and N > 0:
+        nxq = np.zeros((rows, N), dtype=np.int8)
+        nxd = np.zeros((rows, max(N // 32, 1)), dtype=np.float32)
+        a.nxq_out, a.nxd_out = nxq.ctypes.data, nxd.ctypes.data
+    _check(lib().mx_q8_matmul_probe(device, ctypes.byref(a)))
+    del keep
+    if path >= 0:
+        flat = ob.reshape(-1).view(np.float32)[:rows * ld].reshape(rows, ld)
+        r.out, r.guard = flat[:M], flat[M:]
+    r.split, r.packed, r.kcache, r.vcache, r.x = split.value, packed, kc, vc, xo
+    if ssq is not None:
+        r.ssq, r.ssq_guard = ssq[:M], ssq[M:]
+    if xq is not None:
+        r.xq, r.xq_guard, r.xd, r.xd_guard = xq[:M], xq[M:], xd[:M], xd[M:]
+    if nxq is not None:
+        r.nxq, r.nxq_guard, r.nxd, r.nxd_guard = nxq[:M], nxq[M:], nxd[:M], nxd[M:]
+    if want_slabs:
+        r.slabs = slabs[:max(r.split, 0) * M * N].reshape(-1, M, N)
+    return r
+
+
+def q8_dequant_tiles_probe(blocks, device: int = 0):
+    """launch_dequant_q8_tiles on Q8_0 blocks uint8 [N][K/32 * 34] packed as at load: (packed bf16 tiles uint16
+    [N * K], guard uint16 [64 * K])."""
+    ba = np.ascontiguousarray(blocks, dtype=np.uint8)
+    N, K = ba.shape[0], ba.shape[1] // 34 * 32
+    ob = np.zeros((N + PROBE_GUARD_ROWS) * K, dtype=np.uint16)
+    _check(lib().mx_q8_side_probe(device, 0, N, K, ba.ctypes.data, None, 0, ob.ctypes.data, None))
+    return ob[:N * K], ob[N * K:]
+
+
+def q8_embed_probe(blocks, ids, want_ssq: bool = True, device: int = 0):
+    """launch_embed_q8: rows `ids` of a Q8_0 token_embd (blocks uint8 [n_vocab][n/32 * 34]) -> (x f32 [M][n], x
+    guard as uint32, ssq [M][n/16] or None, ssq guard or None)."""
+    ba = np.ascontiguousarray(blocks, dtype=np.uint8)
+    N, K = ba.shape[0], ba.shape[1] // 34 * 32
+    ia = _i32(ids)
+    M = len(ia)
+    ob = np.zeros((M + PROBE_GUARD_ROWS, K), dtype=np.float32)
+    sq = np.zeros((M + PROBE_GUARD_ROWS, K // 16), dtype=np.float32) if want_ssq else None
+    _check(lib().mx_q8_side_probe(device, 1, N, K, ba.ctypes.data, ia.ctypes.data, M, ob.ctypes.data,
+                                  sq.ctypes.data if sq is not None else None))
+    return ob[:M], ob[M:].view(np.uint32), (sq[:M] if sq is not None else None), (sq[M:] if sq is not None else None)
 
 
 def pool_probe(x, w, seq_begin, pooling: int, normalize: bool = False, chunk_rows: int = 0, eps: float = 1e-5,
