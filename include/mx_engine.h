@@ -496,6 +496,118 @@ int mx_q8_matmul_plan(int epi, int M, int N, int K, int wq4, int on_load, int no
  * and, optionally, ssq_out [M + 64][K/16].  Outputs start as 0xFF bytes. */
 int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, const int32_t* ids, int M, void* out,
                      float* ssq_out);
+/* The production K-quant (Q4_K 12, Q5_K 13, Q6_K 14) launchers on caller-supplied operands, no engine.
+ * path 0 launch_mkq (whatever it dispatches, M 1..4096); path 1 launch_mkq_slab (17..32 rows, RESID) finished as
+ * the engine finishes it: the slabs folded by the next launch_rmsnorm_q8k (weights fold_w [N]; out receives the
+ * folded x, nxq_out / nxd_out / nxb_out that norm's Q8_K rows [M + 64][N], [N/256], [N/32]; N > 4096, where that
+ * fold has no form: launch_resid_norm folds and no rows are made); path 2 launch_mkq_qkv_slab (17..32 rows, QKV)
+ * finished by launch_qkv_finish; path -1: the activation step alone (no weights, no matmul).
+ * w: raw GGUF blocks of kq_n (1..3) row segments laid end to end: segment i holds rows [16 kq_tile_end[i-1],
+ * 16 kq_tile_end[i]) as [rows][K/256] blocks of kq_type[i] (144 / 176 / 210 bytes), kq_tile_end strictly
+ * increasing, the last 16 * it = N; K % 256.  Each segment is packed on the device with launch_pack_kq at its own
+ * byte offset, as at model load (packed_out, optional, receives the packed bytes).  SWIGLU: one segment, rows
+ * [0, N/2) ffn_gate (PACK_GATE), [N/2, N) ffn_up (PACK_UP), N % 32.
+ * Activations (act), from f32 rows xf as enqueue_forward_kq's operand makes them: 0 launch_quantize_q8k of xf
+ * [M][ldx] (ldx >= K, 0 = K); 1 launch_rmsnorm_q8k of xf [xrows][K] with norm_w [K], eps and optional row_map [M]
+ * (entries in [0, xrows); without it xrows = M); 2 one token quantised on load (path 0, M 1,
+ * mkq_can_quantize_on_load(1, K, norm)): xf [K], optional norm_w with the sum-of-squares partials ssq_in [K/16]
+ * (NULL: launch_ssq makes them).  Device rows past the caller's hold 0xFF bytes (f32 NaN).  xq_out [M + 64][K]
+ * (int8, permuted within each super-block), xd_out [M + 64][K/256], xb_out [M + 64][K/32] (optional) receive the
+ * device's Q8_K rows of acts 0 / 1, rows >= M still 0xFF.
+ * out: [M + 64][ld] f32, filled with 0xFF bytes before any launch (rows >= M: a guard): F32 ld N; RESID ld N, rows
+ * < M start as resid; SWIGLU ld N/2 (the f32 act); QKV as mx_matmul_probe (K need not equal n_head * head_dim).
+ * ssq_out (want_ssq: RESID, path 0, not with norm on load: MMArgs has one ssq pointer): the partials
+ * [M + 64][N/16], rows >= M a guard.  slabs_out (paths 1 / 2, slabs_cap >= 8 * M * N floats): the raw partials
+ * [ks][M][N] as the launcher left them (the device buffer holds exactly the ks slabs of mkq_slab_ks /
+ * mkq_qkv_slab_ks, which the launcher dispatches on); *split_out: the launcher's return (ks).
+ * Everything a kernel indexes with is checked before any launch (MX_ERR_ARG, nothing launched).  A matmul launcher
+ * that refuses the shape gives MX_ERR_ARG with its name in mx_last_error(): it launched nothing itself, but the
+ * packer and the activation step before it have run. */
+typedef struct {
+  int32_t path, epi, M, N, K, act;
+  int32_t kq_n;
+  int32_t kq_type[3], kq_tile_end[3];
+  const void* w;
+  const float* xf;
+  int32_t xrows, ldx;
+  const float* norm_w;
+  float eps;
+  const int32_t* row_map;
+  const float* ssq_in;
+  int32_t want_ssq;
+  int32_t n_head, n_head_kv, head_dim, n_ctx, n_slots;
+  const int32_t* pos;
+  const int32_t* slot;
+  const float* rope_cs;
+  void* kcache;
+  void* vcache;
+  const float* resid;
+  const float* fold_w;
+  void* out;
+  float* ssq_out;
+  float* slabs_out;
+  uint64_t slabs_cap;
+  int32_t* split_out;
+  void* packed_out;
+  void* xq_out;
+  float* xd_out;
+  float* xb_out;
+  void* nxq_out;
+  float* nxd_out;
+  float* nxb_out;
+} mx_kq_matmul_args;
+int mx_kq_matmul_probe(int device, const mx_kq_matmul_args* a);
+/* The kernel a K-quant shape reaches, no GPU needed: mkq_plan, the function launch_mkq and its sub-launchers
+ * dispatch on.  on_load / norm: one token quantised on load, with RMS_NORM; the row segments as in
+ * mx_kq_matmul_args.  flags: -1 = this process's MX_NO_KQ_* switches, else bit 0 MX_NO_KQ_BD_TILE, bit 1
+ * MX_NO_KQ_PERS, bit 2 MX_NO_KQ_WIDE as if set (the split target stays the process's).
+ * kind: 0 launch_mkq refuses, 1 qkv_pers (mkq_pers_seg_kernel<ks, nkw, tpw, QKV, u>), 2 bd_tile
+ * (mkq_bd_tile_kernel<t, w, nkw = K/256, tpw, epi, u>), 3 pers (mkq_pers_kernel<t, ks, nkw, tpw, nb, epi, u, ql,
+ * bd>), 4 wide (mkq_wide_kernel<t, w, nb, epi, u>), 5 mkq (mkq_kernel<ks, 1, nb, epi, u, ql, bd>); t 0: the type is
+ * chosen per work-group; grid_x, grid_y: the launch grid.  slab_ks / qkv_slab_ks: what launch_mkq_slab /
+ * launch_mkq_qkv_slab return for pre-quantised rows of this shape (-1: refused).  can_on_load:
+ * mkq_can_quantize_on_load(M, K, norm). */
+typedef struct {
+  int32_t kind, t, ks, nkw, tpw, nb, u, bd, ql, w, grid_x, grid_y, slab_ks, qkv_slab_ks, can_on_load;
+} mx_kq_plan;
+int mx_kq_matmul_plan(int epi, int M, int N, int K, int on_load, int norm, int kq_n, const int32_t* kq_type,
+                      const int32_t* kq_tile_end, int flags, mx_kq_plan* out);
+/* The K-quant side kernels alone, no engine; K % 256.  Outputs start as 0xFF bytes; a launcher that refuses gives
+ * MX_ERR_ARG and nothing is launched.
+ * mode 0 launch_pack_kq: blocks [N][K/256] of `type` (N % 16) into a matrix of N + offset rows with PACK_ROWS
+ *   (pack 0, offset % 16 == 0) or of 2 N rows with PACK_GATE / PACK_UP (pack 1 / 2) -> out: that matrix's packed
+ *   bytes (kq_matrix_bytes) then 64 tiles of guard.
+ * mode 1 launch_dequant_kq: blocks in row segments (kq_n, kq_type, kq_tile_end as in mx_kq_matmul_args), each
+ *   packed with launch_pack_kq -> out uint16 [(N + 64) * K] packed bf16 tiles (kernels.h layout).
+ * mode 2 launch_embed_kq: rows ids [M] (in [0, N)) of blocks [N][K/256] of `type` -> out f32 [M + 64][K], ssq_out
+ *   (optional) [M + 64][K/16].
+ * mode 3 launch_quantize_q8k of x f32 [M][ld] (ld >= K, 0 = K; rows = M); mode 4 launch_rmsnorm_q8k of x [rows][K]
+ *   with w [K], eps, optional row_map [M] (entries in [0, rows); without it M = rows) and slabs [nslab][rows][K],
+ *   nslab 0..8, folded into x first -> xq_out [M + 64][K] int8, xd_out [M + 64][K/256], xb_out [M + 64][K/32], and
+ *   x_out (optional) [rows + 64][ld]: the device's x after the launch. */
+typedef struct {
+  int32_t mode, type, N, K;
+  const void* blocks;
+  int32_t pack, offset;
+  int32_t kq_n;
+  int32_t kq_type[3], kq_tile_end[3];
+  const int32_t* ids;
+  int32_t M, rows, ld;
+  const float* x;
+  const float* w;
+  const int32_t* row_map;
+  float eps;
+  const float* slabs;
+  int32_t nslab;
+  void* out;
+  float* ssq_out;
+  void* xq_out;
+  float* xd_out;
+  float* xb_out;
+  float* x_out;
+} mx_kq_side_args;
+int mx_kq_side_probe(int device, const mx_kq_side_args* a);
+
 /* launch_resid_norm (row_map NULL) / launch_rmsnorm (row_map given, nslab 0) on caller-supplied rows, no
  * engine.  x f32 [rows][n] (n % 64, n <= 16384, rows 1..4096); slabs [nslab][rows][n] (0 <= nslab <= 16) are
  * folded into x in slab order; w f32 [n] (optional): y = bf16(rmsnorm(x, eps) * w) [M][n]; row_map [M] (entries

@@ -1602,7 +1602,12 @@ int mx_engine::enqueue_forward_kq(int M, const int* pos, const int* slot, void* 
     }
     int rc;
     if (norm_w && src == x && nslab) {
-      rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
+      if (K > 16 * 256) {  // launch_rmsnorm_q8k folds in one work-group per row, n <= 4096 (h 8192: Llama-3-70B): fold first
+        launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, rows, K, eps, s);
+        rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s);
+      } else {
+        rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
+      }
       nslab = 0;
     } else {
       rc = norm_w ? launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s)
@@ -4291,6 +4296,423 @@ int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, con
   HIPC(hipDeviceSynchronize());
   HIPC(hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost));
   if (ssq_out) HIPC(hipMemcpy(ssq_out, d_ssq, sb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+namespace {
+MkqEnv kq_probe_env(int flags) {
+  MkqEnv env = mkq_env();
+  if (flags >= 0) env.no_bd_tile = flags & 1, env.no_pers = (flags & 2) != 0, env.no_wide = (flags & 4) != 0;
+  return env;
+}
+// the row segments of a K-quant probe matrix: types known, ends strictly increasing up to N / 16
+bool kq_segments_ok(int kq_n, const int32_t* type, const int32_t* tile_end, int N) {
+  if (kq_n < 1 || kq_n > 3 || N < TILE_N || N % TILE_N) return false;
+  for (int i = 0; i < kq_n; i++)
+    if (!kq_tile_bytes(type[i]) || tile_end[i] <= (i ? tile_end[i - 1] : 0)) return false;
+  return (long long)tile_end[kq_n - 1] * TILE_N == N;
+}
+}  // namespace
+
+int mx_kq_matmul_plan(int epi, int M, int N, int K, int on_load, int norm, int kq_n, const int32_t* kq_type,
+                      const int32_t* kq_tile_end, int flags, mx_kq_plan* out) {
+  if (!out || !kq_type || !kq_tile_end) return fail(MX_ERR_ARG, "mx_kq_matmul_plan: null plan or segments");
+  if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || N < TILE_N || N % TILE_N || K < 256 || K % 256 || kq_n < 1 ||
+      kq_n > 3 || flags < -1 || flags > 7)
+    return fail(MX_ERR_ARG, "mx_kq_matmul_plan: epi 0..3, M >= 1, N a multiple of 16, K of 256, 1..3 segments, flags -1..7");
+  const MkqEnv env = kq_probe_env(flags);
+  const MkqPlan p = mkq_plan(epi, M, N, K, on_load != 0, norm != 0, kq_n, kq_type, kq_tile_end, env);
+  *out = mx_kq_plan{p.kind, p.t, p.ks, p.nkw, p.tpw, p.nb, p.u, p.bd, p.ql, p.w, p.grid_x, p.grid_y,
+                    on_load ? -1 : mkq_slab_ks(M, N, K, kq_n, kq_type, env),
+                    on_load ? -1 : mkq_qkv_slab_ks(M, N, K, kq_n, kq_tile_end, env),
+                    mkq_can_quantize_on_load(M, K, norm != 0) ? 1 : 0};
+  return 0;
+}
+
+int mx_kq_matmul_probe(int device, const mx_kq_matmul_args* pa) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (!pa) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: null arguments");
+  const mx_kq_matmul_args& p = *pa;
+  const int path = p.path, epi = p.epi, M = p.M, N = p.N, K = p.K, act = p.act;
+  const bool mm = path >= 0;  // path -1: quantise only
+  if (path < -1 || path > 2 || act < 0 || act > 2) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: path -1..2, act 0..2");
+  if (mm && (epi < EPI_F32 || epi > EPI_SWIGLU)) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: epi 0..3");
+  if (K < 256 || K % 256 || K > 32768) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: K a multiple of 256, <= 32768");
+  if (mm && (N < TILE_N || N % TILE_N || N > (1 << 18) || (size_t)N * K > ((size_t)1 << 30) || !p.w || !p.out))
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: N a multiple of 16 (<= 2^18), N*K <= 2^30, w and out required");
+  if (mm && !kq_segments_ok(p.kq_n, p.kq_type, p.kq_tile_end, N))
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1..3 segments of type 12 / 13 / 14, tile ends increasing to N / 16");
+  if (mm && epi == EPI_SWIGLU && (N % 32 || p.kq_n != 1))
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: SWIGLU: one segment, N a multiple of 32");
+  if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1 <= M <= PREFILL_ROWS rows");
+  if (path >= 1 && (M > MAX_ROWS || act == 2 || epi != (path == 1 ? EPI_RESID : EPI_QKV)))
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: paths 1 / 2 (slabs): <= 64 pre-quantised rows, RESID / QKV");
+  if (!p.xf) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: xf is required");
+  int xrows = M, ldx = K;
+  if (act == 0) {
+    ldx = p.ldx ? p.ldx : K;
+    if (ldx < K || ldx % 4 || ldx > 65536) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: act 0: K <= ldx <= 65536, ldx % 4 == 0");
+    if (p.norm_w || p.row_map) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: act 0 takes no norm_w / row_map");
+  } else if (act == 1) {
+    xrows = p.xrows ? p.xrows : M;
+    if (!p.norm_w || xrows < 1 || xrows > PREFILL_ROWS || (p.ldx && p.ldx != K))
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: act 1: norm_w given, 1 <= xrows <= PREFILL_ROWS, ldx = K");
+    if (p.row_map) {
+      for (int i = 0; i < M; i++)
+        if (p.row_map[i] < 0 || p.row_map[i] >= xrows) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: row_map entry out of range");
+    } else if (xrows != M) {
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: act 1 without row_map: xrows = M");
+    }
+  } else {
+    if (path != 0 || M != 1 || p.row_map || (p.ldx && p.ldx != K))
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: act 2 (quantise on load): path 0, one row, no row_map, ldx = K");
+    if (!mkq_can_quantize_on_load(M, K, p.norm_w != nullptr))
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: mkq_can_quantize_on_load refuses K");
+  }
+  const bool nol = act == 2 && p.norm_w;
+  if (p.ssq_in && !nol) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: ssq_in: act 2 with norm_w");
+  if (p.want_ssq && (!mm || epi != EPI_RESID || path != 0 || !p.ssq_out || nol))
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: want_ssq: RESID on path 0, with ssq_out, no norm on load");
+  if (mm && epi == EPI_RESID) {
+    if (!p.resid) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: RESID takes resid [M][N]");
+    if (path == 1 && (!p.fold_w || N % 64 || N > 16384))
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: RESID slabs: fold_w [N], N a multiple of 64, <= 16384");
+  }
+  int n_q = 0, n_kv = 0, ctx_stride = 0;
+  size_t slot_stride = 0, cache_elems = 0;
+  if (mm && epi == EPI_QKV) {
+    if (!p.pos || !p.slot || !p.rope_cs || !p.kcache || !p.vcache)
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: QKV takes pos, slot, rope_cs and both caches");
+    if ((p.head_dim != 64 && p.head_dim != 128) || p.n_head < 1 || p.n_head_kv < 1 || p.n_head > 1024 ||
+        p.n_head_kv > 1024 || (long long)(p.n_head + 2 * p.n_head_kv) * p.head_dim != N)
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: head_dim 64 or 128, N = (n_head + 2 n_head_kv) * head_dim");
+    if (p.n_ctx < 1 || p.n_ctx > (1 << 20) || p.n_slots < 1 || p.n_slots > 4096)
+      return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+    n_q = p.n_head * p.head_dim;
+    n_kv = p.n_head_kv * p.head_dim;
+    ctx_stride = (p.n_ctx + KV_POS_ALIGN - 1) / KV_POS_ALIGN * KV_POS_ALIGN;
+    slot_stride = (size_t)p.n_head_kv * ctx_stride * p.head_dim;
+    cache_elems = slot_stride * p.n_slots;
+    if (cache_elems > ((size_t)1 << 29)) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: caches above 1 GiB each");
+    for (int i = 0; i < M; i++) {
+      if (p.slot[i] < 0 || p.slot[i] >= p.n_slots) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: slot out of range");
+      if (p.pos[i] < 0 || p.pos[i] > p.n_ctx) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: position outside [0, n_ctx]");
+    }
+  }
+  // the split the launcher will take (it dispatches on the same function): the slab buffer holds exactly ks slabs
+  const int ks_plan = path == 1   ? mkq_slab_ks(M, N, K, p.kq_n, p.kq_type, mkq_env())
+                      : path == 2 ? mkq_qkv_slab_ks(M, N, K, p.kq_n, p.kq_tile_end, mkq_env())
+                                  : 0;
+  const size_t slab_stride = mm ? (size_t)M * N : 0, slab_total = ks_plan > 0 ? slab_stride * ks_plan : 0;
+  if (path >= 1 && p.slabs_out && p.slabs_cap < (uint64_t)slab_stride * 8)
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: slabs_out holds fewer than 8 * M * N floats");
+  if (device >= 0) HIPC(hipSetDevice(device));
+
+  DevBufs dev;
+  const int SB = K / 256;
+  size_t raw_bytes = 0, wbytes = 0, raw_off[3] = {0, 0, 0}, w_off[3] = {0, 0, 0};
+  int seg_rows[3] = {0, 0, 0};
+  if (mm)
+    for (int i = 0; i < p.kq_n; i++) {
+      seg_rows[i] = (p.kq_tile_end[i] - (i ? p.kq_tile_end[i - 1] : 0)) * TILE_N;
+      raw_off[i] = raw_bytes, w_off[i] = wbytes;
+      raw_bytes += (size_t)seg_rows[i] * SB * kq_block_bytes(p.kq_type[i]);
+      wbytes += kq_matrix_bytes(p.kq_type[i], seg_rows[i], K);
+    }
+  uint8_t *d_src = nullptr, *d_w = nullptr, *d_out = nullptr;
+  float *d_xf = nullptr, *d_nw = nullptr, *d_ssq = nullptr, *d_slabs = nullptr, *d_cs = nullptr;
+  float *d_xd = nullptr, *d_xb = nullptr, *d_fw = nullptr, *d_nxd = nullptr, *d_nxb = nullptr;
+  int8_t *d_xq = nullptr, *d_nxq = nullptr;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr, *d_map = nullptr;
+  const int ld = !mm ? 0 : epi == EPI_SWIGLU ? N / 2 : epi == EPI_QKV ? n_q : N;
+  const size_t out_bytes = (size_t)(M + PROBE_GUARD_ROWS) * ld * 4;
+  const size_t xf_bytes = (size_t)(act == 2 ? 1 : xrows) * ldx * 4;
+  const int qrows = M + PROBE_GUARD_ROWS;  // Q8_K rows; those past M stay 0xFF
+  const size_t xq_bytes = (size_t)qrows * K, xd_bytes = (size_t)qrows * SB * 4, xb_bytes = (size_t)qrows * (K / 32) * 4;
+  const int np = nol ? K / 16 : N / 16;
+  const size_t ssq_bytes = nol ? (size_t)np * 4 : (size_t)(M + PROBE_GUARD_ROWS) * np * 4;
+  const bool fold_q8k = path == 1 && N % 256 == 0 && N <= 4096;  // launch_rmsnorm_q8k's fold; else launch_resid_norm
+  if (!dev.alloc(&d_xf, xf_bytes) || (p.norm_w && !dev.alloc(&d_nw, (size_t)K * 4)) ||
+      (p.row_map && !dev.alloc(&d_map, (size_t)M * 4)) ||
+      (act != 2 && (!dev.alloc(&d_xq, xq_bytes) || !dev.alloc(&d_xd, xd_bytes) || !dev.alloc(&d_xb, xb_bytes))))
+    return fail(MX_ERR_HIP, "mx_kq_matmul_probe: device allocation");
+  if (mm && (!dev.alloc(&d_src, raw_bytes) || !dev.alloc(&d_w, wbytes) || !dev.alloc(&d_out, out_bytes) ||
+             ((nol || p.want_ssq) && !dev.alloc(&d_ssq, ssq_bytes)) || (slab_total && !dev.alloc(&d_slabs, slab_total * 4))))
+    return fail(MX_ERR_HIP, "mx_kq_matmul_probe: device allocation");
+  if (fold_q8k && (!dev.alloc(&d_fw, (size_t)N * 4) || !dev.alloc(&d_nxq, (size_t)qrows * N) ||
+                   !dev.alloc(&d_nxd, (size_t)qrows * (N / 256) * 4) || !dev.alloc(&d_nxb, (size_t)qrows * (N / 32) * 4)))
+    return fail(MX_ERR_HIP, "mx_kq_matmul_probe: device allocation");
+  if (mm && epi == EPI_QKV &&
+      (!dev.alloc(&d_k, cache_elems * 2) || !dev.alloc(&d_v, cache_elems * 2) || !dev.alloc(&d_pos, (size_t)M * 4) ||
+       !dev.alloc(&d_slot, (size_t)M * 4) || !dev.alloc(&d_cs, (size_t)p.n_ctx * p.head_dim * 4)))
+    return fail(MX_ERR_HIP, "mx_kq_matmul_probe: device allocation");
+
+  MMArgs a{};
+  if (mm) {  // weights: every segment packed on the device exactly as at model load
+    HIPC(hipMemcpy(d_src, p.w, raw_bytes, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_w, 0xFF, wbytes));
+    for (int i = 0; i < p.kq_n; i++) {
+      const uint8_t* src = d_src + raw_off[i];
+      int rc;
+      if (epi == EPI_SWIGLU) {
+        rc = launch_pack_kq(d_w, src, p.kq_type[0], N / 2, K, PACK_GATE, 0, nullptr);
+        if (!rc)
+          rc = launch_pack_kq(d_w, src + (size_t)(N / 2) * SB * kq_block_bytes(p.kq_type[0]), p.kq_type[0], N / 2, K, PACK_UP,
+                              0, nullptr);
+      } else {
+        rc = launch_pack_kq(d_w + w_off[i], src, p.kq_type[i], seg_rows[i], K, PACK_ROWS, 0, nullptr);
+      }
+      if (rc) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_ARG, "mx_kq_matmul_probe: launch_pack_kq refused the shape");
+      }
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemset(d_out, 0xFF, out_bytes));
+    if (epi == EPI_RESID) HIPC(hipMemcpy(d_out, p.resid, (size_t)M * N * 4, hipMemcpyHostToDevice));
+    if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, ssq_bytes));
+    if (d_slabs) HIPC(hipMemset(d_slabs, 0xFF, slab_total * 4));
+    a.W = reinterpret_cast<const uint16_t*>(d_w); a.N = N; a.K = K; a.M = M; a.eps = p.eps;
+    a.kq_n = p.kq_n;
+    for (int i = 0; i < p.kq_n; i++) a.kq_type[i] = p.kq_type[i], a.kq_tile_end[i] = p.kq_tile_end[i], a.kq_off[i] = w_off[i];
+  }
+  HIPC(hipMemcpy(d_xf, p.xf, xf_bytes, hipMemcpyHostToDevice));
+  if (act != 2) {
+    HIPC(hipMemset(d_xq, 0xFF, xq_bytes));
+    HIPC(hipMemset(d_xd, 0xFF, xd_bytes));
+    HIPC(hipMemset(d_xb, 0xFF, xb_bytes));
+  }
+  if (p.norm_w) HIPC(hipMemcpy(d_nw, p.norm_w, (size_t)K * 4, hipMemcpyHostToDevice));
+  if (p.row_map) HIPC(hipMemcpy(d_map, p.row_map, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (d_fw) {
+    HIPC(hipMemcpy(d_fw, p.fold_w, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_nxq, 0xFF, (size_t)qrows * N));
+    HIPC(hipMemset(d_nxd, 0xFF, (size_t)qrows * (N / 256) * 4));
+    HIPC(hipMemset(d_nxb, 0xFF, (size_t)qrows * (N / 32) * 4));
+  }
+  if (mm && epi == EPI_QKV) {
+    HIPC(hipMemcpy(d_k, p.kcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_v, p.vcache, cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_pos, p.pos, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_slot, p.slot, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_cs, p.rope_cs, (size_t)p.n_ctx * p.head_dim * 4, hipMemcpyHostToDevice));
+    a.n_q = n_q; a.n_kv = n_kv; a.head_dim = p.head_dim; a.pos = d_pos; a.slot = d_slot; a.rope_cs = d_cs;
+    a.kc = d_k; a.vc = d_v; a.n_ctx = p.n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = p.n_head_kv;
+    a.slot_stride = slot_stride;
+  }
+
+  // the operand, as enqueue_forward_kq's `operand` makes it
+  int rc = 0;
+  const char* who = "";
+  if (act == 2) {
+    a.xq = nullptr; a.xf = d_xf; a.norm_w = d_nw; a.np = K / 16;
+    if (nol) {
+      if (p.ssq_in) HIPC(hipMemcpy(d_ssq, p.ssq_in, ssq_bytes, hipMemcpyHostToDevice));
+      else launch_ssq(d_xf, 1, K, d_ssq, nullptr);  // the partials as the embedding / the residual writers leave them
+      a.ssq = d_ssq;
+    }
+  } else {
+    who = act == 1 ? "launch_rmsnorm_q8k" : "launch_quantize_q8k";
+    rc = act == 1 ? launch_rmsnorm_q8k(d_xq, d_xd, d_xb, d_xf, d_nw, d_map, M, K, p.eps, nullptr)
+                  : launch_quantize_q8k(d_xq, d_xd, d_xb, d_xf, ldx, M, K, nullptr);
+    a.xq = d_xq; a.xd = d_xd; a.xb = d_xb;
+  }
+  if (mm && !rc) {
+    if (epi == EPI_SWIGLU) {
+      a.actf = (float*)d_out; a.lda = ld;
+    } else {
+      a.out = (float*)d_out; a.ldo = ld;
+    }
+    if (p.want_ssq) a.ssq = d_ssq, a.np = np;
+    if (path == 0) {
+      who = "launch_mkq";
+      rc = launch_mkq(epi, a, nullptr);
+    } else {
+      who = path == 1 ? "launch_mkq_slab" : "launch_mkq_qkv_slab";
+      rc = path == 1 ? launch_mkq_slab(a, d_slabs, slab_stride, nullptr) : launch_mkq_qkv_slab(a, d_slabs, slab_stride, nullptr);
+      if (rc > 0 && rc != ks_plan) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_STATE, std::string(who) + " split " + std::to_string(rc) + ", planned " + std::to_string(ks_plan));
+      }
+      if (rc > 0 && path == 2) {
+        launch_qkv_finish(a, d_slabs, rc, slab_stride, nullptr);
+      } else if (rc > 0 && fold_q8k) {
+        if (launch_rmsnorm_q8k(d_nxq, d_nxd, d_nxb, (float*)d_out, d_fw, nullptr, M, N, p.eps, nullptr, d_slabs, rc, slab_stride))
+          who = "launch_rmsnorm_q8k (fold)", rc = -1;
+      } else if (rc > 0) {
+        launch_resid_norm(nullptr, 0, (float*)d_out, d_slabs, rc, slab_stride, nullptr, M, N, p.eps, nullptr);
+      }
+    }
+  }
+  if (rc < 0) {
+    hipDeviceSynchronize();
+    return fail(MX_ERR_ARG, std::string("mx_kq_matmul_probe: ") + who + " refused the shape");
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (mm) HIPC(hipMemcpy(p.out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  if (p.want_ssq) HIPC(hipMemcpy(p.ssq_out, d_ssq, ssq_bytes, hipMemcpyDeviceToHost));
+  if (p.slabs_out && path >= 1 && rc > 0) HIPC(hipMemcpy(p.slabs_out, d_slabs, (size_t)rc * slab_stride * 4, hipMemcpyDeviceToHost));
+  if (p.split_out) *p.split_out = rc;
+  if (p.packed_out && mm) HIPC(hipMemcpy(p.packed_out, d_w, wbytes, hipMemcpyDeviceToHost));
+  if (act != 2) {
+    if (p.xq_out) HIPC(hipMemcpy(p.xq_out, d_xq, xq_bytes, hipMemcpyDeviceToHost));
+    if (p.xd_out) HIPC(hipMemcpy(p.xd_out, d_xd, xd_bytes, hipMemcpyDeviceToHost));
+    if (p.xb_out) HIPC(hipMemcpy(p.xb_out, d_xb, xb_bytes, hipMemcpyDeviceToHost));
+  }
+  if (d_nxq) {
+    if (p.nxq_out) HIPC(hipMemcpy(p.nxq_out, d_nxq, (size_t)qrows * N, hipMemcpyDeviceToHost));
+    if (p.nxd_out) HIPC(hipMemcpy(p.nxd_out, d_nxd, (size_t)qrows * (N / 256) * 4, hipMemcpyDeviceToHost));
+    if (p.nxb_out) HIPC(hipMemcpy(p.nxb_out, d_nxb, (size_t)qrows * (N / 32) * 4, hipMemcpyDeviceToHost));
+  }
+  if (mm && epi == EPI_QKV) {
+    HIPC(hipMemcpy(p.kcache, d_k, cache_elems * 2, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(p.vcache, d_v, cache_elems * 2, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int mx_kq_side_probe(int device, const mx_kq_side_args* pa) {
+  if (!pa) return fail(MX_ERR_ARG, "mx_kq_side_probe: null arguments");
+  const mx_kq_side_args& p = *pa;
+  const int mode = p.mode, N = p.N, K = p.K, M = p.M;
+  if (mode < 0 || mode > 4) return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 0..4");
+  if (K < 256 || K % 256 || K > 32768) return fail(MX_ERR_ARG, "mx_kq_side_probe: K a multiple of 256, <= 32768");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  const int SB = K / 256;
+  if (mode <= 2) {
+    if (!p.blocks || !p.out || N < 1 || N > (1 << 18) || (size_t)N * K > ((size_t)1 << 28))
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: blocks and out required, 1 <= N <= 2^18, N*K <= 2^28");
+    uint8_t *d_src = nullptr, *d_w = nullptr, *d_out = nullptr;
+    if (mode == 0) {  // launch_pack_kq alone
+      const int bb = kq_block_bytes(p.type);
+      if (!bb || N % TILE_N || p.pack < PACK_ROWS || p.pack > PACK_UP || p.offset < 0 || p.offset % TILE_N ||
+          p.offset > (1 << 18) || (p.pack != PACK_ROWS && p.offset))
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 0: type 12 / 13 / 14, N % 16, pack 0..2, offset % 16 (pack 0 only)");
+      const int rows = p.pack == PACK_ROWS ? N + p.offset : 2 * N;
+      const size_t raw = (size_t)N * SB * bb, wb = kq_matrix_bytes(p.type, rows, K);
+      const size_t ob = wb + (size_t)PROBE_GUARD_ROWS * kq_tile_bytes(p.type);
+      if (!dev.alloc(&d_src, raw) || !dev.alloc(&d_w, ob)) return fail(MX_ERR_HIP, "mx_kq_side_probe: device allocation");
+      HIPC(hipMemcpy(d_src, p.blocks, raw, hipMemcpyHostToDevice));
+      HIPC(hipMemset(d_w, 0xFF, ob));
+      if (launch_pack_kq(d_w, d_src, p.type, N, K, p.pack, p.offset, nullptr)) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: launch_pack_kq refused the shape");
+      }
+      HIPC(hipGetLastError());
+      HIPC(hipDeviceSynchronize());
+      HIPC(hipMemcpy(p.out, d_w, ob, hipMemcpyDeviceToHost));
+      return 0;
+    }
+    if (mode == 1) {  // packed K-quant tiles -> packed bf16 tiles
+      if (!kq_segments_ok(p.kq_n, p.kq_type, p.kq_tile_end, N))
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 1: 1..3 segments of type 12 / 13 / 14, tile ends increasing to N / 16");
+      size_t raw = 0, wb = 0, raw_off[3], w_off[3];
+      int rows[3], type[3], tile_end[3];
+      for (int i = 0; i < p.kq_n; i++) {
+        rows[i] = (p.kq_tile_end[i] - (i ? p.kq_tile_end[i - 1] : 0)) * TILE_N;
+        type[i] = p.kq_type[i], tile_end[i] = p.kq_tile_end[i];
+        raw_off[i] = raw, w_off[i] = wb;
+        raw += (size_t)rows[i] * SB * kq_block_bytes(type[i]);
+        wb += kq_matrix_bytes(type[i], rows[i], K);
+      }
+      const size_t ob = (size_t)(N + PROBE_GUARD_ROWS) * K * 2;
+      if (!dev.alloc(&d_src, raw) || !dev.alloc(&d_w, wb) || !dev.alloc(&d_out, ob))
+        return fail(MX_ERR_HIP, "mx_kq_side_probe: device allocation");
+      HIPC(hipMemcpy(d_src, p.blocks, raw, hipMemcpyHostToDevice));
+      HIPC(hipMemset(d_w, 0xFF, wb));
+      HIPC(hipMemset(d_out, 0xFF, ob));
+      int rc = 0;
+      for (int i = 0; i < p.kq_n && !rc; i++)
+        rc = launch_pack_kq(d_w + w_off[i], d_src + raw_off[i], type[i], rows[i], K, PACK_ROWS, 0, nullptr);
+      if (!rc) rc = launch_dequant_kq((uint16_t*)d_out, d_w, K, p.kq_n, type, tile_end, w_off, nullptr);
+      if (rc) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: launch_pack_kq / launch_dequant_kq refused the shape");
+      }
+      HIPC(hipGetLastError());
+      HIPC(hipDeviceSynchronize());
+      HIPC(hipMemcpy(p.out, d_out, ob, hipMemcpyDeviceToHost));
+      return 0;
+    }
+    const int bb = kq_block_bytes(p.type);  // mode 2: GET_ROWS
+    if (!bb || !p.ids || M < 1 || M > PREFILL_ROWS)
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 2: type 12 / 13 / 14, ids [M], 1 <= M <= PREFILL_ROWS");
+    for (int i = 0; i < M; i++)
+      if (p.ids[i] < 0 || p.ids[i] >= N) return fail(MX_ERR_ARG, "mx_kq_side_probe: id out of range");
+    float* d_ssq = nullptr;
+    int* d_ids = nullptr;
+    const size_t raw = (size_t)N * SB * bb;
+    const size_t ob = (size_t)(M + PROBE_GUARD_ROWS) * K * 4, sb = (size_t)(M + PROBE_GUARD_ROWS) * (K / 16) * 4;
+    if (!dev.alloc(&d_src, raw) || !dev.alloc(&d_out, ob) || !dev.alloc(&d_ids, (size_t)M * 4) ||
+        (p.ssq_out && !dev.alloc(&d_ssq, sb)))
+      return fail(MX_ERR_HIP, "mx_kq_side_probe: device allocation");
+    HIPC(hipMemcpy(d_src, p.blocks, raw, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_out, 0xFF, ob));
+    if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, sb));
+    HIPC(hipMemcpy(d_ids, p.ids, (size_t)M * 4, hipMemcpyHostToDevice));
+    if (launch_embed_kq((float*)d_out, d_src, p.type, d_ids, M, K, d_ssq, nullptr)) {
+      hipDeviceSynchronize();
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: launch_embed_kq refused the shape");
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(p.out, d_out, ob, hipMemcpyDeviceToHost));
+    if (p.ssq_out) HIPC(hipMemcpy(p.ssq_out, d_ssq, sb, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // modes 3 / 4: the Q8_K quantiser on f32 rows
+  const bool norm = mode == 4;
+  const int ld = norm ? K : (p.ld ? p.ld : K);
+  const int rows = norm ? (p.rows ? p.rows : M) : M;
+  if (!p.x || !p.xq_out || !p.xd_out || !p.xb_out || M < 1 || M > PREFILL_ROWS || rows < 1 || rows > PREFILL_ROWS)
+    return fail(MX_ERR_ARG, "mx_kq_side_probe: modes 3 / 4: x and xq / xd / xb outputs, 1 <= M, rows <= PREFILL_ROWS");
+  if (ld < K || ld % 4 || ld > 65536 || (norm && p.ld && p.ld != K))
+    return fail(MX_ERR_ARG, "mx_kq_side_probe: K <= ld <= 65536, ld % 4 == 0 (mode 4: ld = K)");
+  if (!norm && (p.w || p.row_map || p.nslab || p.slabs)) return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 3 takes no w / row_map / slabs");
+  if (norm) {
+    if (!p.w || p.nslab < 0 || p.nslab > 8 || (p.nslab > 0) != (p.slabs != nullptr))
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 4: w [K], nslab 0..8 with slabs");
+    if (p.row_map) {
+      for (int i = 0; i < M; i++)
+        if (p.row_map[i] < 0 || p.row_map[i] >= rows) return fail(MX_ERR_ARG, "mx_kq_side_probe: row_map entry out of range");
+    } else if (rows != M) {
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 4 without row_map: rows = M");
+    }
+  }
+  float *d_x = nullptr, *d_w = nullptr, *d_slabs = nullptr, *d_xd = nullptr, *d_xb = nullptr;
+  int8_t* d_xq = nullptr;
+  int* d_map = nullptr;
+  const int qrows = M + PROBE_GUARD_ROWS;
+  const size_t x_bytes = (size_t)(rows + PROBE_GUARD_ROWS) * ld * 4, stride = (size_t)rows * K;
+  const size_t xq_bytes = (size_t)qrows * K, xd_bytes = (size_t)qrows * SB * 4, xb_bytes = (size_t)qrows * (K / 32) * 4;
+  if (!dev.alloc(&d_x, x_bytes) || !dev.alloc(&d_xq, xq_bytes) || !dev.alloc(&d_xd, xd_bytes) || !dev.alloc(&d_xb, xb_bytes) ||
+      (norm && !dev.alloc(&d_w, (size_t)K * 4)) || (p.row_map && !dev.alloc(&d_map, (size_t)M * 4)) ||
+      (p.nslab && !dev.alloc(&d_slabs, stride * p.nslab * 4)))
+    return fail(MX_ERR_HIP, "mx_kq_side_probe: device allocation");
+  HIPC(hipMemset(d_x, 0xFF, x_bytes));
+  HIPC(hipMemcpy(d_x, p.x, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_xq, 0xFF, xq_bytes));
+  HIPC(hipMemset(d_xd, 0xFF, xd_bytes));
+  HIPC(hipMemset(d_xb, 0xFF, xb_bytes));
+  if (norm) HIPC(hipMemcpy(d_w, p.w, (size_t)K * 4, hipMemcpyHostToDevice));
+  if (p.row_map) HIPC(hipMemcpy(d_map, p.row_map, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (p.nslab) HIPC(hipMemcpy(d_slabs, p.slabs, stride * p.nslab * 4, hipMemcpyHostToDevice));
+  const int rc = norm ? launch_rmsnorm_q8k(d_xq, d_xd, d_xb, d_x, d_w, d_map, M, K, p.eps, nullptr, d_slabs, p.nslab, stride)
+                      : launch_quantize_q8k(d_xq, d_xd, d_xb, d_x, ld, M, K, nullptr);
+  if (rc) {
+    hipDeviceSynchronize();
+    return fail(MX_ERR_ARG, std::string("mx_kq_side_probe: ") + (norm ? "launch_rmsnorm_q8k" : "launch_quantize_q8k") +
+                                " refused the shape");
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(p.xq_out, d_xq, xq_bytes, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.xd_out, d_xd, xd_bytes, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.xb_out, d_xb, xb_bytes, hipMemcpyDeviceToHost));
+  if (p.x_out) HIPC(hipMemcpy(p.x_out, d_x, x_bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -263,6 +263,34 @@ int launch_mkq_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream
 int launch_mkq_qkv_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s);
 // q/k/v split-K partial slabs -> sum in slab order -> RoPE + q / KV-cache stores (EPI_QKV's epilogue)
 void launch_qkv_finish(const MMArgs& a, const float* slabs, int nslab, size_t slab_stride, hipStream_t s);
+// The kernel launch_mkq reaches for a shape (a pure host function: launch_mkq and its sub-launchers dispatch
+// on its result and on nothing else).  on_load: a.xq == nullptr; norm: a.norm_w given; the row segments as in
+// MMArgs.  kind MKQ_NONE: launch_mkq refuses the shape.
+enum MkqKind : int {
+  MKQ_NONE = 0,
+  MKQ_QKV_PERS = 1,  // mkq_pers_seg_kernel<ks, nkw, tpw, EPI_QKV, u>: one token, q|k|v, quantised on load
+  MKQ_BD_TILE = 2,   // mkq_bd_tile_kernel<t, w, nkw (= K / 256), tpw, epi, u>: one token on load, whole-K waves
+  MKQ_PERS = 3,      // mkq_pers_kernel<t, ks, nkw, tpw, nb, epi, u, ql, bd>
+  MKQ_WIDE = 4,      // mkq_wide_kernel<t, w, nb, epi, u>: 17..32 rows, activations shared through LDS
+  MKQ_GEMV = 5,      // mkq_kernel<ks, 1, nb, epi, u, ql, bd> on grid (grid_x, grid_y)
+};
+// the MX_NO_KQ_* / MX_SLAB_TARGET switches (read once per process by mkq_env)
+struct MkqEnv {
+  bool no_bd_tile, no_pers, no_wide;
+  int slab_target;
+};
+const MkqEnv& mkq_env();
+// t: the type of a single-segment matrix (0: chosen per work-group from the segments); nkw: super-blocks per
+// wave and tile; tpw: tiles per work-group (MKQ_BD_TILE: per wave); w: waves that own whole tiles
+struct MkqPlan {
+  int kind, t, ks, nkw, tpw, nb, u, bd, ql, w, grid_x, grid_y;
+};
+MkqPlan mkq_plan(int epi, int M, int N, int K, bool on_load, bool norm, int kq_n, const int* kq_type,
+                 const int* kq_tile_end, const MkqEnv& env);
+// the split launch_mkq_slab / launch_mkq_qkv_slab take for a shape, -1 = refused (the conditions on the shape
+// alone; both also need pre-quantised rows)
+int mkq_slab_ks(int M, int N, int K, int kq_n, const int* kq_type, const MkqEnv& env);
+int mkq_qkv_slab_ks(int M, int N, int K, int kq_n, const int* kq_tile_end, const MkqEnv& env);
 // packed K-quant matrix (segments as in MMArgs) -> packed bf16 tiles [N/16][K/32] x 1 KiB (prefill GEMM)
 int launch_dequant_kq(uint16_t* dst, const void* W, int K, int kq_n, const int* type, const int* tile_end,
                       const size_t* off, hipStream_t s);

@@ -1396,135 +1396,225 @@ __global__ __launch_bounds__(64 * W) void mkq_bd_tile_kernel(MMArgs a) {
   }
 }
 
-// one token, q|k|v of a K-quant file (K 4096: 16 super-blocks = 8 waves x 2): 2 tiles per
-// work-group (Llama-3-8B: 192 groups) quantising on load; -1 if the shape has no such form
-static int launch_kq_qkv_pers(const MMArgs& a, hipStream_t s) {
-  constexpr bool off = false;
-  if (off || a.M != 1 || a.xq != nullptr || a.K != 4096 || (a.N / TILE_N) % 2) return -1;
-  for (int i = 0; i < a.kq_n; ++i)
-    if (a.kq_tile_end[i] % 2) return -1;
-  mkq_pers_seg_kernel<8, 2, 2, EPI_QKV, 4><<<a.N / TILE_N / 2, 512, 8 * QL_WAVE_BYTES, s>>>(a);
+// ---------------------------------------------------------------------------
+// Dispatch.  mkq_plan is the one place where a shape is matched to a kernel: launch_mkq and the launchers
+// below turn its fields into template arguments and grids and test no shape condition of their own.
+// ---------------------------------------------------------------------------
+const MkqEnv& mkq_env() {
+  // MX_NO_KQ_BD_TILE: the K-split persistent kernel's path; MX_NO_KQ_PERS: the one-tile-per-work-group
+  // kernel; MX_NO_KQ_WIDE: mkq_kernel at 17..32 rows and no slabs (tests compare the paths);
+  // MX_SLAB_TARGET: work-groups the 17..32-row split-K launches aim at (A/B)
+  static const MkqEnv e{getenv("MX_NO_KQ_BD_TILE") != nullptr, getenv("MX_NO_KQ_PERS") != nullptr,
+                        getenv("MX_NO_KQ_WIDE") != nullptr,
+                        getenv("MX_SLAB_TARGET") ? atoi(getenv("MX_SLAB_TARGET")) : 256};
+  return e;
+}
+
+bool mkq_can_quantize_on_load(int M, int K, bool norm) {
+  return M == 1 && K % 256 == 0 && (K / 256 + 7) / 8 <= QL_SB_MAX && (!norm || K / 16 <= 512);
+}
+
+MkqPlan mkq_plan(int epi, int M, int N, int K, bool on_load, bool norm, int kq_n, const int* type,
+                 const int* tile_end, const MkqEnv& env) {
+  MkqPlan p{};
+  if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || K < 256 || K % 256 || N < TILE_N || N % TILE_N) return p;
+  if (on_load && !mkq_can_quantize_on_load(M, K, norm)) return p;
+  if (kq_n < 1 || kq_n > 3 || tile_end[kq_n - 1] * TILE_N != N) return p;
+  for (int i = 0; i < kq_n; ++i)
+    if (!kq_tile_bytes(type[i]) || (i && tile_end[i] <= tile_end[i - 1])) return p;
+  const int ntiles = N / TILE_N, SB = K / 256;
+  p.t = kq_n == 1 ? type[0] : 0;
+  p.nb = 1, p.grid_y = 1;
+  // one token, q|k|v of a K-quant file (K 4096: 16 super-blocks = 8 waves x 2): 2 tiles per work-group
+  // (Llama-3-8B: 192 groups) quantising on load, every segment an even number of tiles
+  if (epi == EPI_QKV && M == 1 && on_load && K == 4096 && ntiles % 2 == 0) {
+    bool even = true;
+    for (int i = 0; i < kq_n; ++i) even = even && tile_end[i] % 2 == 0;
+    if (even) {
+      p.kind = MKQ_QKV_PERS, p.t = 0, p.ks = 8, p.nkw = 2, p.tpw = 2, p.u = 4, p.bd = 1, p.ql = 1, p.grid_x = ntiles / 2;
+      return p;
+    }
+  }
+  // <= 16 tokens, single-type gate/up or lm_head (17-32 rows, two column tiles: spills)
+  if (!env.no_pers && kq_n == 1 && M <= 16 && (epi == EPI_SWIGLU || epi == EPI_F32)) {
+    // one token quantised on load: mkq_bd_tile_kernel when the shape has an instantiation (K 4096 / 2048:
+    // Llama-3-8B, TinyLlama; K 8192 spills)
+    if (!env.no_bd_tile && M == 1 && on_load) {
+      int w = 0, tp = 1;
+      if (epi == EPI_SWIGLU) {
+        if (SB == 16 && ntiles <= 1792) w = 7;
+        else if (SB == 8 && ntiles <= 768) w = 3;
+      } else {
+        if (SB == 16 && ntiles <= 8192) w = 8, tp = 4;
+        else if (SB == 8 && ntiles <= 2048) w = 8;
+      }
+      if (w) {
+        p.kind = MKQ_BD_TILE, p.ks = 1, p.nkw = SB, p.tpw = tp, p.u = 8, p.bd = 1, p.ql = 1, p.w = w;
+        p.grid_x = (ntiles + w * tp - 1) / (w * tp);
+        return p;
+      }
+    }
+    // the Llama shapes: gate/up (K 4096, 1792 tiles / TinyLlama K 2048, 704), the lm_head (128256 / 32000
+    // rows); attn_output / ffn_down (256 tiles, one per work-group) keep mkq_kernel
+    int nkw = 0, tpw = 0, ub = 4;  // ub: the ring of the one-token (block-diagonal, weights only) form
+    if (epi == EPI_SWIGLU) {
+      if (SB == 16 && ntiles == 1792) nkw = 2, tpw = 7;
+      else if (SB == 8 && ntiles == 704) nkw = 1, tpw = 3, ub = 3;
+    } else {
+      if (SB == 16 && ntiles > 256 * 8) nkw = 2, tpw = 8;  // 16: spills
+      else if (SB == 8 && ntiles > 256 * 4) nkw = 1, tpw = 8;
+    }
+    if (nkw) {
+      p.kind = MKQ_PERS, p.ks = 8, p.nkw = nkw, p.tpw = tpw, p.ql = on_load, p.bd = M == 1, p.u = M == 1 ? ub : 2;
+      p.grid_x = (ntiles + tpw - 1) / tpw;
+      return p;
+    }
+  }
+  // 17..32 tokens, one-type matrix, gate/up or lm_head: the LDS-shared form, waves per work-group sized so
+  // the grid covers the 256 CUs (Llama-3-8B gate/up: 1792 = 7 x 256)
+  if (!env.no_wide && M > 16 && M <= 32 && kq_n == 1 && !on_load && SB % 4 == 0 && (epi == EPI_SWIGLU || epi == EPI_F32)) {
+    const int w = (ntiles % 7 == 0 && ntiles / 7 >= 200) ? 7 : (ntiles % 8 == 0 && ntiles / 8 >= 200) ? 8 : ntiles % 4 == 0 ? 4 : 0;
+    if (w) {
+      // ring 4 deep for Q4_K / Q5_K, 2 for Q6_K (its 4-deep ring spills)
+      p.kind = MKQ_WIDE, p.ks = 1, p.nkw = SB, p.tpw = 1, p.nb = 2, p.u = type[0] == 14 ? 2 : 4, p.w = w, p.grid_x = ntiles / w;
+      return p;
+    }
+  }
+  // one tile per work-group, 8 waves split K.  One token: each wave's whole slice of super-blocks in flight
+  // (U >= slice: 1, 2, 4, and quantising on load 7, 8), longer slices ring 2 deep; 2..16 tokens ring 2; more:
+  // two column tiles, U 1 (a 2-deep ring spills ~460 B/lane), grid.y groups of 32 tokens
+  p.kind = MKQ_GEMV, p.t = 0, p.ks = 8, p.nkw = (SB + 7) / 8, p.tpw = 1, p.grid_x = ntiles;
+  if (on_load || M == 1) {
+    const int per = p.nkw;
+    p.bd = 1, p.ql = on_load;
+    p.u = per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : (on_load && per <= 7) ? 7 : (on_load && per <= 8) ? 8 : 2;
+  } else if (M <= 16) {
+    p.u = 2;
+  } else {
+    p.nb = 2, p.u = 1, p.grid_y = M <= 32 ? 1 : (M + 31) / 32;
+  }
+  return p;
+}
+
+static int kq_slab_split(int ntiles, int SB, const MkqEnv& env) {
+  int ks = 1;
+  while (ks < 8 && (ntiles / 4) * ks * 2 <= env.slab_target && SB / (ks * 2) >= 4) ks *= 2;
+  return ks;
+}
+int mkq_slab_ks(int M, int N, int K, int kq_n, const int* type, const MkqEnv& env) {
+  if (env.no_wide || M <= 16 || M > 32 || kq_n != 1 || K < 256 || K % 256 || N < 64 || N % 64 || !kq_tile_bytes(type[0])) return -1;
+  const int ks = kq_slab_split(N / TILE_N, K / 256, env);
+  return ks < 2 ? -1 : ks;
+}
+int mkq_qkv_slab_ks(int M, int N, int K, int kq_n, const int* tile_end, const MkqEnv& env) {
+  if (env.no_wide || M <= 16 || M > 32 || kq_n < 1 || kq_n > 3 || K < 256 || K % 256 || N < 64 || N % 64) return -1;
+  for (int i = 0; i < kq_n; ++i)
+    if (tile_end[i] % 4) return -1;
+  return kq_slab_split(N / TILE_N, K / 256, env);
+}
+
+static int launch_kq_qkv_pers(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  if (p.ks != 8 || p.nkw != 2 || p.tpw != 2 || p.u != 4) return -1;  // the one instantiation: the plan must name it
+  mkq_pers_seg_kernel<8, 2, 2, EPI_QKV, 4><<<p.grid_x, 512, 8 * QL_WAVE_BYTES, s>>>(a);
   return 0;
 }
 
 // U: ring depth for 2..16 tokens; UB: one token (block-diagonal, weights only in the ring)
 // (one token: KSB waves per work-group, each NKW * 8 / KSB super-blocks of every tile)
 template <int T, int NKW, int TPW, int NB, int EPI, int U, int UB, int KSB = 8>
-static void launch_kq_pers_t(const MMArgs& a, int ntiles, hipStream_t s) {
-  const int grid = (ntiles + TPW - 1) / TPW;
+static int launch_kq_pers_t(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  const int grid = p.grid_x;
   constexpr int NKB = NKW * 8 / KSB;
-  if (a.xq == nullptr)  // one token, quantised on load
+  if (p.ks != KSB || p.nb != NB || p.u != (p.bd ? UB : U)) return -1;  // the plan must name what is instantiated
+  if (p.ql)  // one token, quantised on load
     mkq_pers_kernel<T, KSB, NKB, TPW, NB, EPI, UB, true, true><<<grid, 64 * KSB, KSB * QL_WAVE_BYTES, s>>>(a);
-  else if (a.M == 1)
+  else if (p.bd)
     mkq_pers_kernel<T, KSB, NKB, TPW, NB, EPI, UB, false, true><<<grid, 64 * KSB, 0, s>>>(a);
   else
     mkq_pers_kernel<T, 8, NKW, TPW, NB, EPI, U, false, false><<<grid, 512, 0, s>>>(a);
+  return 0;
 }
 
-// single-type matrices of the Llama shapes: gate/up (K 4096, 1792 tiles / TinyLlama K 2048, 704),
-// attn_output / ffn_down (h 4096: 256 tiles, one per work-group: the KS split is mkq_kernel's), the
-// lm_head (128256 / 32000 rows); -1 = no instantiation (mkq_kernel runs)
 template <int T, int NB, int EPI>
-static int launch_kq_pers_ty(const MMArgs& a, int ntiles, hipStream_t s) {
-  const int SB = a.K / 256;
+static int launch_kq_pers_ty(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
   if constexpr (EPI == EPI_SWIGLU) {
-    if (SB == 16 && ntiles == 1792) return launch_kq_pers_t<T, 2, 7, NB, EPI, 2, 4>(a, ntiles, s), 0;
-    if (SB == 8 && ntiles == 704) return launch_kq_pers_t<T, 1, 3, NB, EPI, 2, 3>(a, ntiles, s), 0;
+    if (p.nkw == 2 && p.tpw == 7) return launch_kq_pers_t<T, 2, 7, NB, EPI, 2, 4>(a, p, s);
+    if (p.nkw == 1 && p.tpw == 3) return launch_kq_pers_t<T, 1, 3, NB, EPI, 2, 3>(a, p, s);
   } else {
-    if (SB == 16 && ntiles > 256 * 8) return launch_kq_pers_t<T, 2, 8, NB, EPI, 2, 4>(a, ntiles, s), 0;  // 16: spills
-    if (SB == 8 && ntiles > 256 * 4) return launch_kq_pers_t<T, 1, 8, NB, EPI, 2, 4>(a, ntiles, s), 0;
+    if (p.nkw == 2 && p.tpw == 8) return launch_kq_pers_t<T, 2, 8, NB, EPI, 2, 4>(a, p, s);
+    if (p.nkw == 1 && p.tpw == 8) return launch_kq_pers_t<T, 1, 8, NB, EPI, 2, 4>(a, p, s);
   }
   return -1;
 }
 
-// one token quantised on load, single-type gate/up or lm_head: mkq_bd_tile_kernel when the shape has
-// an instantiation (K 4096 / 2048: Llama-3-8B, TinyLlama; K 8192 spills), else -1
 template <int T, int EPI>
-static int launch_kq_bd_tile_t(const MMArgs& a, int ntiles, hipStream_t s) {
-  const int SB = a.K / 256;
+static int launch_kq_bd_tile_t(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
   auto go = [&](auto wc, auto sbc, auto tc) {
     constexpr int W = decltype(wc)::value, S = decltype(sbc)::value, TP = decltype(tc)::value;
-    const int grid = (ntiles + W * TP - 1) / (W * TP);
-    mkq_bd_tile_kernel<T, W, S, TP, EPI, 8><<<grid, 64 * W, 0, s>>>(a);
+    if (p.w != W || p.nkw != S || p.tpw != TP || p.u != 8) return -1;
+    mkq_bd_tile_kernel<T, W, S, TP, EPI, 8><<<p.grid_x, 64 * W, 0, s>>>(a);
     return 0;
   };
   using std::integral_constant;
   if constexpr (EPI == EPI_SWIGLU) {
-    if (SB == 16 && ntiles <= 1792) return go(integral_constant<int, 7>{}, integral_constant<int, 16>{}, integral_constant<int, 1>{});
-    if (SB == 8 && ntiles <= 768) return go(integral_constant<int, 3>{}, integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    if (p.w == 7) return go(integral_constant<int, 7>{}, integral_constant<int, 16>{}, integral_constant<int, 1>{});
+    return go(integral_constant<int, 3>{}, integral_constant<int, 8>{}, integral_constant<int, 1>{});
   } else {
-    if (SB == 16 && ntiles <= 8192) return go(integral_constant<int, 8>{}, integral_constant<int, 16>{}, integral_constant<int, 4>{});
-    if (SB == 8 && ntiles <= 2048) return go(integral_constant<int, 8>{}, integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    if (p.tpw == 4) return go(integral_constant<int, 8>{}, integral_constant<int, 16>{}, integral_constant<int, 4>{});
+    return go(integral_constant<int, 8>{}, integral_constant<int, 8>{}, integral_constant<int, 1>{});
+  }
+}
+static int launch_kq_bd_tile(int epi, const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  if (epi == EPI_SWIGLU)
+    return p.t == 12 ? launch_kq_bd_tile_t<12, EPI_SWIGLU>(a, p, s)
+         : p.t == 13 ? launch_kq_bd_tile_t<13, EPI_SWIGLU>(a, p, s)
+                     : launch_kq_bd_tile_t<14, EPI_SWIGLU>(a, p, s);
+  if (epi == EPI_F32)
+    return p.t == 12 ? launch_kq_bd_tile_t<12, EPI_F32>(a, p, s)
+         : p.t == 13 ? launch_kq_bd_tile_t<13, EPI_F32>(a, p, s)
+                     : launch_kq_bd_tile_t<14, EPI_F32>(a, p, s);
+  return -1;
+}
+
+static int launch_kq_pers(int epi, const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  const int t = p.t;
+  switch (epi) {
+    case EPI_SWIGLU:
+      return t == 12 ? launch_kq_pers_ty<12, 1, EPI_SWIGLU>(a, p, s)
+           : t == 13 ? launch_kq_pers_ty<13, 1, EPI_SWIGLU>(a, p, s)
+                     : launch_kq_pers_ty<14, 1, EPI_SWIGLU>(a, p, s);
+    case EPI_F32:
+      return t == 12 ? launch_kq_pers_ty<12, 1, EPI_F32>(a, p, s)
+           : t == 13 ? launch_kq_pers_ty<13, 1, EPI_F32>(a, p, s)
+                     : launch_kq_pers_ty<14, 1, EPI_F32>(a, p, s);
   }
   return -1;
 }
-static int launch_kq_bd_tile(int epi, const MMArgs& a, int ntiles, hipStream_t s) {
-  static const bool off = getenv("MX_NO_KQ_BD_TILE") != nullptr;  // tests: the K-split persistent kernel's path
-  if (off || a.M != 1 || a.xq != nullptr || a.kq_n != 1 || !a.xf || (a.norm_w && (!a.ssq || a.np * 16 != a.K)))
-    return -1;
-  const int t = a.kq_type[0];
-  if (epi == EPI_SWIGLU)
-    return t == 12 ? launch_kq_bd_tile_t<12, EPI_SWIGLU>(a, ntiles, s)
-         : t == 13 ? launch_kq_bd_tile_t<13, EPI_SWIGLU>(a, ntiles, s)
-                   : launch_kq_bd_tile_t<14, EPI_SWIGLU>(a, ntiles, s);
-  if (epi == EPI_F32)
-    return t == 12 ? launch_kq_bd_tile_t<12, EPI_F32>(a, ntiles, s)
-         : t == 13 ? launch_kq_bd_tile_t<13, EPI_F32>(a, ntiles, s)
-                   : launch_kq_bd_tile_t<14, EPI_F32>(a, ntiles, s);
-  return -1;
-}
 
-static int launch_kq_pers(int epi, const MMArgs& a, int ntiles, hipStream_t s) {
-  // MX_NO_KQ_PERS: the one-tile-per-work-group kernel (read per launch: tests compare the two)
-  static const bool off = getenv("MX_NO_KQ_PERS") != nullptr;  // tests: the grouped kernel's path
-  if (off || a.kq_n != 1 || a.M > 16) return -1;  // 17-32 rows (two column tiles): spills
-  if (launch_kq_bd_tile(epi, a, ntiles, s) == 0) return 0;
-  const int t = a.kq_type[0];
-  auto by_nb = [&](auto nb) -> int {
-    constexpr int NB = decltype(nb)::value;
-    switch (epi) {
-      case EPI_SWIGLU:
-        return t == 12 ? launch_kq_pers_ty<12, NB, EPI_SWIGLU>(a, ntiles, s)
-             : t == 13 ? launch_kq_pers_ty<13, NB, EPI_SWIGLU>(a, ntiles, s)
-                       : launch_kq_pers_ty<14, NB, EPI_SWIGLU>(a, ntiles, s);
-      case EPI_F32:
-        return t == 12 ? launch_kq_pers_ty<12, NB, EPI_F32>(a, ntiles, s)
-             : t == 13 ? launch_kq_pers_ty<13, NB, EPI_F32>(a, ntiles, s)
-                       : launch_kq_pers_ty<14, NB, EPI_F32>(a, ntiles, s);
-    }
-    return -1;
-  };
-  return by_nb(std::integral_constant<int, 1>{});
-}
-
-// one token, one tile per work-group: 8 waves split K, each with its whole slice of super-blocks in
-// flight (U >= slice: 1, 2, 4, 7, 8); longer slices ring 2 deep
+// one token, one tile per work-group, block-diagonal form: ring depth p.u
 template <int EPI, bool QL>
-static void launch_mkq_bd(const MMArgs& a, int ntiles, hipStream_t s) {
-  const int per = (a.K / 256 + 7) / 8;
-  const dim3 grid(ntiles, 1);
+static int launch_mkq_bd(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid_x, 1);
   const size_t lds = QL ? 8 * QL_WAVE_BYTES : 0;
-  if (per <= 1) mkq_kernel<8, 1, 1, EPI, 1, QL, true><<<grid, 512, lds, s>>>(a);
-  else if (per <= 2) mkq_kernel<8, 1, 1, EPI, 2, QL, true><<<grid, 512, lds, s>>>(a);
-  else if (per <= 4) mkq_kernel<8, 1, 1, EPI, 4, QL, true><<<grid, 512, lds, s>>>(a);
-  else if (QL && per <= 7) mkq_kernel<8, 1, 1, EPI, QL ? 7 : 2, QL, true><<<grid, 512, lds, s>>>(a);
-  else if (QL && per <= 8) mkq_kernel<8, 1, 1, EPI, QL ? 8 : 2, QL, true><<<grid, 512, lds, s>>>(a);
-  else mkq_kernel<8, 1, 1, EPI, 2, QL, true><<<grid, 512, lds, s>>>(a);  // (quantise-on-load slices are <= 8)
+  switch (p.u) {
+    case 1: mkq_kernel<8, 1, 1, EPI, 1, QL, true><<<grid, 512, lds, s>>>(a); return 0;
+    case 2: mkq_kernel<8, 1, 1, EPI, 2, QL, true><<<grid, 512, lds, s>>>(a); return 0;
+    case 4: mkq_kernel<8, 1, 1, EPI, 4, QL, true><<<grid, 512, lds, s>>>(a); return 0;
+    case 7: mkq_kernel<8, 1, 1, EPI, QL ? 7 : 2, QL, true><<<grid, 512, lds, s>>>(a); return 0;
+    case 8: mkq_kernel<8, 1, 1, EPI, QL ? 8 : 2, QL, true><<<grid, 512, lds, s>>>(a); return 0;
+  }
+  return -1;
 }
 
 template <int EPI>
-static void launch_mkq_epi(const MMArgs& a, int ntiles, hipStream_t s) {
-  if (a.xq == nullptr) {  // one token, quantised on load (launch_mkq checked the slice fits)
-    launch_mkq_bd<EPI, true>(a, ntiles, s);
-  } else if (a.M == 1) {
-    launch_mkq_bd<EPI, false>(a, ntiles, s);
-  } else if (a.M <= 16) {
-    mkq_kernel<8, 1, 1, EPI, 2, false><<<dim3(ntiles, 1), 512, 0, s>>>(a);
-  } else if (a.M <= 32) {  // (a 2-deep ring spills ~460 B/lane at two column tiles: U = 1)
-    mkq_kernel<8, 1, 2, EPI, 1, false><<<dim3(ntiles, 1), 512, 0, s>>>(a);
-  } else {
-    mkq_kernel<8, 1, 2, EPI, 1, false><<<dim3(ntiles, (a.M + 31) / 32), 512, 0, s>>>(a);
-  }
+static int launch_mkq_epi(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  if (p.ql) return launch_mkq_bd<EPI, true>(a, p, s);  // one token, quantised on load
+  if (p.bd) return launch_mkq_bd<EPI, false>(a, p, s);
+  const dim3 grid(p.grid_x, p.grid_y);
+  if (p.nb == 1 && p.u == 2) mkq_kernel<8, 1, 1, EPI, 2, false><<<grid, 512, 0, s>>>(a);
+  else if (p.nb == 2 && p.u == 1) mkq_kernel<8, 1, 2, EPI, 1, false><<<grid, 512, 0, s>>>(a);
+  else return -1;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1780,8 +1870,9 @@ static void launch_kq_wide_t(const MMArgs& a, int ntiles, hipStream_t s, int ksp
 }
 
 template <int EPI>
-static int launch_kq_wide_epi(const MMArgs& a, int ntiles, hipStream_t s) {
-  const int t = a.kq_type[0];
+static int launch_kq_wide_epi(const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  const int t = p.t, ntiles = p.grid_x * p.w;
+  if (p.nb != 2 || p.u != (t == 14 ? 2 : 4)) return -1;  // launch_kq_wide_t's instantiation: the plan must name it
   auto by_w = [&](auto wc) {
     constexpr int W = decltype(wc)::value;
     if (t == 12) launch_kq_wide_t<12, W, EPI>(a, ntiles, s);
@@ -1789,39 +1880,27 @@ static int launch_kq_wide_epi(const MMArgs& a, int ntiles, hipStream_t s) {
     else launch_kq_wide_t<14, W, EPI>(a, ntiles, s);
     return 0;
   };
-  // waves per work-group sized so the grid covers the 256 CUs (Llama-3-8B gate/up: 1792 = 7 x 256)
-  if (ntiles % 7 == 0 && ntiles / 7 >= 200) return by_w(std::integral_constant<int, 7>{});
-  if (ntiles % 8 == 0 && ntiles / 8 >= 200) return by_w(std::integral_constant<int, 8>{});
-  if (ntiles % 4 == 0) return by_w(std::integral_constant<int, 4>{});
+  if (p.w == 7) return by_w(std::integral_constant<int, 7>{});
+  if (p.w == 8) return by_w(std::integral_constant<int, 8>{});
+  if (p.w == 4) return by_w(std::integral_constant<int, 4>{});
   return -1;
 }
 
-// 17..32 tokens, one-type matrix, gate/up or lm_head: the LDS-shared form (MX_NO_KQ_WIDE=1: mkq_kernel)
-static int launch_kq_wide(int epi, const MMArgs& a, int ntiles, hipStream_t s) {
-  static const bool off = getenv("MX_NO_KQ_WIDE") != nullptr;
-  if (off || a.M <= 16 || a.M > 32 || a.kq_n != 1 || !a.xq || !a.xd || !a.xb || (a.K / 256) % 4) return -1;
-  if (epi == EPI_SWIGLU) return launch_kq_wide_epi<EPI_SWIGLU>(a, ntiles, s);
-  if (epi == EPI_F32) return launch_kq_wide_epi<EPI_F32>(a, ntiles, s);
+static int launch_kq_wide(int epi, const MMArgs& a, const MkqPlan& p, hipStream_t s) {
+  if (epi == EPI_SWIGLU) return launch_kq_wide_epi<EPI_SWIGLU>(a, p, s);
+  if (epi == EPI_F32) return launch_kq_wide_epi<EPI_F32>(a, p, s);
   return -1;
-}
-
-// work-groups the 17..32-row split-K launches aim at (MX_SLAB_TARGET, A/B)
-static int kq_slab_target() {
-  static const int t = getenv("MX_SLAB_TARGET") ? atoi(getenv("MX_SLAB_TARGET")) : 256;
-  return t;
 }
 
 // 17..32 tokens, attn_output / ffn_down of a K-quant file (256 tiles for h 4096): 4-wave groups with K
-// split over grid.y until ~256 work-groups, partials into slabs [ksplit][token][N] that the next
+// split over grid.y until ~256 work-groups (mkq_slab_ks), partials into slabs [ksplit][token][N] that the next
 // RMS_NORM + Q8_K launch (launch_rmsnorm_q8k with slabs) folds into the residual stream in slab
 // order.  Returns the split, or -1 (the caller runs mkq_kernel's in-place EPI_RESID instead).
 int launch_mkq_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s) {
-  static const bool off = getenv("MX_NO_KQ_WIDE") != nullptr;
-  if (off || a.M <= 16 || a.M > 32 || a.kq_n != 1 || !a.xq || !a.xd || !a.xb || a.K % 256 || a.N % 64) return -1;
-  const int ntiles = a.N / TILE_N, SB = a.K / 256;
-  int ks = 1;
-  while (ks < 8 && (ntiles / 4) * ks * 2 <= kq_slab_target() && SB / (ks * 2) >= 4) ks *= 2;
+  if (!a.xq || !a.xd || !a.xb) return -1;
+  const int ks = mkq_slab_ks(a.M, a.N, a.K, a.kq_n, a.kq_type, mkq_env());
   if (ks < 2) return -1;
+  const int ntiles = a.N / TILE_N;
   MMArgs p = a;
   p.out = slabs;
   p.ldo = a.N;
@@ -1829,56 +1908,42 @@ int launch_mkq_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream
   const int t = a.kq_type[0];
   if (t == 12) launch_kq_wide_t<12, 4, EPI_SLAB>(p, ntiles, s, ks);
   else if (t == 13) launch_kq_wide_t<13, 4, EPI_SLAB>(p, ntiles, s, ks);
-  else if (t == 14) launch_kq_wide_t<14, 4, EPI_SLAB>(p, ntiles, s, ks);
-  else return -1;
+  else launch_kq_wide_t<14, 4, EPI_SLAB>(p, ntiles, s, ks);
   return ks;
 }
 
-// 17..32 tokens, q|k|v of a K-quant file (segments of different types): 4-wave groups, K split in two,
-// partial slabs [2][token][N] that the decode attention (FIN) or launch_qkv_finish completes.
-// Returns the split or -1 (the caller runs mkq_kernel's EPI_QKV instead).
+// 17..32 tokens, q|k|v of a K-quant file (segments of different types): 4-wave groups, K split as
+// launch_mkq_slab's (mkq_qkv_slab_ks; 1: no split), partial slabs [ks][token][N] that the decode attention
+// (FIN) or launch_qkv_finish completes.  Returns the split or -1 (the caller runs mkq_kernel's EPI_QKV instead).
 int launch_mkq_qkv_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream_t s) {
-  static const bool off = getenv("MX_NO_KQ_WIDE") != nullptr;
-  if (off || a.M <= 16 || a.M > 32 || !a.xq || !a.xd || !a.xb || a.K % 256 || a.N % 64) return -1;
-  for (int i = 0; i < a.kq_n; ++i)
-    if (a.kq_tile_end[i] % 4) return -1;
-  const int ntiles = a.N / TILE_N, SB = a.K / 256;
-  int ks = 1;
-  while (ks < 8 && (ntiles / 4) * ks * 2 <= kq_slab_target() && SB / (ks * 2) >= 4) ks *= 2;
+  if (!a.xq || !a.xd || !a.xb) return -1;
+  const int ks = mkq_qkv_slab_ks(a.M, a.N, a.K, a.kq_n, a.kq_tile_end, mkq_env());
+  if (ks < 1) return -1;
   MMArgs p = a;
   p.out = slabs;
   p.ldo = a.N;
   p.slab_stride = slab_stride;
-  mkq_wide_seg_kernel<4, 2, EPI_SLAB><<<dim3(ntiles / 4, ks), 256, 0, s>>>(p);
+  mkq_wide_seg_kernel<4, 2, EPI_SLAB><<<dim3(a.N / TILE_N / 4, ks), 256, 0, s>>>(p);
   return ks;
 }
 
-bool mkq_can_quantize_on_load(int M, int K, bool norm) {
-  return M == 1 && K % 256 == 0 && (K / 256 + 7) / 8 <= QL_SB_MAX && (!norm || K / 16 <= 512);
-}
-
 int launch_mkq(int epi, const MMArgs& a, hipStream_t s) {
-  if (a.M < 1 || a.K % 256 || a.N % TILE_N) return -1;
-  if (a.xq == nullptr) {  // quantise on load
-    if (!a.xf || !mkq_can_quantize_on_load(a.M, a.K, a.norm_w != nullptr) ||
-        (a.norm_w && (!a.ssq || a.np * 16 != a.K)))
-      return -1;
-  } else if (!a.xd || !a.xb) {
-    return -1;
-  }
-  if (a.kq_n < 1 || a.kq_n > 3 || a.kq_tile_end[a.kq_n - 1] * TILE_N != a.N) return -1;
-  for (int i = 0; i < a.kq_n; ++i)
-    if (!kq_tile_bytes(a.kq_type[i]) || (i && a.kq_tile_end[i] <= a.kq_tile_end[i - 1])) return -1;
+  const bool on_load = a.xq == nullptr;
+  if (on_load ? (!a.xf || (a.norm_w && (!a.ssq || a.np * 16 != a.K))) : (!a.xd || !a.xb)) return -1;
   if (epi == EPI_SWIGLU && !a.actf) return -1;
-  const int ntiles = a.N / TILE_N;
-  if (epi == EPI_QKV && launch_kq_qkv_pers(a, s) == 0) return 0;
-  if (launch_kq_pers(epi, a, ntiles, s) == 0) return 0;
-  if (launch_kq_wide(epi, a, ntiles, s) == 0) return 0;
-  switch (epi) {
-    case EPI_F32: launch_mkq_epi<EPI_F32>(a, ntiles, s); return 0;
-    case EPI_RESID: launch_mkq_epi<EPI_RESID>(a, ntiles, s); return 0;
-    case EPI_QKV: launch_mkq_epi<EPI_QKV>(a, ntiles, s); return 0;
-    case EPI_SWIGLU: launch_mkq_epi<EPI_SWIGLU>(a, ntiles, s); return 0;
+  const MkqPlan p = mkq_plan(epi, a.M, a.N, a.K, on_load, a.norm_w != nullptr, a.kq_n, a.kq_type, a.kq_tile_end, mkq_env());
+  switch (p.kind) {
+    case MKQ_QKV_PERS: return launch_kq_qkv_pers(a, p, s);
+    case MKQ_BD_TILE: return launch_kq_bd_tile(epi, a, p, s);
+    case MKQ_PERS: return launch_kq_pers(epi, a, p, s);
+    case MKQ_WIDE: return launch_kq_wide(epi, a, p, s);
+    case MKQ_GEMV:
+      switch (epi) {
+        case EPI_F32: return launch_mkq_epi<EPI_F32>(a, p, s);
+        case EPI_RESID: return launch_mkq_epi<EPI_RESID>(a, p, s);
+        case EPI_QKV: return launch_mkq_epi<EPI_QKV>(a, p, s);
+        case EPI_SWIGLU: return launch_mkq_epi<EPI_SWIGLU>(a, p, s);
+      }
   }
   return -1;
 }

@@ -22,8 +22,10 @@ MX_ERR_ARG, MX_ERR_HIP, MX_ERR_MODEL, MX_ERR_CTX, MX_ERR_NOTFOUND, MX_ERR_STATE 
 MX_DEBUG_STOPPED = 1  # a forward cut short by debug_stop (include/mx_engine.h): raised, never silent
 FINISH_LENGTH, FINISH_STOP, FINISH_ERROR = 0, 1, 2
 
+# the K-quant kernel probes, named in a list of their own (tests/test_kq_kernel_gpu.py) and part of EXPORTS
+EXPORTS_KQ = ["mx_kq_matmul_probe", "mx_kq_matmul_plan", "mx_kq_side_probe"]
 # every symbol include/mx_engine.h declares (checked by tests/test_abi.py)
-EXPORTS = [
+EXPORTS = EXPORTS_KQ + [
     "mx_opts_default", "mx_sampling_default", "mx_last_error", "mx_engine_create", "mx_engine_destroy", "mx_gguf_check",
     "mx_engine_info", "mx_forward_logits", "mx_forward_rows", "mx_forward_topk", "mx_submit", "mx_wait", "mx_submit_batch", "mx_poll", "mx_cancel", "mx_batch_create",
     "mx_batch_step", "mx_batch_ids_device", "mx_batch_bind_ids", "mx_batch_tokens", "mx_batch_destroy", "mx_stage_rows",
@@ -165,6 +167,35 @@ class MxQ8Plan(ctypes.Structure):
                                               "slab_ks", "can_on_load")]
 
 
+class MxKqMatmulArgs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "epi", "M", "N", "K", "act", "kq_n")] + \
+               [("kq_type", ctypes.c_int32 * 3), ("kq_tile_end", ctypes.c_int32 * 3),
+                ("w", ctypes.c_void_p), ("xf", ctypes.c_void_p), ("xrows", ctypes.c_int32), ("ldx", ctypes.c_int32),
+                ("norm_w", ctypes.c_void_p), ("eps", ctypes.c_float), ("row_map", ctypes.c_void_p),
+                ("ssq_in", ctypes.c_void_p), ("want_ssq", ctypes.c_int32)] + \
+               [(n, ctypes.c_int32) for n in ("n_head", "n_head_kv", "head_dim", "n_ctx", "n_slots")] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "slot", "rope_cs", "kcache", "vcache", "resid", "fold_w", "out",
+                                               "ssq_out", "slabs_out")] + \
+               [("slabs_cap", ctypes.c_uint64)] + \
+               [(n, ctypes.c_void_p) for n in ("split_out", "packed_out", "xq_out", "xd_out", "xb_out", "nxq_out",
+                                               "nxd_out", "nxb_out")]
+
+
+class MxKqPlan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "t", "ks", "nkw", "tpw", "nb", "u", "bd", "ql", "w", "grid_x",
+                                              "grid_y", "slab_ks", "qkv_slab_ks", "can_on_load")]
+
+
+class MxKqSideArgs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "type", "N", "K")] + \
+               [("blocks", ctypes.c_void_p), ("pack", ctypes.c_int32), ("offset", ctypes.c_int32),
+                ("kq_n", ctypes.c_int32), ("kq_type", ctypes.c_int32 * 3), ("kq_tile_end", ctypes.c_int32 * 3),
+                ("ids", ctypes.c_void_p), ("M", ctypes.c_int32), ("rows", ctypes.c_int32), ("ld", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("row_map", ctypes.c_void_p), ("eps", ctypes.c_float),
+                ("slabs", ctypes.c_void_p), ("nslab", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("out", "ssq_out", "xq_out", "xd_out", "xb_out", "x_out")]
+
+
 def sampling(temperature: float = 0.0, top_k: int = 40, top_p: float = 0.95, min_p: float = 0.05,
              repeat_penalty: float = 1.0, repeat_last_n: int = 64, seed: Optional[int] = None,
              ignore_eos: bool = False, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> MxSampling:
@@ -269,6 +300,9 @@ def lib() -> ctypes.CDLL:
         L.mx_q8_matmul_probe.argtypes = [i32, P(MxQ8MatmulArgs)]
         L.mx_q8_matmul_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, P(MxQ8Plan)]
         L.mx_q8_side_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp]
+        L.mx_kq_matmul_probe.argtypes = [i32, P(MxKqMatmulArgs)]
+        L.mx_kq_matmul_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, P(MxKqPlan)]
+        L.mx_kq_side_probe.argtypes = [i32, P(MxKqSideArgs)]
         L.mx_submit_spec.argtypes = [vp, vp, i32, P(MxSampling), i32, i32, i32, P(u64)]
         L.mx_spec_stats.argtypes = [vp, u64, P(MxSpecCounts)]
         L.mx_draft_probe.argtypes = [i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -893,6 +927,312 @@ def q8_embed_probe(blocks, ids, want_ssq: bool = True, device: int = 0):
     _check(lib().mx_q8_side_probe(device, 1, N, K, ba.ctypes.data, ia.ctypes.data, M, ob.ctypes.data,
                                   sq.ctypes.data if sq is not None else None))
     return ob[:M], ob[M:].view(np.uint32), (sq[:M] if sq is not None else None), (sq[M:] if sq is not None else None)
+
+
+KQ_KIND = {0: "none", 1: "qkv_pers", 2: "bd_tile", 3: "pers", 4: "wide", 5: "mkq"}
+KQ_BLOCK_BYTES = {12: 144, 13: 176, 14: 210}   # GGUF Q4_K / Q5_K / Q6_K bytes per 256 weights
+KQ_TILE_BYTES = {12: 2368, 13: 2880, 14: 3360}  # packed 16-row x 256-k tile (kquant.hip)
+KQ_NO_BD_TILE, KQ_NO_PERS, KQ_NO_WIDE = 1, 2, 4  # kq_matmul_plan flags: the MX_NO_KQ_* switches as if set
+
+
+def _kq_segments(segs, N=None):
+    """[(type, tile_end), ...] -> (kq_n, c_int32[3] types, c_int32[3] ends); a bare type with N: one segment."""
+    if isinstance(segs, int):
+        segs = [(segs, N // 16)]
+    segs = list(segs)
+    if not 1 <= len(segs) <= 3:
+        raise ValueError("1..3 row segments expected")
+    ty, te = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+    for i, (t, e) in enumerate(segs):
+        ty[i], te[i] = t, e
+    return len(segs), ty, te
+
+
+def kq_matmul_plan(epi: int, M: int, N: int, K: int, segs, on_load: bool = False, norm: bool = False,
+                   flags: int = -1) -> dict:
+    """The kernel a K-quant shape reaches (mx_kq_matmul_plan; no GPU): kind (a KQ_KIND name) and the fields of
+    mx_kq_plan.  segs: a ggml type (one segment) or [(type, tile_end), ...]; flags: -1 = this process's MX_NO_KQ_*
+    switches, else KQ_NO_* bits."""
+    n, ty, te = _kq_segments(segs, N)
+    pl = MxKqPlan()
+    _check(lib().mx_kq_matmul_plan(epi, M, N, K, int(bool(on_load)), int(bool(norm)), n, ctypes.addressof(ty),
+                                   ctypes.addressof(te), flags, ctypes.byref(pl)))
+    d = {f: getattr(pl, f) for f, _ in MxKqPlan._fields_}
+    d["kind"] = KQ_KIND[d["kind"]]
+    d["can_on_load"] = bool(d["can_on_load"])
+    return d
+
+
+class KqResult:
+    """out / guard as MatmulResult (always f32); xq int8 [M][K] (permuted within super-blocks), xd f32 [M][K/256],
+    xb f32 [M][K/32] with their guards; split, ssq [M][N/16] + ssq_guard, slabs [ks][M][N], packed (uint8);
+    nxq / nxd / nxb (+ guards): the folding norm's Q8_K rows on path 1 (N % 256 == 0, N <= 4096); kcache / vcache."""
+    out = guard = ssq = ssq_guard = slabs = packed = kcache = vcache = None
+    xq = xd = xb = xq_guard = xd_guard = xb_guard = None
+    nxq = nxd = nxb = nxq_guard = nxd_guard = nxb_guard = None
+    split = 0
+
+
+def kq_matmul_probe(path: int, epi: int, w, xf, segs, *, act: int = 0, N: Optional[int] = None,
+                    K: Optional[int] = None, M: Optional[int] = None, ldx: int = 0, norm_w=None, eps: float = 0.0,
+                    row_map=None, ssq_in=None, resid=None, fold_w=None, qkv=None, want_ssq: bool = False,
+                    want_slabs: bool = False, want_packed: bool = False, out=None, device: int = 0) -> KqResult:
+    """A production K-quant launcher on caller-supplied operands (include/mx_engine.h mx_kq_matmul_probe).
+    w: raw GGUF blocks, flat uint8 (the row segments laid end to end), None on path -1; segs: a ggml type (one
+    segment; N then required) or [(type, tile_end), ...]; xf f32 rows; act 0 quantise (xf [M][ldx]), 1 RMS_NORM +
+    quantise (norm_w, row_map), 2 one token quantised on load (norm_w, ssq_in optional).  N / K / M override what
+    the arrays imply (tests of refusals)."""
+    fa = np.ascontiguousarray(xf, dtype=np.float32)
+    if fa.ndim != 2:
+        raise ValueError("xf [rows][ld] expected")
+    if K is None:
+        if ldx:
+            raise ValueError("K is required when ldx is given")
+        K = fa.shape[1]
+    a = MxKqMatmulArgs()
+    wa = None
+    if w is not None:
+        wa = np.ascontiguousarray(w, dtype=np.uint8).reshape(-1)
+        if N is None:
+            if isinstance(segs, int):
+                raise ValueError("N is required with a bare type")
+            N = 16 * list(segs)[-1][1]
+        a.kq_n, ty, te = _kq_segments(segs, N)
+        need, t0 = 0, 0
+        for i in range(a.kq_n):
+            a.kq_type[i], a.kq_tile_end[i] = ty[i], te[i]
+            need += max(te[i] - t0, 0) * 16 * (K // 256) * KQ_BLOCK_BYTES.get(ty[i], 0)
+            t0 = te[i]
+        if wa.size < need:
+            raise ValueError(f"w holds {wa.size} bytes, the segments need {need}")
+    if N is None:
+        N = 0
+    ma = None
+    if row_map is not None:
+        ma = _i32(row_map)
+        a.row_map = ma.ctypes.data
+    if M is None:
+        M = len(ma) if ma is not None else fa.shape[0]
+    a.path, a.epi, a.M, a.N, a.K, a.act = path, epi, M, N, K, act
+    a.w = wa.ctypes.data if wa is not None else None
+    a.xf, a.xrows, a.ldx = fa.ctypes.data, (fa.shape[0] if act == 1 else 0), ldx
+    if fa.shape[1] != (ldx or K):
+        raise ValueError("xf row length")
+    if act != 1 and fa.shape[0] < (1 if act == 2 else M):  # the rows the probe copies (act 1: xrows, checked in C)
+        raise ValueError("xf holds fewer rows than the probe reads")
+    keep = [wa, fa, ma]
+    if norm_w is not None:
+        na = np.ascontiguousarray(norm_w, dtype=np.float32)
+        if na.size != K:
+            raise ValueError("norm_w [K] expected")
+        a.norm_w = na.ctypes.data
+        keep.append(na)
+    if ssq_in is not None:
+        qa_ = np.ascontiguousarray(ssq_in, dtype=np.float32)
+        if qa_.size != K // 16:
+            raise ValueError("ssq_in [K/16] expected")
+        a.ssq_in = qa_.ctypes.data
+        keep.append(qa_)
+    a.eps, a.want_ssq = eps, int(bool(want_ssq))
+    if resid is not None:
+        ra = np.ascontiguousarray(resid, dtype=np.float32)
+        if ra.shape != (M, N):
+            raise ValueError("resid [M][N] expected")
+        a.resid = ra.ctypes.data
+        keep.append(ra)
+    if fold_w is not None:
+        fw = np.ascontiguousarray(fold_w, dtype=np.float32)
+        if fw.size != N:
+            raise ValueError("fold_w [N] expected")
+        a.fold_w = fw.ctypes.data
+        keep.append(fw)
+    ld = N // 2 if epi == EPI_SWIGLU else N
+    kc = vc = None
+    if qkv is not None:
+        g = qkv
+        a.n_head, a.n_head_kv, a.head_dim = g["n_head"], g["n_head_kv"], g["head_dim"]
+        a.n_ctx, a.n_slots = g["n_ctx"], g["n_slots"]
+        ld = max(g["n_head"] * g["head_dim"], 1)
+        for name in ("pos", "slot"):
+            if g.get(name) is not None:
+                arr = _i32(g[name])
+                if len(arr) != M:
+                    raise ValueError(f"one {name} per row")
+                setattr(a, name, arr.ctypes.data)
+                keep.append(arr)
+        if g.get("rope_cs") is not None:
+            cs = np.ascontiguousarray(g["rope_cs"], dtype=np.float32)
+            if cs.size != max(g["n_ctx"], 0) * g["head_dim"]:
+                raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
+            a.rope_cs = cs.ctypes.data
+            keep.append(cs)
+        stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+        elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
+        if g.get("kcache") is not None and g.get("vcache") is not None:
+            kc = np.array(g["kcache"], dtype=np.uint16, copy=True).reshape(-1)
+            vc = np.array(g["vcache"], dtype=np.uint16, copy=True).reshape(-1)
+            if kc.size != elems or vc.size != elems:
+                raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+            a.kcache, a.vcache = kc.ctypes.data, vc.ctypes.data
+    Mr = max(M, 0)
+    rows = Mr + PROBE_GUARD_ROWS
+    ld = max(ld, 0)
+    if out is None:
+        ob = np.zeros((rows, max(ld, 1)), dtype=np.float32)
+    else:
+        ob = out
+        if not ob.flags.c_contiguous or ob.nbytes < rows * ld * 4:
+            raise ValueError("out too small")
+    a.out = ob.ctypes.data
+    r = KqResult()
+    split = ctypes.c_int32(0)
+    a.split_out = ctypes.addressof(split)
+    ssq = slabs = packed = xq = xd = xb = nxq = nxd = nxb = None
+    if want_ssq:
+        ssq = np.zeros((rows, max(N // 16, 1)), dtype=np.float32)
+        a.ssq_out = ssq.ctypes.data
+    if want_slabs:
+        slabs = np.zeros(max(8 * Mr * N, 1), dtype=np.float32)
+        a.slabs_out, a.slabs_cap = slabs.ctypes.data, 8 * Mr * N
+    if want_packed and wa is not None:
+        t0, nbytes = 0, 0
+        for i in range(a.kq_n):
+            nbytes += (a.kq_tile_end[i] - t0) * (K // 256) * KQ_TILE_BYTES.get(a.kq_type[i], 0)
+            t0 = a.kq_tile_end[i]
+        packed = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        a.packed_out = packed.ctypes.data
+    if act != 2 and K >= 256:
+        xq = np.zeros((rows, K), dtype=np.int8)
+        xd = np.zeros((rows, K // 256), dtype=np.float32)
+        xb = np.zeros((rows, K // 32), dtype=np.float32)
+        a.xq_out, a.xd_out, a.xb_out = xq.ctypes.data, xd.ctypes.data, xb.ctypes.data
+    if path == 1 and N > 0 and N % 256 == 0 and N <= 4096:
+        nxq = np.zeros((rows, N), dtype=np.int8)
+        nxd = np.zeros((rows, N // 256), dtype=np.float32)
+        nxb = np.zeros((rows, N // 32), dtype=np.float32)
+        a.nxq_out, a.nxd_out, a.nxb_out = nxq.ctypes.data, nxd.ctypes.data, nxb.ctypes.data
+    _check(lib().mx_kq_matmul_probe(device, ctypes.byref(a)))
+    del keep
+    if path >= 0:
+        flat = ob.reshape(-1).view(np.float32)[:rows * ld].reshape(rows, ld)
+        r.out, r.guard = flat[:M], flat[M:]
+    r.split, r.packed, r.kcache, r.vcache = split.value, packed, kc, vc
+    if ssq is not None:
+        r.ssq, r.ssq_guard = ssq[:M], ssq[M:]
+    if xq is not None:
+        r.xq, r.xq_guard, r.xd, r.xd_guard, r.xb, r.xb_guard = xq[:M], xq[M:], xd[:M], xd[M:], xb[:M], xb[M:]
+    if nxq is not None:
+        r.nxq, r.nxq_guard, r.nxd, r.nxd_guard, r.nxb, r.nxb_guard = nxq[:M], nxq[M:], nxd[:M], nxd[M:], nxb[:M], nxb[M:]
+    if want_slabs:
+        r.slabs = slabs[:max(r.split, 0) * M * N].reshape(-1, M, N)
+    return r
+
+
+def kq_pack_probe(blocks, type: int, N: int, K: int, pack: int = 0, offset: int = 0, device: int = 0):
+    """launch_pack_kq alone (mx_kq_side_probe mode 0): blocks uint8 [N * K/256 * block bytes] -> (the packed bytes
+    of the N + offset (pack 0) or 2 N (pack 1 / 2: PACK_GATE / PACK_UP) row matrix, 0xFF where nothing was written,
+    guard: 64 tiles that must be all-ones bits)."""
+    ba = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+    if ba.size < N * (K // 256) * KQ_BLOCK_BYTES.get(type, 0):
+        raise ValueError("blocks too short")
+    rows = N + offset if pack == 0 else 2 * N
+    wb = max(rows, 0) // 16 * (K // 256) * KQ_TILE_BYTES.get(type, 0)
+    ob = np.zeros(wb + PROBE_GUARD_ROWS * KQ_TILE_BYTES.get(type, 0) + 16, dtype=np.uint8)
+    a = MxKqSideArgs()
+    a.mode, a.type, a.N, a.K, a.blocks, a.pack, a.offset, a.out = 0, type, N, K, ba.ctypes.data, pack, offset, ob.ctypes.data
+    _check(lib().mx_kq_side_probe(device, ctypes.byref(a)))
+    return ob[:wb], ob[wb:-16]
+
+
+def kq_dequant_probe(blocks, segs, N: int, K: int, device: int = 0):
+    """launch_dequant_kq on blocks packed as at load (mode 1): (packed bf16 tiles uint16 [N * K], guard [64 * K])."""
+    ba = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+    a = MxKqSideArgs()
+    a.kq_n, ty, te = _kq_segments(segs, N)
+    need, t0 = 0, 0
+    for i in range(a.kq_n):
+        a.kq_type[i], a.kq_tile_end[i] = ty[i], te[i]
+        need += max(te[i] - t0, 0) * 16 * (K // 256) * KQ_BLOCK_BYTES.get(ty[i], 0)
+        t0 = te[i]
+    if ba.size < need:
+        raise ValueError("blocks too short")
+    ob = np.zeros((max(N, 0) + PROBE_GUARD_ROWS) * K, dtype=np.uint16)
+    a.mode, a.N, a.K, a.blocks, a.out = 1, N, K, ba.ctypes.data, ob.ctypes.data
+    _check(lib().mx_kq_side_probe(device, ctypes.byref(a)))
+    return ob[:N * K], ob[N * K:]
+
+
+def kq_embed_probe(blocks, type: int, N: int, K: int, ids, want_ssq: bool = True, device: int = 0):
+    """launch_embed_kq (mode 2): rows `ids` of a K-quant token_embd -> (x f32 [M][K], x guard as uint32, ssq
+    [M][K/16] or None, ssq guard or None)."""
+    ba = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+    if ba.size < N * (K // 256) * KQ_BLOCK_BYTES.get(type, 0):
+        raise ValueError("blocks too short")
+    ia = _i32(ids)
+    M = len(ia)
+    ob = np.zeros((M + PROBE_GUARD_ROWS, K), dtype=np.float32)
+    sq = np.zeros((M + PROBE_GUARD_ROWS, K // 16), dtype=np.float32) if want_ssq else None
+    a = MxKqSideArgs()
+    a.mode, a.type, a.N, a.K, a.blocks, a.ids, a.M, a.out = 2, type, N, K, ba.ctypes.data, ia.ctypes.data, M, ob.ctypes.data
+    a.ssq_out = sq.ctypes.data if sq is not None else None
+    _check(lib().mx_kq_side_probe(device, ctypes.byref(a)))
+    return ob[:M], ob[M:].view(np.uint32), (sq[:M] if sq is not None else None), (sq[M:] if sq is not None else None)
+
+
+class Q8kResult:
+    """xq int8 [M][n], xd [M][n/256], xb [M][n/32] and their 64-row guards; x [rows][ld] (the device's x after the
+    launch: folded where slabs were given) and x_guard."""
+    xq = xd = xb = xq_guard = xd_guard = xb_guard = x = x_guard = None
+
+
+def q8k_probe(x, n: Optional[int] = None, w=None, row_map=None, eps: float = 0.0, slabs=None, M: Optional[int] = None,
+              device: int = 0) -> Q8kResult:
+    """launch_quantize_q8k (w None: x f32 [M][ld], ld >= n) / launch_rmsnorm_q8k (w [n]; row_map [M]; slabs
+    [nslab][rows][n] folded into x first) on caller-supplied rows (mx_kq_side_probe modes 3 / 4)."""
+    xa = np.ascontiguousarray(x, dtype=np.float32)
+    if xa.ndim != 2:
+        raise ValueError("x [rows][ld] expected")
+    rows, ld = xa.shape
+    if n is None:
+        n = ld
+    a = MxKqSideArgs()
+    keep = [xa]
+    a.mode, a.K, a.x, a.ld, a.eps = (3 if w is None else 4), n, xa.ctypes.data, ld, eps
+    if row_map is not None:
+        ma = _i32(row_map)
+        a.row_map = ma.ctypes.data
+        keep.append(ma)
+        if M is None:
+            M = len(ma)
+    if M is None:
+        M = rows
+    a.M, a.rows = M, rows
+    if w is not None:
+        wa = np.ascontiguousarray(w, dtype=np.float32)
+        if wa.size != n:
+            raise ValueError("w [n] expected")
+        a.w = wa.ctypes.data
+        keep.append(wa)
+    if slabs is not None:
+        sa = np.ascontiguousarray(slabs, dtype=np.float32)
+        if sa.ndim != 3 or sa.shape[1:] != (rows, n):
+            raise ValueError("slabs [nslab][rows][n] expected")
+        a.nslab = sa.shape[0]
+        if a.nslab:
+            a.slabs = sa.ctypes.data
+        keep.append(sa)
+    Mr, g = max(M, 0), PROBE_GUARD_ROWS
+    xq = np.zeros((Mr + g, max(n, 1)), dtype=np.int8)
+    xd = np.zeros((Mr + g, max(n // 256, 1)), dtype=np.float32)
+    xb = np.zeros((Mr + g, max(n // 32, 1)), dtype=np.float32)
+    xo = np.zeros((rows + g, ld), dtype=np.float32)
+    a.xq_out, a.xd_out, a.xb_out, a.x_out = xq.ctypes.data, xd.ctypes.data, xb.ctypes.data, xo.ctypes.data
+    _check(lib().mx_kq_side_probe(device, ctypes.byref(a)))
+    del keep
+    r = Q8kResult()
+    r.xq, r.xq_guard, r.xd, r.xd_guard, r.xb, r.xb_guard = xq[:M], xq[M:], xd[:M], xd[M:], xb[:M], xb[M:]
+    r.x, r.x_guard = xo[:rows], xo[rows:]
+    return r
 
 
 def pool_probe(x, w, seq_begin, pooling: int, normalize: bool = False, chunk_rows: int = 0, eps: float = 1e-5,
