@@ -608,6 +608,43 @@ typedef struct {
 } mx_kq_side_args;
 int mx_kq_side_probe(int device, const mx_kq_side_args* a);
 
+/* The dequantise-at-load, residual-stream boundary and greedy-pick launchers alone, no engine.  Every output starts
+ * as 0xFF bytes, carries a guard behind it (64 rows for row-shaped outputs, 4096 elements for flat ones) and returns
+ * whole.  Arguments a launcher would mishandle give MX_ERR_ARG and nothing is launched.
+ * mode 0 launch_dequant_bf16: src = src_bytes bytes of raw GGUF blocks of ggml `type`, count elements -> out uint16
+ *   [count + 4096].  An unsupported type, or a count that is no multiple of the type's block, is handed to the
+ *   launcher, and its refusal is reported (MX_ERR_ARG, "launch_dequant_bf16 refused" in mx_last_error()).
+ * mode 1 launch_embed: src bf16 [N][n], ids [M] in [0, N) -> out f32 [M + 64][n]; ssq_out (optional) [M + 64][n/16],
+ *   handed to the launcher only when want_ssq is set (otherwise it returns all 0xFF).
+ * mode 2 launch_ssq: src f32 [M][n] -> ssq_out [M + 64][n/16].
+ * mode 3 launch_f32_in: src f32 [M][n] -> out and ssq_out as mode 1.   mode 4 launch_bf16_to_f32: src bf16 [M][n].
+ *   Modes 1..4: n a multiple of 64 (<= 16384), 1 <= M <= 4096.
+ * mode 5 launch_f32_to_bf16: src f32 [count] -> out uint16 [count + 4096]; mode 6 launch_copy_f32: -> out f32
+ *   [count + 4096]; count a multiple of 4.
+ * mode 7 launch_argmax: src = logits f32 [M][ldl], 1 <= V <= ldl; state in: pos [M], hist_count [M] (>= 0),
+ *   hist_stride, max_hist <= hist_stride; null_mask: bit 0 tok_out, 1 ids_next, 2 pos_next, 3 hist are handed to the
+ *   launcher as NULL (their buffers then return as they were filled) -> tok_out, ids_next_out, pos_next_out (rows < M
+ *   start as pos), hist_count_out (rows < M start as hist_count), each int32 [M + 4096], and hist_out int32
+ *   [M + 64][hist_stride]. */
+typedef struct {
+  int32_t mode, type;
+  uint64_t count, src_bytes;
+  int32_t M, N, n, want_ssq;
+  const void* src;
+  const int32_t* ids;
+  void* out;
+  float* ssq_out;
+  int32_t V, ldl, hist_stride, max_hist, null_mask;
+  const int32_t* pos;
+  const int32_t* hist_count;
+  int32_t* tok_out;
+  int32_t* ids_next_out;
+  int32_t* pos_next_out;
+  int32_t* hist_out;
+  int32_t* hist_count_out;
+} mx_glue_args;
+int mx_glue_probe(int device, const mx_glue_args* a);
+
 /* launch_resid_norm (row_map NULL) / launch_rmsnorm (row_map given, nslab 0) on caller-supplied rows, no
  * engine.  x f32 [rows][n] (n % 64, n <= 16384, rows 1..4096); slabs [nslab][rows][n] (0 <= nslab <= 16) are
  * folded into x in slab order; w f32 [n] (optional): y = bf16(rmsnorm(x, eps) * w) [M][n]; row_map [M] (entries

@@ -22,6 +22,14 @@ __device__ __forceinline__ uint32_t f2bf(float f) {
   uint32_t u = __float_as_uint(f);
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
+// the same with ggml's NaN branch: a NaN keeps its sign and top payload bits and is made quiet (f2bf's carry turns
+// some NaNs into an infinity or a zero).  For the cold paths that may meet one: the bf16 stage hand-off and the
+// dequantisation at load; every other input gives f2bf's bits.
+__device__ __forceinline__ uint32_t f2bf_nan(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
 __device__ __forceinline__ float round_f16(float f) { return (float)(_Float16)f; }
 
 // ---------------------------------------------------------------------------

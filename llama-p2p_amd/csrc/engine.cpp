@@ -4716,6 +4716,143 @@ int mx_kq_side_probe(int device, const mx_kq_side_args* pa) {
   return 0;
 }
 
+namespace {
+constexpr size_t GLUE_GUARD_FLAT = 4096;  // elements of 0xFF after every flat mx_glue_probe output
+size_t glue_block_bytes(int type) {       // bytes of ggml_block_elems(type) values in the file
+  switch (type) {
+    case 0: return 128;
+    case 1: return 64;
+    case 2: return 18;
+    case 8: return 34;
+    case 12: return 144;
+    case 13: return 176;
+    case 14: return 210;
+  }
+  return 0;
+}
+}  // namespace
+
+int mx_glue_probe(int device, const mx_glue_args* pa) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (!pa) return fail(MX_ERR_ARG, "mx_glue_probe: null arguments");
+  const mx_glue_args& p = *pa;
+  const int mode = p.mode, M = p.M, n = p.n;
+  if (mode < 0 || mode > 7) return fail(MX_ERR_ARG, "mx_glue_probe: mode 0..7");
+  if (mode == 0 || mode == 5 || mode == 6) {  // flat: count elements of src -> out [count + 4096]
+    const size_t cnt = p.count, esz = mode == 6 ? 4 : 2;
+    if (!p.src || !p.out || cnt < 1 || cnt > ((size_t)1 << 30))
+      return fail(MX_ERR_ARG, "mx_glue_probe: flat modes: src and out required, 1 <= count <= 2^30");
+    size_t sbytes = cnt * 4;
+    if (mode == 0) {
+      const int be = ggml_block_elems(p.type);
+      sbytes = p.src_bytes;
+      if (sbytes < 1 || sbytes > ((size_t)1 << 32)) return fail(MX_ERR_ARG, "mx_glue_probe: mode 0: 1 <= src_bytes <= 2^32");
+      if (be && cnt % be == 0 && sbytes < cnt / be * glue_block_bytes(p.type))
+        return fail(MX_ERR_ARG, "mx_glue_probe: mode 0: src_bytes is less than count elements of this type");
+    } else if (cnt % 4) {
+      return fail(MX_ERR_ARG, "mx_glue_probe: modes 5 / 6: count a multiple of 4");
+    }
+    if (device >= 0) HIPC(hipSetDevice(device));
+    DevBufs dev;
+    uint8_t *d_src = nullptr, *d_out = nullptr;
+    const size_t ob = (cnt + GLUE_GUARD_FLAT) * esz;
+    if (!dev.alloc(&d_src, sbytes) || !dev.alloc(&d_out, ob)) return fail(MX_ERR_HIP, "mx_glue_probe: device allocation");
+    HIPC(hipMemcpy(d_src, p.src, sbytes, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d_out, 0xFF, ob));
+    HIPC(hipDeviceSynchronize());
+    if (mode == 0) {
+      if (launch_dequant_bf16((uint16_t*)d_out, d_src, p.type, cnt, nullptr)) {
+        hipDeviceSynchronize();
+        return fail(MX_ERR_ARG, "mx_glue_probe: launch_dequant_bf16 refused the type or the count");
+      }
+    } else if (mode == 5) {
+      launch_f32_to_bf16((uint16_t*)d_out, (const float*)d_src, cnt, nullptr);
+    } else {
+      launch_copy_f32((float*)d_out, (const float*)d_src, cnt, nullptr);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(p.out, d_out, ob, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (mode <= 4) {  // rows of the residual stream: x [M + 64][n], ssq [M + 64][n / 16]
+    const bool has_x = mode != 2;
+    if (n < 64 || n % 64 || n > 16384) return fail(MX_ERR_ARG, "mx_glue_probe: modes 1..4: n a multiple of 64, <= 16384");
+    if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_glue_probe: modes 1..4: 1 <= M <= 4096");
+    if (!p.src || (has_x && !p.out) || (mode == 2 && !p.ssq_out))
+      return fail(MX_ERR_ARG, "mx_glue_probe: modes 1..4: src required, out (not mode 2), ssq_out (mode 2)");
+    int srows = M;
+    if (mode == 1) {
+      srows = p.N;
+      if (!p.ids || srows < 1 || srows > (1 << 18)) return fail(MX_ERR_ARG, "mx_glue_probe: mode 1: ids [M], 1 <= N <= 2^18");
+      for (int i = 0; i < M; i++)
+        if (p.ids[i] < 0 || p.ids[i] >= srows) return fail(MX_ERR_ARG, "mx_glue_probe: id out of range");
+    }
+    if (device >= 0) HIPC(hipSetDevice(device));
+    DevBufs dev;
+    uint8_t* d_src = nullptr;
+    float *d_x = nullptr, *d_ssq = nullptr;
+    int* d_ids = nullptr;
+    const size_t sbytes = (size_t)srows * n * ((mode == 1 || mode == 4) ? 2 : 4);
+    const size_t xb = (size_t)(M + PROBE_GUARD_ROWS) * n * 4, qb = (size_t)(M + PROBE_GUARD_ROWS) * (n / 16) * 4;
+    if (!dev.alloc(&d_src, sbytes) || (has_x && !dev.alloc(&d_x, xb)) || (p.ssq_out && !dev.alloc(&d_ssq, qb)) ||
+        (mode == 1 && !dev.alloc(&d_ids, (size_t)M * 4)))
+      return fail(MX_ERR_HIP, "mx_glue_probe: device allocation");
+    HIPC(hipMemcpy(d_src, p.src, sbytes, hipMemcpyHostToDevice));
+    if (d_x) HIPC(hipMemset(d_x, 0xFF, xb));
+    if (d_ssq) HIPC(hipMemset(d_ssq, 0xFF, qb));
+    if (d_ids) HIPC(hipMemcpy(d_ids, p.ids, (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPC(hipDeviceSynchronize());
+    // ssq_out with want_ssq 0: the launcher gets NULL and the buffer returns as it was filled
+    float* ssq_arg = p.want_ssq ? d_ssq : nullptr;
+    if (mode == 1) launch_embed(d_x, (const uint16_t*)d_src, d_ids, M, n, ssq_arg, nullptr);
+    else if (mode == 2) launch_ssq((const float*)d_src, M, n, d_ssq, nullptr);
+    else if (mode == 3) launch_f32_in(d_x, (const float*)d_src, M, n, ssq_arg, nullptr);
+    else launch_bf16_to_f32(d_x, (const uint16_t*)d_src, M, n, ssq_arg, nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    if (has_x) HIPC(hipMemcpy(p.out, d_x, xb, hipMemcpyDeviceToHost));
+    if (p.ssq_out) HIPC(hipMemcpy(p.ssq_out, d_ssq, qb, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // mode 7: launch_argmax.  tok / ids_next / pos_next / hist_count [M + 4096], hist [M + 64][hist_stride]
+  const int V = p.V, ldl = p.ldl, hs = p.hist_stride, mh = p.max_hist;
+  if (M < 1 || M > PREFILL_ROWS || V < 1 || ldl < V || ldl > (1 << 20) || (size_t)M * ldl > ((size_t)1 << 27))
+    return fail(MX_ERR_ARG, "mx_glue_probe: mode 7: 1 <= M <= 4096, 1 <= V <= ldl <= 2^20, M * ldl <= 2^27");
+  if (!p.src || !p.pos || !p.hist_count || !p.tok_out || !p.ids_next_out || !p.pos_next_out || !p.hist_out || !p.hist_count_out)
+    return fail(MX_ERR_ARG, "mx_glue_probe: mode 7: logits, pos, hist_count and the five outputs are required");
+  if (hs < 1 || hs > 4096 || mh < 0 || mh > hs) return fail(MX_ERR_ARG, "mx_glue_probe: mode 7: 0 <= max_hist <= hist_stride <= 4096");
+  for (int i = 0; i < M; i++)
+    if (p.hist_count[i] < 0) return fail(MX_ERR_ARG, "mx_glue_probe: mode 7: negative hist_count");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  float *d_lg = nullptr, *d_wv = nullptr;
+  int *d_wi = nullptr, *d_tok = nullptr, *d_ids = nullptr, *d_pos = nullptr, *d_hist = nullptr, *d_hc = nullptr;
+  const size_t lb = (size_t)M * ldl * 4, fb = ((size_t)M + GLUE_GUARD_FLAT) * 4, wsb = (size_t)M * 64 * 4;
+  const size_t hb = (size_t)(M + PROBE_GUARD_ROWS) * hs * 4;
+  if (!dev.alloc(&d_lg, lb) || !dev.alloc(&d_wv, wsb) || !dev.alloc(&d_wi, wsb) || !dev.alloc(&d_tok, fb) ||
+      !dev.alloc(&d_ids, fb) || !dev.alloc(&d_pos, fb) || !dev.alloc(&d_hc, fb) || !dev.alloc(&d_hist, hb))
+    return fail(MX_ERR_HIP, "mx_glue_probe: device allocation");
+  HIPC(hipMemcpy(d_lg, p.src, lb, hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_wv, 0xFF, wsb));
+  HIPC(hipMemset(d_wi, 0xFF, wsb));
+  for (int* b : {d_tok, d_ids, d_pos, d_hc}) HIPC(hipMemset(b, 0xFF, fb));
+  HIPC(hipMemset(d_hist, 0xFF, hb));
+  HIPC(hipMemcpy(d_pos, p.pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_hc, p.hist_count, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  launch_argmax(d_lg, ldl, M, V, d_wv, d_wi, (p.null_mask & 1) ? nullptr : d_tok, (p.null_mask & 2) ? nullptr : d_ids,
+                (p.null_mask & 4) ? nullptr : d_pos, (p.null_mask & 8) ? nullptr : d_hist, hs, d_hc, mh, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(p.tok_out, d_tok, fb, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.ids_next_out, d_ids, fb, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.pos_next_out, d_pos, fb, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.hist_count_out, d_hc, fb, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(p.hist_out, d_hist, hb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int mx_submit_spec(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int num_pred_tokens,
                    int max_ngram_size, uint64_t* req) {
   if (!e || !ids || n < 1 || !req) return fail(MX_ERR_ARG, "bad arguments");

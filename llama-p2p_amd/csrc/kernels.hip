@@ -2169,8 +2169,8 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(uint16_t* dst, const f
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
     u32x2 o;
-    o[0] = f2bf(v[0]) | (f2bf(v[1]) << 16);
-    o[1] = f2bf(v[2]) | (f2bf(v[3]) << 16);
+    o[0] = f2bf_nan(v[0]) | (f2bf_nan(v[1]) << 16);
+    o[1] = f2bf_nan(v[2]) | (f2bf_nan(v[3]) << 16);
     reinterpret_cast<u32x2*>(dst)[i] = o;
   }
 }
@@ -2921,7 +2921,8 @@ void launch_synth_q8_rowmajor(uint8_t* dst, int N, int K, uint64_t seed, uint64_
 
 // ---------------------------------------------------------------------------
 // Any other GGUF block type -> bf16 at load (dequantize_row_* of ggml-quants.c in f32, one rounding
-// per operation as the C code -- contraction is off here -- then round-to-nearest-even to bf16).
+// per operation as the C code -- contraction is off here -- then round-to-nearest-even to bf16, a NaN
+// staying a NaN: f2bf_nan).
 // Used when a file's layer matrices are not all BF16 or all Q8_0 (Q4_K_M, Q5_K_M, Q4_0, F16 ...):
 // the model then runs on the bf16 path.  gguf.py dequantize() is the same restatement.
 // ---------------------------------------------------------------------------
@@ -2931,21 +2932,21 @@ __global__ void dequant_bf16_kernel(uint16_t* dst, const uint8_t* src, int type,
     if (type == 0 || type == 1) {  // F32 / F16: "blocks" of 32 values
       uint16_t* y = dst + b * 32;
       for (int j = 0; j < 32; ++j)
-        y[j] = (uint16_t)f2bf(type == 0 ? reinterpret_cast<const float*>(src)[b * 32 + j]
+        y[j] = (uint16_t)f2bf_nan(type == 0 ? reinterpret_cast<const float*>(src)[b * 32 + j]
                                         : (float)reinterpret_cast<const _Float16*>(src)[b * 32 + j]);
     } else if (type == 2) {  // Q4_0
       const uint8_t* x = src + b * 18;
       const float d = f16b(x);
       uint16_t* y = dst + b * 32;
       for (int j = 0; j < 16; ++j) {
-        y[j] = (uint16_t)f2bf((float)((x[2 + j] & 15) - 8) * d);
-        y[j + 16] = (uint16_t)f2bf((float)((x[2 + j] >> 4) - 8) * d);
+        y[j] = (uint16_t)f2bf_nan((float)((x[2 + j] & 15) - 8) * d);
+        y[j + 16] = (uint16_t)f2bf_nan((float)((x[2 + j] >> 4) - 8) * d);
       }
     } else if (type == 8) {  // Q8_0
       const uint8_t* x = src + b * 34;
       const float d = f16b(x);
       uint16_t* y = dst + b * 32;
-      for (int j = 0; j < 32; ++j) y[j] = (uint16_t)f2bf((float)(int8_t)x[2 + j] * d);
+      for (int j = 0; j < 32; ++j) y[j] = (uint16_t)f2bf_nan((float)(int8_t)x[2 + j] * d);
     } else if (type == 12 || type == 13) {  // Q4_K, Q5_K
       const bool q5 = type == 13;
       const uint8_t* x = src + b * (q5 ? 176 : 144);
@@ -2966,8 +2967,8 @@ __global__ void dequant_bf16_kernel(uint16_t* dst, const uint8_t* src, int type,
             lo += (qh[l] & (1 << (2 * g))) ? 16 : 0;
             hi += (qh[l] & (2 << (2 * g))) ? 16 : 0;
           }
-          y[64 * g + l] = (uint16_t)f2bf(d1 * (float)lo - m1);
-          y[64 * g + 32 + l] = (uint16_t)f2bf(d2 * (float)hi - m2);
+          y[64 * g + l] = (uint16_t)f2bf_nan(d1 * (float)lo - m1);
+          y[64 * g + 32 + l] = (uint16_t)f2bf_nan(d2 * (float)hi - m2);
         }
       }
     } else if (type == 14) {  // Q6_K
@@ -2983,7 +2984,7 @@ __global__ void dequant_bf16_kernel(uint16_t* dst, const uint8_t* src, int type,
           const int qv[4] = {((L0 & 15) | (((H >> 0) & 3) << 4)) - 32, ((L1 & 15) | (((H >> 2) & 3) << 4)) - 32,
                              ((L0 >> 4) | (((H >> 4) & 3) << 4)) - 32, ((L1 >> 4) | (((H >> 6) & 3) << 4)) - 32};
           for (int i = 0; i < 4; ++i)
-            y[128 * h + 32 * i + l] = (uint16_t)f2bf((d * (float)sc[8 * h + l / 16 + 2 * i]) * (float)qv[i]);
+            y[128 * h + 32 * i + l] = (uint16_t)f2bf_nan((d * (float)sc[8 * h + l / 16 + 2 * i]) * (float)qv[i]);
         }
     }
   }

@@ -38,6 +38,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
     "mx_engine_set_host_cache", "mx_host_cache_stats", "mx_kv_pack_probe",
     "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
+    "mx_glue_probe",
 ]
 # the Q8_0 / Q4_0 kernel probes: names with a digit, listed apart (tests/test_gguf_abi.py checks both lists)
 EXPORTS_Q8 = ["mx_q8_matmul_probe", "mx_q8_matmul_plan", "mx_q8_side_probe"]
@@ -196,6 +197,16 @@ class MxKqSideArgs(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("out", "ssq_out", "xq_out", "xd_out", "xb_out", "x_out")]
 
 
+class MxGlueArgs(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int32), ("type", ctypes.c_int32), ("count", ctypes.c_uint64),
+                ("src_bytes", ctypes.c_uint64)] + \
+               [(n, ctypes.c_int32) for n in ("M", "N", "n", "want_ssq")] + \
+               [(n, ctypes.c_void_p) for n in ("src", "ids", "out", "ssq_out")] + \
+               [(n, ctypes.c_int32) for n in ("V", "ldl", "hist_stride", "max_hist", "null_mask")] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "hist_count", "tok_out", "ids_next_out", "pos_next_out",
+                                               "hist_out", "hist_count_out")]
+
+
 def sampling(temperature: float = 0.0, top_k: int = 40, top_p: float = 0.95, min_p: float = 0.05,
              repeat_penalty: float = 1.0, repeat_last_n: int = 64, seed: Optional[int] = None,
              ignore_eos: bool = False, frequency_penalty: float = 0.0, presence_penalty: float = 0.0) -> MxSampling:
@@ -303,6 +314,7 @@ def lib() -> ctypes.CDLL:
         L.mx_kq_matmul_probe.argtypes = [i32, P(MxKqMatmulArgs)]
         L.mx_kq_matmul_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, P(MxKqPlan)]
         L.mx_kq_side_probe.argtypes = [i32, P(MxKqSideArgs)]
+        L.mx_glue_probe.argtypes = [i32, P(MxGlueArgs)]
         L.mx_submit_spec.argtypes = [vp, vp, i32, P(MxSampling), i32, i32, i32, P(u64)]
         L.mx_spec_stats.argtypes = [vp, u64, P(MxSpecCounts)]
         L.mx_draft_probe.argtypes = [i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -1177,6 +1189,86 @@ def kq_embed_probe(blocks, type: int, N: int, K: int, ids, want_ssq: bool = True
     a.ssq_out = sq.ctypes.data if sq is not None else None
     _check(lib().mx_kq_side_probe(device, ctypes.byref(a)))
     return ob[:M], ob[M:].view(np.uint32), (sq[:M] if sq is not None else None), (sq[M:] if sq is not None else None)
+
+
+GLUE_GUARD_FLAT = 4096  # elements of 0xFF behind every flat mx_glue_probe output
+
+
+def glue_flat_probe(mode: int, src, count: int, type: int = 0, device: int = 0):
+    """The flat modes of mx_glue_probe: 0 launch_dequant_bf16 (src: the raw blocks of ggml `type`, any dtype; count
+    elements), 5 launch_f32_to_bf16, 6 launch_copy_f32 (src f32 [count]) -> (out [count], guard [4096]), uint16 for
+    modes 0 / 5 and uint32 (the f32 bits) for mode 6."""
+    if mode not in (0, 5, 6):
+        raise ValueError("flat modes are 0, 5 and 6")
+    sa = np.ascontiguousarray(src).reshape(-1).view(np.uint8) if mode == 0 else \
+        np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+    if mode != 0 and sa.size < count:
+        raise ValueError("src too short")
+    ob = np.zeros(max(count, 0) + GLUE_GUARD_FLAT, dtype=np.uint32 if mode == 6 else np.uint16)
+    a = MxGlueArgs()
+    a.mode, a.type, a.count, a.src_bytes, a.src, a.out = mode, type, max(count, 0), sa.nbytes, sa.ctypes.data, ob.ctypes.data
+    _check(lib().mx_glue_probe(device, ctypes.byref(a)))
+    return ob[:count], ob[count:]
+
+
+def glue_rows_probe(mode: int, src, ids=None, want_ssq: bool = True, M: Optional[int] = None, n: Optional[int] = None,
+                    device: int = 0):
+    """The row modes of mx_glue_probe: 1 launch_embed (src bf16 bits [N][n], ids [M]), 2 launch_ssq (src f32 [M][n]),
+    3 launch_f32_in (src f32 [M][n]), 4 launch_bf16_to_f32 (src bf16 bits [M][n]) -> (x [M][n] as uint32 or None
+    (mode 2), x guard [64][n], ssq [M][n/16] as uint32, ssq guard [64][n/16]).  The ssq buffer always travels: with
+    want_ssq False the launcher gets NULL and it must return all-ones bits.  M / n override the shape of src (refusal
+    tests)."""
+    if mode not in (1, 2, 3, 4):
+        raise ValueError("row modes are 1..4")
+    sa = np.ascontiguousarray(src, dtype=np.uint16 if mode in (1, 4) else np.float32)
+    rows, ncol = sa.shape
+    n = ncol if n is None else n
+    a = MxGlueArgs()
+    ia = None
+    if mode == 1:
+        ia = _i32(ids)
+        a.N, a.ids = rows, ia.ctypes.data
+        M = len(ia) if M is None else M
+    M = rows if M is None else M
+    xo = np.zeros((max(M, 0) + PROBE_GUARD_ROWS, max(n, 0)), dtype=np.uint32) if mode != 2 else None
+    sq = np.zeros((max(M, 0) + PROBE_GUARD_ROWS, max(n, 0) // 16), dtype=np.uint32)
+    a.mode, a.M, a.n, a.want_ssq, a.src = mode, M, n, int(want_ssq), sa.ctypes.data
+    a.out = xo.ctypes.data if xo is not None else None
+    a.ssq_out = sq.ctypes.data
+    _check(lib().mx_glue_probe(device, ctypes.byref(a)))
+    return (xo[:M] if xo is not None else None), (xo[M:] if xo is not None else None), sq[:M], sq[M:]
+
+
+class ArgmaxResult:
+    """tok, ids_next, pos_next, hist_count int32 [M] with their 4096-element guards (*_guard), hist [M][hist_stride]
+    and hist_guard [64][hist_stride]; a buffer whose pointer was withheld (null_mask) returns as it was filled."""
+
+
+def argmax_probe(logits, V: int, pos, hist_count, hist_stride: int, max_hist: int, null_mask: int = 0,
+                 M: Optional[int] = None, ldl: Optional[int] = None, device: int = 0) -> ArgmaxResult:
+    """launch_argmax (argmax_stage1 + argmax_stage2) on caller-supplied logits f32 [M][ldl] (mx_glue_probe mode 7).
+    null_mask: bit 0 tok_out, 1 ids_next, 2 pos_next, 3 hist passed as NULL."""
+    la = np.ascontiguousarray(logits, dtype=np.float32)
+    rows, ld = la.shape
+    M = rows if M is None else M
+    ldl = ld if ldl is None else ldl
+    pa, ha = _i32(pos), _i32(hist_count)
+    if len(pa) < M or len(ha) < M:
+        raise ValueError("pos [M] and hist_count [M] expected")
+    flat = [np.zeros(max(M, 0) + GLUE_GUARD_FLAT, dtype=np.int32) for _ in range(4)]
+    hist = np.zeros((max(M, 0) + PROBE_GUARD_ROWS, max(hist_stride, 1)), dtype=np.int32)
+    a = MxGlueArgs()
+    a.mode, a.M, a.V, a.ldl, a.hist_stride, a.max_hist, a.null_mask = 7, M, V, ldl, hist_stride, max_hist, null_mask
+    a.src, a.pos, a.hist_count = la.ctypes.data, pa.ctypes.data, ha.ctypes.data
+    a.tok_out, a.ids_next_out, a.pos_next_out, a.hist_count_out = (f.ctypes.data for f in flat)
+    a.hist_out = hist.ctypes.data
+    _check(lib().mx_glue_probe(device, ctypes.byref(a)))
+    r = ArgmaxResult()
+    for name, f in zip(("tok", "ids_next", "pos_next", "hist_count"), flat):
+        setattr(r, name, f[:M])
+        setattr(r, name + "_guard", f[M:])
+    r.hist, r.hist_guard = hist[:M], hist[M:]
+    return r
 
 
 class Q8kResult:
