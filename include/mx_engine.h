@@ -685,7 +685,11 @@ int mx_stage_rows(mx_engine* e, int n, const int32_t* slots, const int32_t* pos,
 /* Pipelined prefill of n rows (any count: GEMM chunks as mx_forward_rows; x_in / x_out device
  * [n][n_embd] in the hand-off dtype).  On the last stage, rows rowmap[0..n_out) (increasing) each pick
  * a token -- the device sampling chain with samp[i], or greedy argmax when samp is NULL -- copied to
- * tok_out (host int32[n_out]); the first token of each prompt in the pipeline server. */
+ * tok_out (host int32[n_out]); the first token of each prompt in the pipeline server.
+ * Rows need no padding: a call with more than 64 picks whose rows fall in one chunk is cut into
+ * forwards of at most 64 picks each, after the 64th pick's 16-row block (where padded prompts end) but
+ * never past the next picked row, so every rowmap entry is produced by the forward that holds its row.  A prompt the cut
+ * divides keeps its result: its later rows attend to the K/V its earlier rows stored. */
 int mx_stage_rows_pick(mx_engine* e, int n, const int32_t* slots, const int32_t* pos, const int32_t* ids,
                        const void* x_in, void* x_out, int n_out, const int32_t* rowmap, const mx_row_sampler* samp,
                        int32_t* tok_out, void* stream);

@@ -3789,8 +3789,11 @@ int mx_stage_rows_pick(mx_engine* e, int n, const int32_t* slots, const int32_t*
   for (int i = 0; i < n;) {
     int end = std::min(n, i + chunk), k1 = k0;
     while (k1 < n_out && rowmap[k1] < end && k1 - k0 < MAX_ROWS) k1++;
-    // cut after the 64th prompt's last row, rounded up to its 16-row block (the prompts' padding)
-    if (k1 - k0 == MAX_ROWS && k1 < n_out && rowmap[k1] < end) end = std::min(n, (rowmap[k1 - 1] + 16) / 16 * 16);
+    // cut after the 64th prompt's last row, rounded up to its 16-row block (the prompts' padding) but
+    // never past the next picked row: unpadded prompts may end inside that block, and a row the cut
+    // skipped would reach the next chunk's row map as a negative index
+    if (k1 - k0 == MAX_ROWS && k1 < n_out && rowmap[k1] < end)
+      end = std::min({n, (rowmap[k1 - 1] + 16) / 16 * 16, rowmap[k1]});
     const int m = end - i, no = k1 - k0;
     for (int r = i; r < end; r++) {
       if (slots[r] < 0 || slots[r] >= e->n_seq_max) return fail(MX_ERR_ARG, "slot out of range");

@@ -18,6 +18,8 @@ answer whatever else the engine is serving.  Bitwise, on the full 32-layer Llama
 import numpy as np
 import pytest
 
+from walk_ref import blocked_layout
+
 pytestmark = pytest.mark.gpu
 
 N_CTX = 512
@@ -80,24 +82,6 @@ def _decode_rows_bitwise(e):
     print({"rows_checked": checked})
 
 
-def _rows(prompts, slot0, n_ctx=N_CTX):
-    """The scheduler's prefill layout (engine.cpp prefill_batch, pipeserve._prefill): each prompt from a
-    16-row block boundary, padded to whole blocks; returns rows and each prompt's row range."""
-    slots, pos, ids, spans = [], [], [], []
-    for k, p in enumerate(prompts):
-        n = len(p)
-        r0 = len(slots)
-        slots += [slot0 + k] * n
-        pos += list(range(n))
-        ids += p
-        spans.append((r0, r0 + n))
-        pad = (16 - n % 16) % 16
-        slots += [slot0 + k] * pad
-        pos += list(range(n, n + pad)) if n + pad <= n_ctx else [n - 1] * pad
-        ids += [p[-1]] * pad
-    return slots, pos, ids, spans
-
-
 def test_prefill_hidden_states_bitwise_alone_and_in_a_chunk(eng8b):
     import torch
 
@@ -107,13 +91,13 @@ def test_prefill_hidden_states_bitwise_alone_and_in_a_chunk(eng8b):
     targets.append(_prompts(e.n_vocab, 1, 13, N_CTX - 3, N_CTX - 3)[0])  # padded with copies near n_ctx
     dev = torch.device("cuda", 0)
     for ti, t in enumerate(targets):
-        s, p, i, sp = _rows([t], 0)
+        s, p, i, sp = blocked_layout([t], 0, N_CTX)
         xa = torch.empty((len(s), e.n_embd), dtype=torch.float32, device=dev)
         e.stage_rows_pick(s, p, i, x_out=xa.data_ptr())
         torch.cuda.synchronize()
         alone = xa[sp[0][0]:sp[0][1]].cpu().numpy()
         batch = others[:ti * 5] + [t] + others[ti * 5:]
-        s, p, i, sp = _rows(batch, 1)
+        s, p, i, sp = blocked_layout(batch, 1, N_CTX)
         xb = torch.empty((len(s), e.n_embd), dtype=torch.float32, device=dev)
         e.stage_rows_pick(s, p, i, x_out=xb.data_ptr())
         torch.cuda.synchronize()

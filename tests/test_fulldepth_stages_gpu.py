@@ -20,12 +20,9 @@ import numpy as np
 import pytest
 import torch
 
+from walk_ref import bf16_tol_rows as _bf16_tol  # the bf16 bar (conftest.logit_tol) row by row
+
 pytestmark = pytest.mark.gpu
-
-
-def _bf16_tol(ref):
-    """The bf16 bar (conftest.logit_tol) row by row: 1e-2*|ref| + 2e-2*max|ref of that row|."""
-    return 1e-2 * np.abs(ref) + 2e-2 * np.abs(ref).max(axis=-1, keepdims=True)
 
 
 def _prompts(vocab, n, lo, hi, seed):
