@@ -56,7 +56,9 @@ extern "C" {
 #define MX_DEBUG_STOPPED 1   /* a 17..64-row forward ended at the mx_debug stop (diagnosis only) */
 
 #define MX_FINISH_LENGTH 0 /* max_tokens or n_ctx reached  ("length") */
-#define MX_FINISH_STOP 1   /* end-of-generation token       ("stop")   */
+#define MX_FINISH_STOP 1   /* end-of-generation token: tokenizer.ggml.eos_token_id or, when the file has
+                              one, tokenizer.ggml.eot_token_id -- returned as the last token; also a
+                              cancelled request              ("stop")   */
 #define MX_FINISH_ERROR 2
 
 typedef struct mx_engine mx_engine;
@@ -82,6 +84,7 @@ typedef struct {
   int32_t layer_begin, layer_end, has_embed, has_head;
   uint64_t weight_bytes; /* device bytes of the weights this stage streams per decode step */
   int32_t weight_type;       /* ggml type of the layer matrices: 30 BF16, 8 Q8_0, 2 Q4_0, 12 Q4_K (Q4_K_M), 13 Q5_K (Q5_K_M) */
+  int32_t eot_id;            /* tokenizer.ggml.eot_token_id: ends a request like eos_id; -1 when the file has none */
 } mx_model_info;
 
 typedef struct {

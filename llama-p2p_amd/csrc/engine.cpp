@@ -269,6 +269,8 @@ struct mx_engine {
   std::vector<float> rope_ff;
   float rope_freq_scale = 1.0f;
   int bos = 1, eos = 2;
+  int eot = -1;  // tokenizer.ggml.eot_token_id (end of turn): ends a request as eos does; -1 when the file has none
+  bool is_eog(int32_t t) const { return t == eos || (eot >= 0 && t == eot); }  // llama.cpp llama_token_is_eog
   int n_ctx = 512, n_seq_max = 64, lb = 0, le = 0, device = 0;
   bool has_embed = true, has_head = true, use_graphs = true;
   // <= 4 rows: RMS_NORM applied while loading the GEMV's B operand, from per-tile sums of squares
@@ -933,6 +935,7 @@ int mx_engine::load_gguf(const std::string& path) {
   n_ctx_train = (int)f.get_num("llama.context_length", 2048);
   bos = (int)f.get_num("tokenizer.ggml.bos_token_id", 1);
   eos = (int)f.get_num("tokenizer.ggml.eos_token_id", 2);
+  eot = (int)f.get_num("tokenizer.ggml.eot_token_id", -1);
   const GGUFTensor* te = f.tensor("token_embd.weight");
   if (!te || te->ne.size() != 2) return fail(MX_ERR_MODEL, "missing token_embd.weight");
   n_vocab = (int)te->ne[1];
@@ -2667,7 +2670,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
         r->pos++;
         r->out.push_back(t);
         r->next_tok = t;
-        if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
+        if ((is_eog(t) && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
         else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
       }
       off += a + 1;
@@ -2848,7 +2851,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
         if (host_pick) ent[0] = (raw - lpms[2 * i]) - lpms[2 * i + 1];
         r->lp_append(ent, lpk);
       }
-      if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
+      if ((is_eog(t) && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
       else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
     }
     note_kv(r);
@@ -3036,7 +3039,7 @@ void mx_engine::scheduler_loop() {
           continue;
         }
         const int32_t t = r->out.back();
-        if ((t == eos && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
+        if ((is_eog(t) && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
         else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
         else active.push_back(r);
       }
@@ -3205,7 +3208,7 @@ int mx_engine_info(const mx_engine* e, mx_model_info* o) {
   if (!e || !o) return fail(MX_ERR_ARG, "null argument");
   o->n_embd = e->n_embd; o->n_layer = e->n_layer; o->n_head = e->n_head; o->n_head_kv = e->n_head_kv;
   o->head_dim = e->head_dim; o->n_ff = e->n_ff; o->n_vocab = e->n_vocab; o->n_ctx_train = e->n_ctx_train;
-  o->eps = e->eps; o->rope_base = e->rope_base; o->bos_id = e->bos; o->eos_id = e->eos;
+  o->eps = e->eps; o->rope_base = e->rope_base; o->bos_id = e->bos; o->eos_id = e->eos; o->eot_id = e->eot;
   o->n_ctx = e->n_ctx; o->n_seq_max = e->n_seq_max; o->layer_begin = e->lb; o->layer_end = e->le;
   o->has_embed = e->has_embed; o->has_head = e->has_head; o->weight_bytes = e->weight_bytes;
   o->weight_type = e->wq4 ? 2 : e->wq8 ? 8 : e->wkq ? e->kq_main_type : 30;

@@ -66,7 +66,7 @@ class MxModelInfo(ctypes.Structure):
                [("eps", ctypes.c_float), ("rope_base", ctypes.c_float)] + \
                [(n, ctypes.c_int32) for n in ("bos_id", "eos_id", "n_ctx", "n_seq_max", "layer_begin",
                                               "layer_end", "has_embed", "has_head")] + \
-               [("weight_bytes", ctypes.c_uint64), ("weight_type", ctypes.c_int32)]
+               [("weight_bytes", ctypes.c_uint64), ("weight_type", ctypes.c_int32), ("eot_id", ctypes.c_int32)]
 
 
 class MxSampling(ctypes.Structure):

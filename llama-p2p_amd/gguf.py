@@ -455,7 +455,7 @@ def _mixed_type(wtype: str, name: str) -> int:
 
 def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = None, wtype: str = "bf16",
                          dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None,
-                         pooling_type: int = None):
+                         pooling_type: int = None, eos_token_id: int = 2, eot_token_id: int = None):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
     "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
@@ -466,7 +466,9 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     (type, factor) written as llama.rope.scaling.type / .factor.  embd_type: token_embd.weight as this
     type instead (GGML_Q8_0 or GGML_F16 of the synthetic bf16 table; llama-quantize
     --token-embedding-type).  pooling_type: written as llama.pooling_type (an embedding model's default pooling,
-    llama.h enum llama_pooling_type)."""
+    llama.h enum llama_pooling_type).  eos_token_id: tokenizer.ggml.eos_token_id; eot_token_id: written as
+    tokenizer.ggml.eot_token_id when given (the end-of-turn token, which ends a request as EOS does) -- the
+    defaults leave the file as it always was."""
     from . import synth
 
     if wtype not in ("bf16", "q8_0", "q4_0_synth") and wtype not in MIXED:
@@ -499,7 +501,9 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     w.add_array("tokenizer.ggml.scores", T_FLOAT32, scores)
     w.add_array("tokenizer.ggml.token_type", T_INT32, types)
     w.add_uint32("tokenizer.ggml.bos_token_id", 1)
-    w.add_uint32("tokenizer.ggml.eos_token_id", 2)
+    w.add_uint32("tokenizer.ggml.eos_token_id", eos_token_id)
+    if eot_token_id is not None:
+        w.add_uint32("tokenizer.ggml.eot_token_id", eot_token_id)
     w.add_uint32("tokenizer.ggml.unknown_token_id", 0)
     w.add_bool("tokenizer.ggml.add_bos_token", True)
     arrays = []

@@ -78,8 +78,9 @@ class Scheduler:
     """Rank 0: pending queue, lane table, placement, round plans, token bookkeeping."""
 
     def __init__(self, lanes: int, rows: int, n_ctx: int, eos: int, kmax: int = 8, policy: str = "score_aware",
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, eot: int = -1):
         self.S, self.M, self.n_ctx, self.eos, self.kmax = lanes, rows, n_ctx, eos, kmax
+        self.eot = eot  # the end-of-turn token (mx_model_info.eot_id): ends a request as eos does; -1: none
         self.table: List[List[Optional[PRequest]]] = [[None] * rows for _ in range(lanes)]
         self.pending: collections.deque = collections.deque()
         self.reqs: Dict[int, PRequest] = {}
@@ -265,7 +266,8 @@ class Scheduler:
         if r.done:
             return True
         t = r.out[-1] if r.out else None
-        if (t == self.eos and not r.samp.get("ignore_eos", False)) or r.cancel:
+        eog = t is not None and (t == self.eos or (self.eot >= 0 and t == self.eot))
+        if (eog and not r.samp.get("ignore_eos", False)) or r.cancel:
             r.done, r.finish = True, FINISH_STOP
         elif len(r.out) >= r.max_tokens or r.pos >= self.n_ctx:
             r.done, r.finish = True, FINISH_LENGTH
@@ -896,7 +898,7 @@ def pipeline_llama(model_path: str, comm, world: int, lanes: Optional[int] = Non
     eng, parts = _stage_setup(model_path, 0, world, lanes, rows, n_ctx, kmax, device, handoff_bf16, parts)
     runner = StageRunner(EngineExecutor(eng, device), comm, 0, world, lanes, rows, kmax, device,
                          stage_time_every, timing_lock=timing_lock)
-    sched = Scheduler(lanes, rows, n_ctx, eng.info.eos_id, kmax, policy=policy, seed=seed)
+    sched = Scheduler(lanes, rows, n_ctx, eng.info.eos_id, kmax, policy=policy, seed=seed, eot=eng.info.eot_id)
     costs = _layer_costs(model_path)
     head_layers = costs[1] / costs[0] if costs else 1.0
     planner = StagePlanner(parts, head_layers=head_layers, min_gain=min_gain, enabled=repartition, **(planner_kw or {}))
