@@ -201,7 +201,10 @@ int mx_logprob_probe(int device, const float* logits_host, int n, int V, int ldl
  * carried across steps and rounds): tokens with -log2 p <= mu stay (the argmax when none does), the draw walks them
  * by ascending id, mu -= eta (-log2 p'_tok - tau).  mirostat_mode 1 (a sort of the whole vocabulary), any other
  * mode, NaN settings and a bad bias table are MX_ERR_ARG.  Log-probabilities stay those of the raw lm_head row.
- * A request with any of these settings never speculates.  mx_sampling / mx_row_sampler are unchanged. */
+ * A request with any of these settings never speculates.  mx_sampling / mx_row_sampler are unchanged.
+ * base.top_k: any value samples on the device.  <= 0 or >= the vocabulary: every token is a candidate; more than
+ * 64 candidates take the wide kernel, which has no tail-free / typical cut: tfs_z < 1 or
+ * typical_p < 1 over more than 64 candidates is sampled on the host (mx_sample_plan tells which). */
 typedef struct {
   mx_sampling base;
   float typical_p, tfs_z;   /* 1.0 = off */
@@ -219,11 +222,37 @@ int mx_submit_ext(mx_engine* e, const int32_t* ids, int n, const mx_sampling_ext
 /* As mx_submit_batch with one mx_sampling_ext per request: all validated first, then queued under one lock. */
 int mx_submit_ext_batch(mx_engine* e, int n_req, const int32_t* const* ids, const int32_t* lens,
                         const mx_sampling_ext* s, const int32_t* max_tokens, uint64_t* reqs);
+/* Which sampler picks the rows of a request with these settings over a vocabulary of V -- what the scheduler, the
+ * prefill and mx_sample_probe dispatch on; no GPU touched.  Validates as mx_submit_ext (MX_ERR_ARG otherwise; also
+ * for V < 1).  k_eff = V when top_k <= 0 or top_k >= V, else top_k; penalties = a repeat / frequency / presence
+ * penalty off its default.  The first rule that holds:
+ *   temperature <= 0, no penalties, no logit_bias       MX_PICK_ARGMAX    the argmax kernels
+ *   penalties with repeat_last_n < 0 or > 64            MX_PICK_HOST      the host sampler; the whole round with it
+ *   temperature <= 0 otherwise                          MX_PICK_CHAIN     (greedy never reads top_k)
+ *   mirostat_mode == 2                                  MX_PICK_MIROSTAT  the Mirostat kernels
+ *   k_eff <= 64                                         MX_PICK_CHAIN     top-k kernels + the per-row pick kernel
+ *   k_eff > 64 with tfs_z < 1 or typical_p < 1          MX_PICK_HOST
+ *   k_eff > 64 with V > 262144                          MX_PICK_HOST
+ *   anything else                                       MX_PICK_WIDE      the wide kernel over k_eff candidates */
+#define MX_PICK_ARGMAX 0
+#define MX_PICK_CHAIN 1
+#define MX_PICK_MIROSTAT 2
+#define MX_PICK_WIDE 3
+#define MX_PICK_HOST 4
+int mx_sample_plan(const mx_sampling_ext* s, int V, int32_t* path);
+/* Sampler counters of the request path (mx_stats is fixed): device_steps / host_steps: decode steps whose picks
+ * ran on the device (greedy or any chain) / in the host sampler; wide_rows: row-steps the wide kernel picked, the
+ * first token from the prefill included; rounds: the scheduler rounds those steps ran in (a device round runs
+ * several steps per host round trip, a host round one). */
+typedef struct {
+  uint64_t device_steps, host_steps, wide_rows, rounds;
+} mx_sampler_counts;
+int mx_sampler_stats(mx_engine* e, mx_sampler_counts* out);
 /* The chain on caller-supplied rows, no engine: logits_host [n][ldl] f32 with V <= ldl valid columns, n <= 64,
  * V <= 262144; row i samples draw n_drawn[i] of stream seeds[i] with penalty window win[i][0..n_win[i]) (<= 64) and
  * Mirostat state mu_in[i].  device >= 0: the production launch sequence (bias -> penalties -> top-k -> sample
- * kernel, Mirostat kernels; top_k 1..64 and repeat_last_n 0..64 as for any device-sampled row); device == -1: the
- * host sampler, no GPU touched.  tok_out / mu_out [n] start as 0xFF bytes; logits_out (optional, [n][ldl]): the
+ * kernel, Mirostat kernels, wide kernel), each row on the path mx_sample_plan gives it, mixed freely; a row on
+ * MX_PICK_HOST is refused; device == -1: the host sampler, no GPU touched.  tok_out / mu_out [n] start as 0xFF bytes; logits_out (optional, [n][ldl]): the
  * rows as the chain left them (bias and penalties applied), columns >= V bit-identical.  Anything invalid:
  * MX_ERR_ARG, nothing launched. */
 int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl, const mx_sampling_ext* samp,

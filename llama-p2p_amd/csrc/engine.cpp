@@ -233,6 +233,9 @@ struct Request {
   }
 };
 
+// the sampler path of a request's rows (mx_sample_plan's rules over its settings) and the candidates it asks for
+int req_path(const Request* r, int V, int* k_eff);
+
 struct GraphKey {
   int M;
   const void* xin;
@@ -350,7 +353,8 @@ struct mx_engine {
 
   // graphs for the scheduler's decode steps, by (M, top-k of the device sampling chain or 0 = argmax)
   // ... and the top-k of the round's log-probabilities (-1: none; such rounds enqueue what they always did)
-  // ... and whether the round runs the extended chain (0: none; 1: bias / tail-free / typical; 2: Mirostat too)
+  // ... and whether the round runs the extended chain (0: none; 1: bias / tail-free / typical; 2: Mirostat too;
+  // + 4: some row takes the wide kernel)
   std::map<std::tuple<int, int, int, int>, hipGraphExec_t> sched_graphs;
   // pipeline stage hand-off dtype: x_in / x_out are bf16 [M][n_embd] instead of f32 (mx_opts.handoff_bf16)
   bool handoff_bf16 = false;
@@ -369,19 +373,21 @@ struct mx_engine {
   // (null: the launches are those of the plain chain), pick_miro when one of them is a Mirostat row.
   // d_mu [MAX_ROWS]: Mirostat state of the rows, d_mu_hist [MAX_ROWS][SCHED_KMAX] its value after each step
   const SampExt* pick_ext = nullptr;
-  bool pick_miro = false;
+  bool pick_miro = false, pick_wide = false;  // pick_wide: a row with more than TOPK_MAX candidates
   SampExt* d_sext = nullptr;
   float *d_bias_raw = nullptr, *d_mu = nullptr, *d_mu_hist = nullptr, *miro_wf = nullptr;
   double* miro_wd = nullptr;
   int* miro_wi = nullptr;
   std::vector<SampExt> h_sext;  // host staging of upload_ext
   std::vector<float> h_mu;
-  // SampExt rows and mu of a run over rows[0..n) to the device and pick_ext / pick_miro set; returns the level
-  // the graph key carries (0: no row has a setting, nothing copied; 1: some; 2: a Mirostat row among them)
+  // SampExt rows and mu of a run over rows[0..n) to the device and pick_ext / pick_miro / pick_wide set; returns
+  // the level the graph key carries (0: no row has a setting, nothing copied; 1: some; 2: a Mirostat row among
+  // them; + 4: a wide row among them)
   int upload_ext(Request* const* rows, int n, hipStream_t s) {
-    pick_ext = nullptr, pick_miro = false;
+    pick_ext = nullptr, pick_miro = false, pick_wide = false;
     bool any = false;
-    for (int i = 0; i < n; i++) any |= rows[i]->has_ext;
+    int kw = 0;
+    for (int i = 0; i < n; i++) any |= rows[i]->has_ext || req_path(rows[i], n_vocab, &kw) == MX_PICK_WIDE;
     if (!any) return 0;
     // the buffers of the extended chain come with its first request, so an engine that never sees one has the
     // device memory layout it always had
@@ -401,12 +407,14 @@ struct mx_engine {
       else h_sext[i].typical_p = h_sext[i].tfs_z = 1.0f;
       h_mu[i] = rows[i]->mu;
       pick_miro |= h_sext[i].miro == 2;
+      h_sext[i].wide_k = req_path(rows[i], n_vocab, &kw) == MX_PICK_WIDE ? kw : 0;
+      pick_wide |= h_sext[i].wide_k > 0;
     }
     if (hipMemcpyAsync(d_sext, h_sext.data(), n * sizeof(SampExt), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_mu, h_mu.data(), n * 4, hipMemcpyHostToDevice, s) != hipSuccess)
       return -1;
     pick_ext = d_sext;
-    return pick_miro ? 2 : 1;
+    return (pick_miro ? 2 : 1) + (pick_wide ? 4 : 0);
   }
   void pick(int n_out, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count, int max_hist,
             hipStream_t s) {
@@ -415,6 +423,7 @@ struct mx_engine {
     xa.ext = pick_samp ? pick_ext : nullptr;
     xa.bias_raw = d_bias_raw, xa.mu = d_mu, xa.mu_hist = d_mu_hist, xa.mu_stride = SCHED_KMAX;
     xa.ws_f = miro_wf, xa.ws_d = miro_wd, xa.ws_i = miro_wi, xa.any_miro = pick_miro;
+    xa.any_wide = pick_wide;
     if (lp)
       launch_logprob_stats(logits, n_vocab, n_out, n_vocab, pick_lp, tk_ws_val, tk_ws_idx, lp_part, lp_ms, lp_top,
                            lp_idx, s);
@@ -579,6 +588,9 @@ struct mx_engine {
   int *spec_ctx = nullptr, *spec_len = nullptr, *spec_par = nullptr, *spec_ndraft = nullptr, *spec_hist = nullptr;
   int *spec_hist_count = nullptr, *spec_cnt = nullptr, *spec_log = nullptr;
   uint64_t stat_spec_steps = 0, stat_spec_drafted = 0, stat_spec_accepted = 0;
+  // mx_sampler_stats: decode steps picked on the device / in sample_host, the rounds they ran in, and the
+  // row-steps of the wide kernel
+  uint64_t stat_dev_steps = 0, stat_host_steps = 0, stat_rounds = 0, stat_wide_rows = 0;
   bool spec_eligible(const Request* r) const;
   // 1 when the round ran speculating (rows updated), 0 when it has to run plain, < 0 on an error
   int sched_step_spec(std::vector<Request*>& rows);
@@ -2092,18 +2104,23 @@ bool mx::has_penalties(const mx_sampling& sp) {
 static bool needs_chain(const Request* r) {
   return r->samp.temperature > 0.f || has_penalties(r->samp) || (r->has_ext && r->ext.n_bias > 0);
 }
-// the device chain can serve the request: top_k 1..64 (a Mirostat row takes no top-k) and a window <= 64
-static bool dev_sampleable(const Request* r) {
-  if (r->has_ext && r->ext.miro == 2) {
-    mx_sampling sp = r->samp;
-    sp.top_k = 1;
-    return device_sampleable(sp);
-  }
-  return device_sampleable(r->samp);
+namespace {
+int req_path(const Request* r, int V, int* k_eff) {
+  SampExt none{};
+  none.typical_p = none.tfs_z = 1.0f;
+  return sample_path(r->samp, r->has_ext ? r->ext : none, V, k_eff);
 }
-// top-k the request asks of the device chain (what the round's K is the maximum of)
+}  // namespace
+// a device kernel can pick the request's rows: any path but the host sampler's
+static bool dev_sampleable(const Request* r, int n_vocab) {
+  int k;
+  return req_path(r, n_vocab, &k) != MX_PICK_HOST;
+}
+// top-k the request asks of the device chain (what the round's K is the maximum of): its candidates on the chain
+// path, the first one alone for a Mirostat or a wide row
 static int chain_topk(const Request* r, int n_vocab) {
-  return r->has_ext && r->ext.miro == 2 ? 1 : std::max(1, std::min(r->samp.top_k, n_vocab));
+  int k = 1;
+  return req_path(r, n_vocab, &k) == MX_PICK_CHAIN ? k : 1;
 }
 
 // bias and penalties of the host sampler on a copy of the row (the order and f32 arithmetic of the kernels)
@@ -2201,6 +2218,25 @@ bool mx::device_sampleable(const mx_sampling& sp) {
   return true;
 }
 
+// mx_sample_plan's rules, in its order (include/mx_engine.h)
+int mx::sample_path(const mx_sampling& sp, const SampExt& x, int V, int* k_eff) {
+  const bool pen = has_penalties(sp);
+  *k_eff = 1;
+  if (sp.temperature <= 0.f && !pen && x.n_bias == 0) return MX_PICK_ARGMAX;
+  if (pen && (sp.repeat_last_n < 0 || sp.repeat_last_n > SAMP_WIN)) return MX_PICK_HOST;
+  if (!(sp.temperature > 0.f)) {  // greedy never reads top_k; inside 1..64 it still sizes the round's top-k as before
+    if (sp.top_k >= 1 && sp.top_k <= TOPK_MAX) *k_eff = std::min(sp.top_k, V);
+    return MX_PICK_CHAIN;
+  }
+  if (x.miro == 2) return MX_PICK_MIROSTAT;
+  const int k = sp.top_k <= 0 || sp.top_k >= V ? V : sp.top_k;
+  *k_eff = k;
+  if (k <= TOPK_MAX) return MX_PICK_CHAIN;
+  if (x.tfs_z < 1.0f || x.typical_p < 1.0f) return MX_PICK_HOST;
+  if (V > SAMP_WIDE_VMAX) return MX_PICK_HOST;
+  return MX_PICK_WIDE;
+}
+
 void mx_engine::samp_row(const Request* r, SampRow* o) const {
   const mx_sampling& sp = r->samp;
   memset(o, 0, sizeof(*o));
@@ -2210,7 +2246,9 @@ void mx_engine::samp_row(const Request* r, SampRow* o) const {
   o->repeat = sp.repeat_penalty;
   o->freq = sp.frequency_penalty;
   o->presence = sp.presence_penalty;
-  o->top_k = std::max(1, std::min(sp.top_k, TOPK_MAX));
+  int k = 1;
+  req_path(r, n_vocab, &k);
+  o->top_k = std::max(1, std::min(k, TOPK_MAX));  // the chain path's candidates; the wide kernel reads SampExt.wide_k
   o->last_n = has_penalties(sp) ? std::min(sp.repeat_last_n, SAMP_WIN) : 0;
   o->seed = r->seed;
   o->draw0 = (int)r->out.size();
@@ -2286,7 +2324,7 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
   for (Request* r : reqs)
     if (needs_chain(r)) {
       any_sampling = true;
-      dev_pick &= dev_sampleable(r);
+      dev_pick &= dev_sampleable(r, n_vocab);
     }
   // every sampling request fits the device chain: first tokens are drawn on the device (the same
   // samp_pick and counter-based draw 0 as the host sampler), no logits rows cross PCIe
@@ -2340,8 +2378,8 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
       pick_samp = nullptr;
       pick_k = 0;
-      pick_ext = nullptr, pick_miro = false;
-      if (xl == 2) {
+      pick_ext = nullptr, pick_miro = false, pick_wide = false;
+      if (xl & 2) {
         mu_new.resize(n_out);
         HIPC(hipMemcpyAsync(mu_new.data(), d_mu, n_out * 4, hipMemcpyDeviceToHost, st));
       }
@@ -2373,6 +2411,7 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       int32_t t = tok[q0 + k];
       const bool host_pick = !dev_pick && needs_chain(r);
       if (host_pick) t = sample_host(r, lg.data() + (size_t)k * n_vocab);
+      else if (int kw = 0; dev_pick && needs_chain(r) && req_path(r, n_vocab, &kw) == MX_PICK_WIDE) stat_wide_rows++;
       if (!mu_new.empty() && r->has_ext && r->ext.miro == 2) r->mu = mu_new[k];
       r->out.push_back(t);
       r->next_tok = t;
@@ -2657,6 +2696,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
   HIPC(hipMemcpyAsync(log.data(), spec_log, log.size() * 4, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
   std::lock_guard<std::mutex> lk(mu);
+  stat_rounds++, stat_dev_steps += K;
   int emitted = 0;
   for (int i = 0; i < R; i++) {
     Request* r = rows[i];
@@ -2706,7 +2746,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     slots[i] = rows[i]->slot;
     if (needs_chain(rows[i])) {
       all_greedy = false;
-      if (use_dev_topk && dev_sampleable(rows[i])) ktop = std::max(ktop, chain_topk(rows[i], n_vocab));
+      if (use_dev_topk && dev_sampleable(rows[i], n_vocab)) ktop = std::max(ktop, chain_topk(rows[i], n_vocab));
       else all_dev = false;
     }
     room = std::min(room, n_ctx - rows[i]->pos);
@@ -2737,7 +2777,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     mx_engine* e;
     ~Reset() {
       e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1;
-      e->pick_ext = nullptr; e->pick_miro = false;
+      e->pick_ext = nullptr; e->pick_miro = false; e->pick_wide = false;
     }
   } reset_flags{this};
   // rows with the extended settings: their SampExt and mu beside the SampRows; the level joins the graph key
@@ -2812,7 +2852,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   }
   // Mirostat rows: mu after each step, so a row keeps the mu of the last step whose token it keeps
   std::vector<float> muh;
-  if (xl == 2) {
+  if (xl & 2) {
     muh.resize((size_t)M * SCHED_KMAX);
     HIPC(hipMemcpyAsync(muh.data(), d_mu_hist, muh.size() * 4, hipMemcpyDeviceToHost, s));
   }
@@ -2820,14 +2860,19 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   if (trace) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     fprintf(stderr, "sched: decode M=%d K=%d %s%s%s%s%.3f ms\n", M, K, dev_chain ? "(device sampling) " : "",
-            xl == 2 ? "(mirostat) " : xl == 1 ? "(extended chain) " : "", lpk >= 0 ? "(logprobs) " : "",
+            xl & 4 ? "(wide) " : xl & 2 ? "(mirostat) " : xl == 1 ? "(extended chain) " : "", lpk >= 0 ? "(logprobs) " : "",
             captured ? "(graph captured) " : "", ms);
   }
   std::lock_guard<std::mutex> lk(mu);
+  stat_rounds++;
+  (all_greedy || dev_chain ? stat_dev_steps : stat_host_steps) += K;
   for (int i = 0; i < M; i++) {
     Request* r = rows[i];
+    int kw = 0;
+    const bool wide = dev_chain && (xl & 4) && req_path(r, n_vocab, &kw) == MX_PICK_WIDE;
     for (int k = 0; k < K && !r->done; k++) {
       r->pos++;
+      stat_wide_rows += wide ? 1 : 0;
       int32_t t = hist[(size_t)i * SCHED_KMAX + k];
       float raw = 0.f;  // host pick: the chosen token's raw logit (candidate list or copied row)
       const bool host_pick = !dev_chain && needs_chain(r);
@@ -3469,6 +3514,23 @@ int mx_submit_spec(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s
   r->spec_d = num_pred_tokens;
   r->spec_ng = max_ngram_size;
   return enqueue_requests(e, &r, 1, req);
+}
+
+int mx_sample_plan(const mx_sampling_ext* s, int V, int32_t* path) {
+  if (!s || !path || V < 1) return fail(MX_ERR_ARG, "mx_sample_plan: settings, V >= 1 and path");
+  SampExt x;
+  bool has = false;
+  if (int rc = check_sampling_ext(s, V, &x, &has)) return rc;
+  int k = 1;
+  *path = sample_path(s->base, x, V, &k);
+  return 0;
+}
+
+int mx_sampler_stats(mx_engine* e, mx_sampler_counts* out) {
+  if (!e || !out) return fail(MX_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  *out = {e->stat_dev_steps, e->stat_host_steps, e->stat_wide_rows, e->stat_rounds};
+  return 0;
 }
 
 int mx_spec_stats(mx_engine* e, uint64_t req, mx_spec_counts* out) {

@@ -42,8 +42,13 @@ int embd_tail(const float* x, const float* w, float eps, int n, const std::vecto
 
 // ---- sampling
 bool has_penalties(const mx_sampling& sp);
-// the device chain can serve these settings: top_k 1..64 and a penalty window of 0..64 tokens
+// the per-row pick kernel can serve these settings: top_k 1..64 and a penalty window of 0..64 tokens (what the
+// stage rows of mx_batch_reset / mx_stage_rows_pick still require)
 bool device_sampleable(const mx_sampling& sp);
+// which sampler picks a row of these settings over a vocabulary of V (MX_PICK_*; the rules of mx_sample_plan, which
+// the scheduler, prefill_batch and mx_sample_probe all dispatch on), x the row's validated extended settings;
+// *k_eff: the candidates the path takes (CHAIN: 1..64, the round's top-k; WIDE: 65..V; 1 otherwise)
+int sample_path(const mx_sampling& sp, const SampExt& x, int V, int* k_eff);
 // validates the extended settings against a vocabulary of V and restates them as a SampExt (the bias table
 // copied); *has: some setting is off its default, so the request / row takes the extended chain
 int check_sampling_ext(const mx_sampling_ext* s, int V, SampExt* o, bool* has);

@@ -458,7 +458,11 @@ struct SampExt {
   int n_bias;              // distinct tokens inside the vocabulary
   int bias_tok[SAMP_BIAS_MAX];
   float bias_val[SAMP_BIAS_MAX];
+  int wide_k;              // > TOPK_MAX: the row's candidates are its first wide_k tokens of the order (V: all of
+                           // them) and sample_wide_kernel picks it; 0: any other row
 };
+// the largest vocabulary the whole-vocabulary kernels take (64 slices of 4096 columns)
+constexpr int SAMP_WIDE_VMAX = 262144;
 // Mirostat v2 of one row on the host, x = the row after bias and penalties: p = softmax(x / temp) over all V, kept =
 // surprise -log2 p_i <= mu (the argmax, ties to the lowest id, when none is), the draw u01 over the kept mass walks
 // the kept tokens by ascending id, mu -= eta (-log2 p'_tok - tau) with p' renormalised over the kept set.
@@ -477,6 +481,7 @@ struct SampExtArgs {
   double* ws_d = nullptr;        // miro_ws_doubles(M)
   int* ws_i = nullptr;           // miro_ws_ints(M)
   bool any_miro = false;         // some row has miro == 2: the Mirostat launches run
+  bool any_wide = false;         // some row has wide_k > 0: the wide launch runs (V <= SAMP_WIDE_VMAX)
 };
 // penalties (in place on the logits rows), top-k of K = max top_k of the rows, the draw, then the
 // same token bookkeeping as launch_argmax (tok_out, ids_next, pos_next, history)
@@ -485,6 +490,12 @@ int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* sam
                         int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok = nullptr,
                         float* side_val = nullptr,  // side_*: [M][SAMP_WIN] raw logits the penalties rewrote
                         const SampExtArgs* x = nullptr);  // with x->ext: bias first, tail-free / typical, Mirostat rows
+// the pick of the rows with ext[c].wide_k > 0 (every other row is skipped), after launch_topk with K >= 1 wrote the
+// rows' first candidate to tk_val / tk_idx [M][K]: the chain of samp_pick over wide_k > TOPK_MAX candidates without a
+// sort, and the bookkeeping of sample_kernel.  The logits are only read.  V <= SAMP_WIDE_VMAX.
+int launch_sample_wide(const float* logits, int ldl, int M, int V, const SampRow* samp, const SampExt* ext,
+                       const float* tk_val, const int* tk_idx, int K, int* tok_out, int* ids_next, int* pos_next,
+                       int* hist, int hist_stride, int* hist_count, int max_hist, hipStream_t s);
 // ---- per-token log-probabilities, logprob(i) = (x_i - m) - log(sum exp(x - m)) over the raw logits row
 // (DESIGN.md §9).  K = 0..min(TOPK_MAX, V) top entries per row (value descending, ties lower id first).
 // stats: one read of the rows -> part [M][64][2] slice (max, sum) partials, ms [M][2] = (m, log s) and the

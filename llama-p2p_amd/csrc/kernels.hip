@@ -1782,7 +1782,7 @@ __global__ __launch_bounds__(SAMP_BIAS_MAX) void bias_kernel(float* logits, int 
 }
 
 // sample_kernel with the tail-free and typical cuts of samp_pick; rows of Mirostat requests are left to
-// miro_pick_kernel (token and bookkeeping)
+// miro_pick_kernel, rows with more than TOPK_MAX candidates to sample_wide_kernel (token and bookkeeping)
 template <int LATE = 0>
 __global__ __launch_bounds__(64) void sample_ext_kernel(const float* tk_val, const int* tk_idx, int K,
                                                         const SampRow* samp, const SampExt* ext, int* tok_out,
@@ -1792,7 +1792,7 @@ __global__ __launch_bounds__(64) void sample_ext_kernel(const float* tk_val, con
   if (threadIdx.x != 0) return;
   const SampRow& sp = samp[c];
   const SampExt& x = ext[c];
-  if (x.miro == 2) return;
+  if (x.miro == 2 || x.wide_k > TOPK_MAX) return;  // picked by miro_pick_kernel / sample_wide_kernel
   const int nh = hist ? hist_count[c] : 0;
   double p[TOPK_MAX], w[TOPK_MAX];
   float cv[TOPK_MAX];
@@ -2003,11 +2003,452 @@ int miro_pick_host(const float* x, int V, float temp, float tau, float eta, doub
   return tok;
 }
 
+// ---------------------------------------------------------------------------
+// The candidate chain over more than TOPK_MAX candidates, up to the whole vocabulary: top_k ->
+// top_p -> min_p -> temperature -> draw as samp_pick runs them, without a sort.  Every cut keeps a prefix of one
+// total order (value descending, ties to the lower id), so the kept set is a bound (key, id) and the draw is a
+// search for a cumulative weight in the same order.  One work-group of 1024 threads per wide row; the row is only
+// read (it stays in L2 between the passes).
+//   key      wide_dkey: the f32 bits made an unsigned integer that ascends as the value descends, -0.0 folded
+//            into +0.0 first (the host comparator sees them equal: ties go by id)
+//   sweep    wide_sweep: a pass over the row, thread t taking the groups of four columns t, t + 1024, ...
+//   top_k    (k < V) the key at which the running count reaches k: 4 passes of 8 key bits over an integer
+//            histogram in LDS
+//   search   8 passes of 4 key bits.  A pass sums, per thread, the terms of the elements inside the bound whose
+//            key shares the prefix found so far into 16 buckets by the next 4 bits (f64 terms from the f32 inputs,
+//            and integer counts), reduces them (a thread's terms in sweep order, the wave64 butterfly, the 16
+//            waves in order through LDS) and walks the 16 sums in order from the carried base to the bucket that
+//            holds the target.  Elements below the prefix are in the carried base and take no exp; the first pass
+//            also gives the total.  Two uses: top_p over e_i = exp(x_i - x0), and the draw over
+//            w_i = exp(x_i / temp - x0 / temp) inside the final bound when more than 1024 candidates are kept.
+//   ties     the elements of the key a search ends on have one term: the first j of them (by id) that reach the
+//            target are taken; when that is not all of them the id of the j-th comes from an ordered scan by id
+//            (wide_nth)
+//   min_p    e_i >= min_p is monotone in the key: the last key that passes comes from a bisection of the key range
+//   small    at most 1024 candidates (every top_k <= 1024; or the kept set once the cuts are known) are gathered
+//            into LDS and ranked in the order, and one thread runs samp_pick's own loops over them
+//            (wide_pick_small): top_p, min_p and the draw for top_k <= 1024, the draw alone after the searches.
+//            A larger kept set takes the search for the draw.
+// Nothing is added in an order that depends on M, the row index, the batch-mates or the run.
+// ---------------------------------------------------------------------------
+constexpr int WIDE_NT = 1024, WIDE_NW = WIDE_NT / 64, WIDE_NB = 16;
+
+__device__ __forceinline__ uint32_t wide_dkey(float x) {
+  if (x == 0.0f) x = 0.0f;  // -0.0 -> +0.0
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x80000000u) ? b : 0x7fffffffu - b;
+}
+__device__ __forceinline__ float wide_val(uint32_t d) {
+  return __uint_as_float((d & 0x80000000u) ? d : 0x7fffffffu - d);
+}
+struct WideBound {  // the prefix of the order: the elements with (key, id) <= (t, id)
+  uint32_t t;
+  int id;
+};
+__device__ __forceinline__ bool wide_in(uint32_t d, int i, WideBound b) { return d < b.t || (d == b.t && i <= b.id); }
+constexpr int WIDE_CAP = 1024;  // kept sets up to this size are ordered in LDS and drawn from as samp_pick does
+struct WideShared {
+  double red[WIDE_NW][WIDE_NB], tot[WIDE_NB];
+  int redn[WIDE_NW][WIDE_NB], totn[WIDE_NB];
+  int wcnt[WIDE_NW];
+  int found;
+  int hist[256];
+  int lhist[256 * 16];  // the histogram of a pass in 16 copies by lane: at most 4 lanes of a wave share an address
+  double pe[WIDE_CAP];
+  int gcount;
+  uint32_t gkey[WIDE_CAP];
+  int gid[WIDE_CAP], sid[WIDE_CAP];
+  double sw[WIDE_CAP];
+};
+// one pass over the row: f(x_j, j) for every j < V.  Thread t takes the groups of four columns t, t + 1024, ...
+// (one 16-byte load each when the row is aligned, four of them in flight before the first is worked on) and
+// column 4 (V / 4) + t of the tail, whatever the alignment: the order of a thread's terms depends on V alone.
+template <class F>
+__device__ __forceinline__ void wide_sweep(const float* lr, int V, F f) {
+  const int tid = threadIdx.x, n4 = V >> 2;
+  const bool al = ((uintptr_t)lr & 15) == 0;
+  auto load = [&](int q) {
+    if (al) return reinterpret_cast<const float4*>(lr)[q];
+    return make_float4(lr[4 * q], lr[4 * q + 1], lr[4 * q + 2], lr[4 * q + 3]);
+  };
+  for (int q0 = tid; q0 < n4; q0 += 4 * WIDE_NT) {
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + u * WIDE_NT;
+      v[u] = q < n4 ? load(q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + u * WIDE_NT;
+      if (q < n4) f(v[u].x, 4 * q), f(v[u].y, 4 * q + 1), f(v[u].z, 4 * q + 2), f(v[u].w, 4 * q + 3);
+    }
+  }
+  const int j = 4 * n4 + tid;
+  if (j < V) f(lr[j], j);
+}
+struct WideHit {
+  uint32_t t;     // the key the search ended on
+  int n_below;    // elements inside the bound before that key, and with it
+  int n_at;
+  double below;   // their terms before that key
+  double total;   // all terms inside the bound
+};
+// MODE 0: counts; 1: e_i; 2: w_i
+template <int MODE>
+__device__ __forceinline__ double wide_term(float x, double x0, double temp, double m0) {
+#pragma clang fp contract(off)
+  if (MODE == 1) return exp((double)x - x0);
+  if (MODE == 2) return exp((double)x / temp - m0);
+  return 0.0;
+}
+template <int MODE>
+__device__ __forceinline__ bool wide_reached(double target, double cum, int k, int ncum) {
+  return MODE == 0 ? ncum >= k : MODE == 1 ? cum >= target : target < cum;
+}
+// the first key, in the order, at which the running count reaches k (MODE 0), the running e reaches q * total
+// (MODE 1) or exceeds it (MODE 2); the last key inside the bound when none does
+template <int MODE>
+__device__ WideHit wide_search(const float* lr, int V, WideBound bd, double x0, double temp, double m0, double q, int k,
+                               WideShared& sh) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  uint32_t prefix = 0;
+  double base = 0.0, target = 0.0, total = 0.0;
+  int nbase = 0, n_at = 0;
+  for (int p = 0; p < 8; ++p) {
+    const int shift = 28 - 4 * p;
+    double acc[WIDE_NB];
+    int cnt[WIDE_NB];
+#pragma unroll
+    for (int b = 0; b < WIDE_NB; ++b) acc[b] = 0.0, cnt[b] = 0;
+    wide_sweep(lr, V, [&](float x, int j) {
+      const uint32_t d = wide_dkey(x);
+      if ((uint32_t)((uint64_t)d >> (shift + 4)) == prefix && wide_in(d, j, bd)) {
+        const int bk = (int)((d >> shift) & 15u);
+        const double e = wide_term<MODE>(x, x0, temp, m0);
+#pragma unroll
+        for (int b = 0; b < WIDE_NB; ++b) {
+          if (MODE != 0) acc[b] += bk == b ? e : 0.0;
+          cnt[b] += bk == b ? 1 : 0;
+        }
+      }
+    });
+#pragma unroll
+    for (int b = 0; b < WIDE_NB; ++b) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        if (MODE != 0) acc[b] += __shfl_xor(acc[b], o);
+        cnt[b] += __shfl_xor(cnt[b], o);
+      }
+      if (lane == 0) sh.red[wave][b] = acc[b], sh.redn[wave][b] = cnt[b];
+    }
+    __syncthreads();
+    if (tid < WIDE_NB) {
+      double a = 0.0;
+      int n = 0;
+      for (int w = 0; w < WIDE_NW; ++w) a += sh.red[w][tid], n += sh.redn[w][tid];
+      sh.tot[tid] = a, sh.totn[tid] = n;
+    }
+    __syncthreads();
+    if (p == 0) {
+      for (int b = 0; b < WIDE_NB; ++b) total += sh.tot[b];
+      target = q * total;
+    }
+    double cum = base, pb = base;
+    int ncum = nbase, pn = nbase, pick = 0;
+    n_at = 0;
+    for (int b = 0; b < WIDE_NB; ++b) {
+      const double tb = sh.tot[b];
+      const int nb = sh.totn[b];
+      if (nb > 0) {
+        pb = cum, pn = ncum, pick = b, n_at = nb;
+        if (wide_reached<MODE>(target, cum + tb, k, ncum + nb)) break;
+      }
+      cum += tb, ncum += nb;
+    }
+    base = pb, nbase = pn;
+    prefix = (prefix << 4) | (uint32_t)pick;
+  }
+  return WideHit{prefix, nbase, n_at, base, total};
+}
+// the count cut: the key at which the running count of the order reaches k, by 4 passes of 8 key bits over an
+// integer histogram in LDS (integer atomics: the counts do not depend on their order)
+__device__ WideHit wide_count_search(const float* lr, int V, int k, WideShared& sh) {
+  const int tid = threadIdx.x;
+  uint32_t prefix = 0;
+  int nbase = 0, n_at = 0;
+  for (int p = 0; p < 4; ++p) {
+    const int shift = 24 - 8 * p;
+    for (int i = tid; i < 256 * 16; i += WIDE_NT) sh.lhist[i] = 0;
+    __syncthreads();
+    wide_sweep(lr, V, [&](float x, int j) {
+      const uint32_t d = wide_dkey(x);
+      if ((uint32_t)((uint64_t)d >> (shift + 8)) == prefix)
+        atomicAdd(&sh.lhist[((d >> shift) & 255u) * 16 + (tid & 15)], 1);
+    });
+    __syncthreads();
+    {  // bin tid / 4: four threads add 4 copies each
+      int n = 0;
+      for (int i = 0; i < 4; ++i) n += sh.lhist[(tid >> 2) * 16 + (tid & 3) * 4 + i];
+      n += __shfl_xor(n, 1);
+      n += __shfl_xor(n, 2);
+      if ((tid & 3) == 0) sh.hist[tid >> 2] = n;
+    }
+    __syncthreads();
+    int cum = nbase, pn = nbase, pick = 0;
+    n_at = 0;
+    for (int b = 0; b < 256; ++b) {
+      const int nb = sh.hist[b];
+      if (nb > 0) {
+        pn = cum, pick = b, n_at = nb;
+        if (cum + nb >= k) break;
+      }
+      cum += nb;
+    }
+    nbase = pn;
+    prefix = (prefix << 8) | (uint32_t)pick;
+    __syncthreads();  // every thread has read the histogram before the next pass clears it
+  }
+  return WideHit{prefix, nbase, n_at, 0.0, 0.0};
+}
+// the rest of the chain over a bound that holds at most WIDE_CAP candidates: they are gathered into LDS, each finds
+// its rank in the order, the first kcut of them are the candidates, every thread forms one e_i and w_i, and one
+// thread runs samp_pick's own loops (top_p, min_p, the draw) over them in that order -- the host sampler's
+// additions in the host sampler's order.  Returns the token, or -1 when the bound holds more (nothing decided).
+__device__ int wide_pick_small(const float* lr, int V, WideBound bd, int kcut, double x0, double temp, double m0,
+                               float top_p, float min_p, double u01, WideShared& sh) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid == 0) sh.gcount = 0, sh.found = -1;
+  __syncthreads();
+  wide_sweep(lr, V, [&](float x, int j) {
+    const uint32_t d = wide_dkey(x);
+    const bool in = wide_in(d, j, bd);
+    const unsigned long long bal = __ballot(in);
+    if (bal) {
+      int base = 0;
+      const int leader = __ffsll((long long)bal) - 1;
+      if (lane == leader) base = atomicAdd(&sh.gcount, __popcll(bal));
+      base = __shfl(base, leader);
+      const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
+      if (in && slot < WIDE_CAP) sh.gkey[slot] = d, sh.gid[slot] = j;
+    }
+  });
+  __syncthreads();
+  const int n = sh.gcount;
+  if (n > WIDE_CAP || n < 1) {
+    __syncthreads();
+    return -1;
+  }
+  const int k = min(n, kcut);
+  if (tid < n) {
+    const uint32_t d = sh.gkey[tid];
+    const int id = sh.gid[tid];
+    int rank = 0;
+    for (int s2 = 0; s2 < n; ++s2) {
+      const uint32_t ds = sh.gkey[s2];
+      rank += (ds < d || (ds == d && sh.gid[s2] < id)) ? 1 : 0;
+    }
+    sh.sid[rank] = id;
+    sh.pe[rank] = wide_term<1>(wide_val(d), x0, temp, m0);
+    sh.sw[rank] = wide_term<2>(wide_val(d), x0, temp, m0);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum += sh.pe[i];
+    sh.tot[0] = sum;
+  }
+  __syncthreads();
+  if (tid < k) sh.pe[tid] /= sh.tot[0];
+  __syncthreads();
+  if (tid == 0) {
+    int keep = k;
+    if (top_p < 1.0f) {
+      double cum = 0.0;
+      for (int i = 0; i < k; ++i) {
+        cum += sh.pe[i];
+        if (cum >= top_p) {
+          keep = i + 1;
+          break;
+        }
+      }
+    }
+    if (min_p > 0.f) {
+      int kk = 1;
+      for (int i = 1; i < keep; ++i)
+        if (sh.pe[i] >= min_p * sh.pe[0]) kk = i + 1;
+      keep = kk;
+    }
+    double s2 = 0.0;
+    for (int i = 0; i < keep; ++i) s2 += sh.sw[i];
+    const double u = u01 * s2;
+    double acc = 0.0;
+    int tok = sh.sid[keep - 1];
+    for (int i = 0; i < keep; ++i) {
+      acc += sh.sw[i];
+      if (u < acc) {
+        tok = sh.sid[i];
+        break;
+      }
+    }
+    sh.found = tok;
+  }
+  __syncthreads();
+  const int f = sh.found;
+  __syncthreads();
+  return f;
+}
+// how many of the n_at elements of one key (term `each`), taken in order after `below`, it takes to reach the
+// target: the smallest j >= 1, n_at when none does
+template <int MODE>
+__device__ int wide_ties(double below, double each, double target, int n_at) {
+#pragma clang fp contract(off)
+  if (n_at <= 1) return 1;
+  if (!(each > 0.0)) return wide_reached<MODE>(target, below, 0, 0) ? 1 : n_at;
+  int j = (int)fmin(fmax(ceil((target - below) / each), 1.0), (double)n_at);
+  while (j > 1 && wide_reached<MODE>(target, below + (double)(j - 1) * each, 0, 0)) --j;
+  while (j < n_at && !wide_reached<MODE>(target, below + (double)j * each, 0, 0)) ++j;
+  return j;
+}
+// the id of the r-th element (r >= 1, by ascending id) whose key is t: the 16 waves count their segments of the
+// row, then the wave holding the r-th scans its segment again
+__device__ int wide_nth(const float* lr, int V, uint32_t t, int r, WideShared& sh) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int seg = ((V + WIDE_NW - 1) / WIDE_NW + 63) & ~63;
+  const int lo = wave * seg, hi = min(V, lo + seg);
+  int n = 0;
+  for (int j0 = lo; j0 < hi; j0 += 64) {
+    const int j = j0 + lane;
+    n += __popcll(__ballot(j < hi && wide_dkey(lr[j]) == t));
+  }
+  if (lane == 0) sh.wcnt[wave] = n;
+  if (tid == 0) sh.found = -1;
+  __syncthreads();
+  int before = 0, ww = -1;
+  for (int w = 0; w < WIDE_NW; ++w) {
+    const int cw = sh.wcnt[w];
+    if (ww < 0 && r <= before + cw) ww = w;
+    if (ww < 0) before += cw;
+  }
+  if (wave == ww) {
+    int run = before;
+    for (int j0 = lo; j0 < hi; j0 += 64) {
+      const int j = j0 + lane;
+      const bool m = j < hi && wide_dkey(lr[j]) == t;
+      const unsigned long long bal = __ballot(m);
+      const int pc = __popcll(bal);
+      if (r <= run + pc) {
+        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        if (m && run + rank + 1 == r) sh.found = j;
+        break;
+      }
+      run += pc;
+    }
+  }
+  __syncthreads();
+  const int f = sh.found;
+  __syncthreads();  // every thread has read it before the next call resets it
+  return f;
+}
+
+template <int LATE = 0>
+__global__ __launch_bounds__(WIDE_NT) void sample_wide_kernel(const float* logits, int ldl, int V, const SampRow* samp,
+                                                              const SampExt* ext, const float* tk_val,
+                                                              const int* tk_idx, int K, int* tok_out, int* ids_next,
+                                                              int* pos_next, int* hist, int hist_stride,
+                                                              int* hist_count, int max_hist) {
+#pragma clang fp contract(off)
+  __shared__ WideShared sh;
+  const int c = blockIdx.x;
+  const int kw = ext[c].wide_k;
+  if (kw <= TOPK_MAX) return;
+  const SampRow& sp = samp[c];
+  const float* lr = logits + (size_t)c * ldl;
+  const int nh = hist ? hist_count[c] : 0;
+  const float x0f = tk_val[(size_t)c * K];  // the first candidate: the maximum, ties to the lowest id
+  const int id0 = min(max(tk_idx[(size_t)c * K], 0), V - 1);
+  int tok = id0;  // a row whose maximum is -inf has no distribution: its lowest id
+  if (x0f > -INFINITY) {
+    const double x0 = (double)x0f, temp = (double)sp.temp, m0 = x0 / temp;
+    const uint32_t d0 = wide_dkey(x0f);
+    WideBound bd{0xffffffffu, 0x7fffffff};
+    const double u01 = samp_u01(sp.seed, (uint64_t)(sp.draw0 + nh));
+    int f = -1;
+    if (kw <= WIDE_CAP) {
+      // few candidates: the count cut, then the whole chain over them in LDS.  The bound takes every element of
+      // the last key; the rank cuts them to kw.
+      if (kw < V) bd = WideBound{wide_count_search(lr, V, kw, sh).t, 0x7fffffff};
+      f = wide_pick_small(lr, V, bd, kw, x0, temp, m0, sp.top_p, sp.min_p, u01, sh);
+      bd = WideBound{0xffffffffu, 0x7fffffff};  // (more ties than the LDS holds: the general path, from the start)
+    }
+    if (f < 0) {
+      int n_kept = V;  // -1 once a cut leaves it unknown
+      if (kw < V) {  // top_k: the first kw of the order
+        const WideHit h = wide_count_search(lr, V, kw, sh);
+        const int r = min(max(kw - h.n_below, 1), max(h.n_at, 1));
+        // all the elements of the last key: no id bound to look for
+        bd = WideBound{h.t, r >= h.n_at ? 0x7fffffff : wide_nth(lr, V, h.t, r, sh)};
+        n_kept = kw;
+      }
+      if (sp.top_p < 1.0f) {  // through the first candidate at which the running e reaches top_p * S
+        const WideHit h = wide_search<1>(lr, V, bd, x0, temp, m0, (double)sp.top_p, 0, sh);
+        const double each = wide_term<1>(wide_val(h.t), x0, temp, m0);
+        const int j = wide_ties<1>(h.below, each, (double)sp.top_p * h.total, h.n_at);
+        bd = WideBound{h.t, j >= h.n_at ? 0x7fffffff : wide_nth(lr, V, h.t, j, sh)};
+        n_kept = h.n_below + j;
+      }
+      if (sp.min_p > 0.0f) {  // of those, through the last one with e_i >= min_p (p_i >= min_p p_0); the first stays
+        const double mp = (double)sp.min_p;
+        n_kept = -1;
+        if (!(1.0 >= mp)) {
+          bd = WideBound{d0, id0};
+        } else {
+          uint32_t lo = d0, hi = 0xff800000u;  // x0 .. -inf: no key between them is a NaN
+          while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo + 1) / 2;
+            if (wide_term<1>(wide_val(mid), x0, temp, m0) >= mp) lo = mid;
+            else hi = mid - 1;
+          }
+          if (lo < bd.t) bd = WideBound{lo, 0x7fffffff};
+        }
+      }
+      if (n_kept <= WIDE_CAP) f = wide_pick_small(lr, V, bd, 0x7fffffff, x0, temp, m0, 1.0f, 0.0f, u01, sh);
+      if (f < 0) {  // a large kept set: the search
+        const WideHit h = wide_search<2>(lr, V, bd, x0, temp, m0, u01, 0, sh);
+        const double each = wide_term<2>(wide_val(h.t), x0, temp, m0);
+        const int j = wide_ties<2>(h.below, each, u01 * h.total, h.n_at);
+        f = wide_nth(lr, V, h.t, j, sh);
+      }
+    }
+    tok = f >= 0 ? f : id0;
+  }
+  if (threadIdx.x == 0) {
+    if (tok_out) tok_out[c] = tok;
+    if (ids_next) ids_next[c] = tok;
+    if (pos_next) pos_next[c] += 1;
+    if (hist) {
+      if (nh < max_hist) hist[(size_t)c * hist_stride + nh] = tok;
+      hist_count[c] = nh + 1;
+    }
+  }
+}
+
+int launch_sample_wide(const float* logits, int ldl, int M, int V, const SampRow* samp, const SampExt* ext,
+                       const float* tk_val, const int* tk_idx, int K, int* tok_out, int* ids_next, int* pos_next,
+                       int* hist, int hist_stride, int* hist_count, int max_hist, hipStream_t s) {
+  if (M < 1 || V < 1 || V > SAMP_WIDE_VMAX || ldl < V || K < 1 || !ext || !tk_val || !tk_idx) return -1;
+  sample_wide_kernel<0><<<M, WIDE_NT, 0, s>>>(logits, ldl, V, samp, ext, tk_val, tk_idx, K, tok_out, ids_next, pos_next,
+                                              hist, hist_stride, hist_count, max_hist);
+  return 0;
+}
+
 int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* samp, int K, float* ws_val, int* ws_idx,
                         float* tk_val, int* tk_idx, int* tok_out, int* ids_next, int* pos_next, int* hist,
                         int hist_stride, int* hist_count, int max_hist, hipStream_t s, int* side_tok,
                         float* side_val, const SampExtArgs* x) {
   if (K < 1 || K > TOPK_MAX || M < 1) return -1;
+  if (x && x->any_wide && (!x->ext || V > SAMP_WIDE_VMAX)) return -1;
   const SampExt* ext = x ? x->ext : nullptr;
   const int nb = std::min(64, std::max(1, (V + 2047) / 2048));
   if (ext && x->any_miro && (!x->mu || !x->ws_f || !x->ws_d || !x->ws_i || (V + nb - 1) / nb > 4096)) return -1;
@@ -2031,6 +2472,10 @@ int launch_sample_chain(float* logits, int ldl, int M, int V, const SampRow* sam
                                       x->mu_stride, tok_out, ids_next, pos_next, hist, hist_stride, hist_count,
                                       max_hist);
   }
+  if (x->any_wide &&
+      launch_sample_wide(logits, ldl, M, V, samp, ext, tk_val, tk_idx, K, tok_out, ids_next, pos_next, hist,
+                         hist_stride, hist_count, max_hist, s))
+    return -1;
   return 0;
 }
 

@@ -223,7 +223,7 @@ int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl,
   std::vector<SampExt> sx(n);
   std::vector<SampRow> sr(n, SampRow{});
   int ktop = 1;
-  bool any_miro = false;
+  bool any_miro = false, any_wide = false;
   for (int i = 0; i < n; i++) {
     bool has = false;
     if (int rc = check_sampling_ext(&samp[i], V, &sx[i], &has)) return rc;
@@ -233,14 +233,18 @@ int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl,
       if (win[i * SAMP_WIN + j] < 0 || win[i * SAMP_WIN + j] >= V) return fail(MX_ERR_ARG, "mx_sample_probe: window token outside the vocabulary");
     if (std::isnan(sp.temperature) || std::isnan(mu_in[i])) return fail(MX_ERR_ARG, "mx_sample_probe: NaN setting");
     if (device >= 0) {
-      mx_sampling d = sp;
-      if (sx[i].miro == 2 || sp.temperature <= 0.f) d.top_k = 1;
-      if (!device_sampleable(d))
-        return fail(MX_ERR_ARG, "mx_sample_probe: settings outside the device chain (top_k 1..64, repeat_last_n 0..64)");
+      int k = 1;
+      const int path = sample_path(sp, sx[i], V, &k);
+      if (path == MX_PICK_HOST)
+        return fail(MX_ERR_ARG, "mx_sample_probe: settings of the host sampler (repeat_last_n outside 0..64, or "
+                                "tfs_z / typical_p over more than 64 candidates)");
+      sx[i].wide_k = path == MX_PICK_WIDE ? k : 0;
+      if (path != MX_PICK_CHAIN || sp.temperature <= 0.f) k = 1;
+      any_wide |= sx[i].wide_k > 0;
       SampRow& o = sr[i];
       o.temp = sp.temperature, o.top_p = sp.top_p, o.min_p = sp.min_p;
       o.repeat = sp.repeat_penalty, o.freq = sp.frequency_penalty, o.presence = sp.presence_penalty;
-      o.top_k = std::max(1, std::min(d.top_k, TOPK_MAX));
+      o.top_k = std::max(1, std::min(k, TOPK_MAX));
       o.last_n = has_penalties(sp) ? std::min(sp.repeat_last_n, SAMP_WIN) : 0;
       o.seed = seeds[i];
       o.draw0 = n_drawn[i];
@@ -284,7 +288,7 @@ int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl,
   HIPC(hipMemcpy(d_mu, mu_in, (size_t)n * 4, hipMemcpyHostToDevice));
   SampExtArgs xa;
   xa.ext = d_sx, xa.bias_raw = d_braw, xa.mu = d_mu, xa.ws_f = d_wf, xa.ws_d = d_wd, xa.ws_i = d_wi;
-  xa.any_miro = any_miro;
+  xa.any_miro = any_miro, xa.any_wide = any_wide;
   if (launch_sample_chain(d_lg, ldl, n, V, d_sr, ktop, d_wsv, d_wsi, d_tkv, d_tki, d_tok, nullptr, nullptr, nullptr, 0,
                           nullptr, 0, nullptr, nullptr, nullptr, &xa))
     return fail(MX_ERR_ARG, "mx_sample_probe: launch shape (V too large for the top-k slices)");

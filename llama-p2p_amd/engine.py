@@ -38,6 +38,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
     "mx_engine_set_host_cache", "mx_host_cache_stats", "mx_kv_pack_probe",
     "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
+    "mx_sample_plan", "mx_sampler_stats",
     "mx_glue_probe",
 ]
 # the Q8_0 / Q4_0 kernel probes: names with a digit, listed apart (tests/test_gguf_abi.py checks both lists)
@@ -45,6 +46,8 @@ EXPORTS_Q8 = ["mx_q8_matmul_probe", "mx_q8_matmul_plan", "mx_q8_side_probe"]
 LOGIT_BIAS_MAX = 256  # kernels.h SAMP_BIAS_MAX: most logit_bias entries per request
 POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3  # mx_engine.h MX_POOL_*: how embed() pools a sequence's rows
 TOPK_MAX = 64  # kernels.h: most top entries per token (logprobs=, device top_k)
+# mx_engine.h MX_PICK_*: which sampler picks a row (sample_plan())
+MX_PICK_ARGMAX, MX_PICK_CHAIN, MX_PICK_MIROSTAT, MX_PICK_WIDE, MX_PICK_HOST = 0, 1, 2, 3, 4
 SPEC_MAX_DRAFT = 15  # kernels.h: most draft tokens per speculating step (1 + 15 rows of the <= 16-row path)
 
 
@@ -117,6 +120,11 @@ class MxRowSampler(ctypes.Structure):
 
 class MxSpecCounts(ctypes.Structure):
     _fields_ = [("steps", ctypes.c_uint64), ("drafted", ctypes.c_uint64), ("accepted", ctypes.c_uint64)]
+
+
+class MxSamplerCounts(ctypes.Structure):
+    _fields_ = [("device_steps", ctypes.c_uint64), ("host_steps", ctypes.c_uint64), ("wide_rows", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint64)]
 
 
 class MxSharingStats(ctypes.Structure):
@@ -331,6 +339,8 @@ def lib() -> ctypes.CDLL:
         L.mx_sampling_ext_default.argtypes = [P(MxSamplingExt)]
         L.mx_submit_ext.argtypes = [vp, vp, i32, P(MxSamplingExt), i32, i32, i32, P(u64)]
         L.mx_submit_ext_batch.argtypes = [vp, i32, vp, vp, vp, vp, P(u64)]
+        L.mx_sample_plan.argtypes = [P(MxSamplingExt), i32, P(i32)]
+        L.mx_sampler_stats.argtypes = [vp, P(MxSamplerCounts)]
         L.mx_sample_probe.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for name in EXPORTS + EXPORTS_Q8:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_sampling_ext_default", "mx_last_error",
@@ -383,6 +393,20 @@ def logprob_probe(logits, targets, k: int, V: Optional[int] = None, device: int 
     _check(lib().mx_logprob_probe(device, lg.ctypes.data, n, V, ldl, tg.ctypes.data, k, tgt.ctypes.data,
                                   top.ctypes.data if ke else None, idx.ctypes.data if ke else None))
     return tgt, top, idx
+
+
+def sample_plan(settings: dict, V: int) -> int:
+    """Which sampler picks the rows of a request with these settings (the keywords of Engine.submit) over a
+    vocabulary of V: one of MX_PICK_ARGMAX / CHAIN / MIROSTAT / WIDE / HOST (include/mx_engine.h mx_sample_plan;
+    no GPU).  Settings mx_submit_ext refuses raise MxError(MX_ERR_ARG)."""
+    kw = dict(settings)
+    ext = {k: kw.pop(k) for k in _EXT_KEYS if k in kw}
+    kw.pop("seed", None)
+    x, keep = sampling_ext(sampling(**kw), **ext)
+    path = ctypes.c_int32(-1)
+    _check(lib().mx_sample_plan(ctypes.byref(x), int(V), ctypes.byref(path)))
+    del keep
+    return path.value
 
 
 def sample_probe(logits, settings, seeds, n_drawn, windows=None, mu_in=None, V: Optional[int] = None,
@@ -1553,6 +1577,14 @@ class Engine:
             _check(L.mx_request_logprobs(self._h, req, tok.ctypes.data, top.ctypes.data if kk else None,
                                          idx.ctypes.data if kk else None, cap, ctypes.byref(n), ctypes.byref(k)))
         return tok, top, idx
+
+    def sampler_stats(self) -> dict:
+        """device_steps / host_steps (decode steps picked on the device / by the host sampler), wide_rows (row-steps
+        of the wide kernel: more than 64 candidates) and rounds (the scheduler rounds behind the
+        steps) -- include/mx_engine.h mx_sampler_counts."""
+        c = MxSamplerCounts()
+        _check(lib().mx_sampler_stats(self._h, ctypes.byref(c)))
+        return {k: getattr(c, k) for k, _ in MxSamplerCounts._fields_}
 
     def spec_stats(self, req: Optional[int] = None) -> dict:
         """Speculation counters of a request not yet released by wait(), or (None) the engine's totals: steps

@@ -204,6 +204,10 @@ class Llama:
                           mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1,
                           logit_bias: Optional[Dict[int, float]] = None,
                           **kwargs: Any) -> Union[Dict[str, Any], Iterator[Dict[str, Any]]]:
+        """llama-cpp-python's create_completion.  Every sampler setting is applied on the device, several decode
+        steps per host round trip; top_k takes any value (<= 0 or at least the vocabulary size: every token is a
+        candidate, as in llama-cpp-python).  Only a penalty window over 64 tokens, and tfs_z / typical_p over
+        more than 64 candidates, are sampled on the host (engine.sample_plan tells)."""
         ext_kw = self._sampler_ext_kw(typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
         if logprobs is not None:
             if logprobs < 0 or logprobs > _engine.TOPK_MAX:

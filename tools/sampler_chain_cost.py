@@ -1,5 +1,6 @@
-"""What the sampler chain costs per decode step (DESIGN.md §13): greedy, the default chain, typical + tail-free,
-a 256-entry logit_bias and Mirostat v2, 1 and 32 rows, in the scheduler's multi-step device rounds.
+"""What the sampler chain costs per decode step (DESIGN.md §13, §15): greedy, the default chain, typical + tail-free,
+a 256-entry logit_bias, Mirostat v2 and more than 64 candidates (top_k = 0, top_k = 100: the wide kernel; the host
+sampler in a tree from before it), 1 and 32 rows, in the scheduler's rounds.
 
     python tools/sampler_chain_cost.py [--model synthetic:llama3-8b:seed=0] [--tokens 64] [--out profiles/sampler_chain.txt]
                                        [--baseline PATH ...]
@@ -9,10 +10,14 @@ completion (captures the round's graph) and a timed one of --tokens tokens for e
 trace line of a round ("sched: decode M=.. K=.. ... ms": host clock from the round's first copy to its
 synchronise, K decode steps) gives ms per step = ms / K; rounds that captured a graph and the short last round
 are left out, the median, minimum and maximum of the rest are reported, with the trace lines of one round each.
+A host-sampled round's trace ends at its synchronise, before the host sampler runs, so every configuration also
+reports the wall clock of the timed completion per token (submit to the last wait, its prefill included): that is
+the figure to compare a host-sampled configuration by.
 
---baseline PATH: a checkout of another commit with its library built (e.g. the parent); its greedy and default
-chain are measured by the same child, importing that tree's package, before and after this tree's run, so the
-two baseline runs bracket it on the same machine in the same session.
+--baseline PATH: a checkout of another commit with its library built (e.g. the parent); its greedy, default chain,
+top_k = 0 and top_k = 100 (one host-sampled step per round there) are measured by the same child, importing that
+tree's package, before and after this tree's run, so the two baseline runs bracket it on the same machine in the
+same session.
 """
 import argparse
 import os
@@ -20,6 +25,7 @@ import re
 import statistics
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,8 +36,10 @@ CONFIGS = {
     "typical + tfs": dict(temperature=0.8, typical_p=0.9, tfs_z=0.95),
     "bias (256 entries)": dict(temperature=0.8, logit_bias=BIAS),
     "mirostat v2": dict(temperature=0.8, mirostat_mode=2),
+    "top_k=0": dict(temperature=0.8, top_k=0),
+    "top_k=100": dict(temperature=0.8, top_k=100),
 }
-OLD = ("greedy", "default chain")  # what a tree from before the extended chain can run
+OLD = ("greedy", "default chain", "top_k=0", "top_k=100")  # what a tree from before the extended chain can run
 
 
 def child(a):
@@ -46,10 +54,12 @@ def child(a):
             prompts = [np.concatenate([[1], rng.integers(3, eng.n_vocab, 7)]).astype(np.int32) for _ in range(rows)]
             for phase in ("warm-up", "timed"):
                 print(f"cfg: {name} | {rows} | {phase}", file=sys.stderr, flush=True)
+                t0 = time.perf_counter()
                 reqs = eng.submit_many(prompts, a.tokens, seeds=list(range(1, rows + 1)), ignore_eos=True,
                                        **CONFIGS[name])
                 for r in reqs:
                     eng.wait(r)
+                print(f"wall: {1e3 * (time.perf_counter() - t0) / a.tokens:.4f}", file=sys.stderr, flush=True)
     eng.close()
 
 
@@ -58,19 +68,23 @@ def run_child(a, tree, configs):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--model", a.model, "--tokens",
            str(a.tokens), "--rows", ",".join(map(str, a.rows)), "--configs", ";".join(configs)]
     print(f"measuring {len(configs)} configurations over {tree} ...", file=sys.stderr, flush=True)
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=a.timeout)
     if p.returncode != 0:
         raise SystemExit(f"child over {tree} failed ({p.returncode}):\n{p.stderr[-3000:]}")
-    out, key = {}, None
+    out, wall, key = {}, {}, None
     for line in p.stderr.splitlines():
         m = re.match(r"cfg: (.*) \| (\d+) \| (.*)", line)
         if m:
             key = (m[1], int(m[2])) if m[3] == "timed" else None
             continue
+        m = re.match(r"wall: ([0-9.]+)", line)
+        if m and key:
+            wall[key] = float(m[1])
+            continue
         m = re.match(r"sched: decode M=(\d+) K=(\d+) (.*?)([0-9.]+) ms", line)
         if m and key:
             out.setdefault(key, []).append((int(m[2]), float(m[4]), "graph captured" in m[3], line))
-    return out
+    return out, wall
 
 
 def summarise(rounds):
@@ -87,6 +101,7 @@ def main():
     ap.add_argument("--rows", default="1,32")
     ap.add_argument("--baseline", action="append", default=[])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--timeout", type=int, default=600, help="seconds one child process may take")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--configs", default=";".join(CONFIGS), help=argparse.SUPPRESS)
@@ -104,14 +119,16 @@ def main():
     lines = [f"sampler chain cost: {a.model}, {a.tokens} tokens per request after a warm-up completion, rows {a.rows}; "
              f"ms per decode step = a round's traced time / its K steps, rounds of the largest K without a graph "
              f"capture; every run is one child process with one engine, in the order listed"]
-    med = {}
-    for label, out in runs:
+    med, wal = {}, {}
+    for label, (out, wall) in runs:
         lines.append(f"-- {label}")
         for (name, rows), rounds in out.items():
             steps, k, sample = summarise(rounds)
             med[(label, name, rows)] = statistics.median(steps)
+            wal[(label, name, rows)] = wall[(name, rows)]
             lines.append(f"{name:>20s}, {rows:2d} rows: median {statistics.median(steps):.4f} ms/step, min {min(steps):.4f}, "
-                         f"max {max(steps):.4f} ({len(steps)} rounds of K={k})   | {sample}")
+                         f"max {max(steps):.4f} ({len(steps)} rounds of K={k}), wall {wall[(name, rows)]:.4f} ms/token"
+                         f"   | {sample}")
     here = {(n, r): v for (lab, n, r), v in med.items() if lab == "this tree"}
     lines.append("-- over the default chain, this tree (medians)")
     for (name, rows), v in here.items():
@@ -127,6 +144,13 @@ def main():
                 v = here[(name, rows)]
                 where = "inside" if lo <= v <= hi else ("below" if v < lo else "above")
                 lines.append(f"{name:>20s}, {rows:2d} rows: {v:.4f} ms/step, baseline runs {lo:.4f} .. {hi:.4f}: {where} their spread")
+        lines.append("-- wall clock per token (host sampling included), this tree against the baseline runs")
+        for name in OLD:
+            for rows in a.rows:
+                base = [v for (lab, n, r), v in wal.items() if lab != "this tree" and n == name and r == rows]
+                v = wal[("this tree", name, rows)]
+                lines.append(f"{name:>20s}, {rows:2d} rows: {v:.4f} ms/token, baseline runs {min(base):.4f} .. {max(base):.4f}"
+                             f" ({min(base) / v:.2f}x .. {max(base) / v:.2f}x)")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
