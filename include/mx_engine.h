@@ -127,6 +127,42 @@ void mx_engine_destroy(mx_engine* e);
 int mx_gguf_check(const char* path);
 int mx_engine_info(const mx_engine* e, mx_model_info* out);
 
+/* LoRA adapters (llama-cpp-python's Llama(lora_path=, lora_scale=)), DESIGN.md §16.  The adapter is merged into
+ * the weights while the model loads: for every base matrix T with a pair, W' = bf16(W + scale B A) with A =
+ * T.lora_a (f32 [r][n_in]), B = T.lora_b (f32 [n_out][r]), scale = lora_scale * adapter.lora.alpha / r (lora_scale
+ * alone when alpha is 0; llama.cpp's rule), the sum over r and the update in f32, one RNE rounding to bf16.  The
+ * engine then is the one a BF16 GGUF of the merged model would give -- not llama.cpp's run-time adapter, which adds
+ * scale B (A x) beside every product and never rounds W' -- and every kernel, row count and graph runs as without.
+ * A quantised base (Q8_0, Q4_0, K-quants) leaves its native path: every matrix, token_embd included, is dequantised
+ * to bf16 at load, mx_model_info.weight_type is 30 and the weights take 2 bytes per element.
+ * lora_path: a GGUF written by convert_lora_to_gguf.py: general.type "adapter", adapter.type "lora",
+ * general.architecture "llama"; tensors T.lora_a ne {n_in, r} and T.lora_b ne {r, n_out} (F32, F16 or BF16) for
+ * any subset of blk.N.{attn_q,attn_k,attn_v,attn_output,ffn_gate,ffn_up,ffn_down}.weight, r per tensor, merged in
+ * GGUF order (the converter has permuted q / k already).  Checked against the base before anything is allocated
+ * on the device; MX_ERR_MODEL with the tensor or key named for a wrong type key, a half pair, a shape that does
+ * not fit the base, r < 1, a target outside the base or the seven matrices, a quantised adapter tensor.  Pairs of
+ * layers outside [layer_begin, layer_end) are skipped.  lora_scale == 0 and tensors without a pair skip the merge:
+ * those weights are the base's bit for bit.  A "synthetic:" base, a NULL path, a non-finite scale: MX_ERR_ARG. */
+int mx_engine_create_lora(const char* model_path, const mx_opts* opts, const char* lora_path, float lora_scale,
+                          mx_engine** out);
+/* The same validation of an adapter against its base, no GPU touched (as mx_gguf_check). */
+int mx_lora_check(const char* model_path, const char* lora_path);
+/* n_tensors: matrices of this engine's layers the adapter was merged into (0 without an adapter or with
+ * lora_scale 0); rank_max: the largest r among them; alpha, lora_scale: as loaded (0 without an adapter). */
+typedef struct {
+  int32_t n_tensors, rank_max;
+  float alpha, lora_scale;
+} mx_lora_info;
+int mx_engine_lora_info(const mx_engine* e, mx_lora_info* out);
+/* launch_lora_merge, the production launch, on caller-supplied data, no engine: w bf16 [rows][cols], A f32
+ * [r][cols], B f32 [rows][r]; rows, cols 1..65536 with rows * cols <= 2^28, r 1..4096, scale finite.  out: uint16
+ * [rows * cols + 4096], filled with 0xFF bytes before the launch (the last 4096 elements are a guard that must come
+ * back as 0xFF); it receives w merged by one launch.  iters > 0: the kernel alone is then launched iters more
+ * times (on the merged matrix, after two warm-up launches) between two HIP events, *us_per_launch the mean;
+ * iters == 0 leaves it alone.  Anything else is MX_ERR_ARG and nothing is launched. */
+int mx_lora_merge_probe(int device, int rows, int cols, int r, const uint16_t* w, const float* A, const float* B,
+                        float scale, uint16_t* out, int iters, double* us_per_launch);
+
 /* Parity hook: evaluate n tokens of sequence `slot` at positions pos0..pos0+n-1
  * (prefill or decode, chunked internally by 64 rows) and copy the f32 logits of
  * every row to logits_out[n][n_vocab]; NULL skips lm_head entirely (prefill). */

@@ -328,6 +328,12 @@ struct mx_engine {
   int kq_main_type = 0;          // type of ffn_gate (mx_model_info.weight_type)
   int embd_kq_type = 0;          // token_embd kept as K-quant GGUF blocks when non-zero
   uint8_t* tok_embd_kq = nullptr;
+  // LoRA adapter merged at load: opened and checked against the base before the engine touches
+  // the device, released when load_gguf returns; the counters are what mx_engine_lora_info reports
+  std::unique_ptr<LoraAdapter> lora;
+  float lora_scale = 0.f, lora_alpha = 0.f;
+  int lora_merged = 0, lora_rank_max = 0;
+  bool has_lora = false;
   float* xkb = nullptr;
   KqMat kq_out;
   int8_t* xq8 = nullptr;    // Q8_0 activation rows [PREFILL_ROWS][max(h, ff)]
@@ -1024,7 +1030,15 @@ int mx_engine::load_gguf(const std::string& path) {
     if (wq8 && !out_q8) deq = false;
     embd_q8 = te->type == 8;
     if (wkq && (te->type == 12 || te->type == 13 || te->type == 14)) embd_kq_type = te->type;
-    if (te->type != 30 && te->type != 8) {
+    if (lora) {
+      // an adapter is merged into bf16 matrices: the native Q8_0 / Q4_0 / K-quant paths are off and every
+      // matrix, token_embd included, is dequantised to bf16 at load -- the model a BF16 file of the merged
+      // weights would give
+      wq8 = out_q8 = wq4 = out_q4 = out_kq_head = wkq = embd_q8 = false;
+      kq_main_type = embd_kq_type = 0;
+      deq = n30 != (int)mats.size();
+    }
+    if (te->type != 30 && !embd_q8) {
       if (!ggml_block_elems(te->type))
         return fail(MX_ERR_MODEL, "token_embd.weight: ggml type " + std::to_string(te->type) + " is not supported");
       raw_max = std::max(raw_max, (size_t)te->nbytes);
@@ -1039,11 +1053,30 @@ int mx_engine::load_gguf(const std::string& path) {
   uint16_t* stage = nullptr;
   uint8_t* stage_raw = nullptr;
   HIPC(hipMalloc((void**)&stage, stage_bytes));
-  if (raw_max && (deq || wkq || out_kq_head || (te->type != 30 && te->type != 8))) {
+  if (raw_max && (deq || wkq || out_kq_head || (te->type != 30 && !embd_q8))) {
     if (hipMalloc((void**)&stage_raw, raw_max) != hipSuccess) {
       hipFree(stage);
       return fail(MX_ERR_HIP, "staging buffer");
     }
+  }
+  // the largest A and B of the adapter's pairs in this stage's layers, as f32
+  float *lora_a = nullptr, *lora_b = nullptr;
+  std::vector<float> lora_host;
+  if (lora && lora_scale != 0.f) {
+    size_t amax = 0, bmax = 0;
+    for (const auto& kvp : lora->pairs) {
+      const LoraPair& p = kvp.second;
+      if (p.layer < lb || p.layer >= le) continue;
+      amax = std::max(amax, (size_t)p.r * p.n_in);
+      bmax = std::max(bmax, (size_t)p.r * p.n_out);
+    }
+    if (amax && (hipMalloc((void**)&lora_a, amax * 4) != hipSuccess || hipMalloc((void**)&lora_b, bmax * 4) != hipSuccess)) {
+      hipFree(stage);
+      if (stage_raw) hipFree(stage_raw);
+      if (lora_a) hipFree(lora_a);
+      return fail(MX_ERR_HIP, "LoRA staging buffers");
+    }
+    lora_host.resize(std::max(amax, bmax));
   }
   // any supported type -> bf16 row-major in `stage`
   auto to_bf16 = [&](const GGUFTensor* t, size_t n) -> int {
@@ -1078,6 +1111,21 @@ int mx_engine::load_gguf(const std::string& path) {
       else launch_pack_q8((uint8_t*)dst, (const uint8_t*)stage, rows, cols, mode, offset, stream);
     } else {
       if (int rc = to_bf16(t, (size_t)rows * cols)) return rc;
+      if (lora_a) {  // W' = bf16(W + scale B A) on the row-major matrix, before it is packed
+        const auto it = lora->pairs.find(name);
+        if (it != lora->pairs.end()) {
+          const LoraPair& p = it->second;
+          if (p.n_in != cols || p.n_out != rows) return fail(MX_ERR_MODEL, "LoRA adapter: shape of " + name);
+          lora->to_f32(*p.a, lora_host.data());
+          HIPC(hipMemcpy(lora_a, lora_host.data(), (size_t)p.r * cols * 4, hipMemcpyHostToDevice));
+          lora->to_f32(*p.b, lora_host.data());
+          HIPC(hipMemcpy(lora_b, lora_host.data(), (size_t)p.r * rows * 4, hipMemcpyHostToDevice));
+          if (launch_lora_merge(stage, lora_a, lora_b, rows, cols, p.r, lora->scale(p, lora_scale), stream))
+            return fail(MX_ERR_MODEL, "LoRA merge of " + name);
+          lora_merged++;
+          lora_rank_max = std::max(lora_rank_max, p.r);
+        }
+      }
       launch_pack(dst, stage, rows, cols, mode, offset, stream);
     }
     HIPC(hipStreamSynchronize(stream));
@@ -1175,7 +1223,7 @@ int mx_engine::load_gguf(const std::string& path) {
       rc = fail(MX_ERR_MODEL, "tensor token_embd.weight has unexpected shape");
       goto out;
     }
-    if (t->type == 30 || t->type == 8) {  // rows used as stored (Q8_0 rows dequantised per lookup)
+    if (t->type == 30 || embd_q8) {  // rows used as stored (Q8_0 rows dequantised per lookup)
       void** dst = embd_q8 ? (void**)&tok_embd8 : (void**)&tok_embd;
       if ((rc = alloc(dst, t->nbytes))) goto out;
       if (hipMemcpy(*dst, f.data(*t), t->nbytes, hipMemcpyHostToDevice) != hipSuccess) {
@@ -1245,6 +1293,8 @@ out:
   hipStreamSynchronize(stream);
   hipFree(stage);
   if (stage_raw) hipFree(stage_raw);
+  if (lora_a) hipFree(lora_a);
+  if (lora_b) hipFree(lora_b);
   return rc;
 }
 
@@ -3185,14 +3235,37 @@ void mx_sampling_default(mx_sampling* s) {
 
 const char* mx_last_error(void) { return g_err.c_str(); }
 
-int mx_engine_create(const char* model_path, const mx_opts* opts, mx_engine** out) {
-  if (!model_path || !out) return fail(MX_ERR_ARG, "null argument");
-  *out = nullptr;
+// the checks of mx_lora_check and mx_engine_create_lora: both files opened and the adapter validated against the
+// base, no GPU touched
+static int lora_open(const char* model_path, const char* lora_path, std::unique_ptr<LoraAdapter>& ad) {
+  if (!model_path || !lora_path) return fail(MX_ERR_ARG, "null argument");
+  if (std::string(model_path).rfind("synthetic:", 0) == 0)
+    return fail(MX_ERR_ARG, "a LoRA adapter needs a GGUF base model, not a synthetic: one");
+  GGUFFile base;
+  std::string err = base.open(model_path);
+  if (!err.empty()) return fail(MX_ERR_MODEL, err);
+  ad.reset(new LoraAdapter());
+  err = ad->open(lora_path, base);
+  if (!err.empty()) {
+    ad.reset();
+    return fail(MX_ERR_MODEL, err);
+  }
+  return 0;
+}
+
+static int engine_create(const char* model_path, const mx_opts* opts, std::unique_ptr<LoraAdapter> lora,
+                         float lora_scale, mx_engine** out) {
   mx_opts o;
   mx_opts_default(&o);
   if (opts) o = *opts;
   if (o.n_ctx < 1 || o.n_seq_max < 1) return fail(MX_ERR_ARG, "n_ctx and n_seq_max must be >= 1");
   std::unique_ptr<mx_engine> e(new mx_engine());
+  if (lora) {
+    e->has_lora = true;
+    e->lora_scale = lora_scale;
+    e->lora_alpha = lora->alpha;
+    e->lora = std::move(lora);
+  }
   e->n_ctx = o.n_ctx;
   e->n_seq_max = o.n_seq_max;
   e->lb = o.layer_begin;
@@ -3235,8 +3308,39 @@ int mx_engine_create(const char* model_path, const mx_opts* opts, mx_engine** ou
   } else {
     rc = e->load_gguf(path);
   }
+  e->lora.reset();  // the adapter file is needed no longer
   if (rc) return rc;
   *out = e.release();
+  return 0;
+}
+
+int mx_engine_create(const char* model_path, const mx_opts* opts, mx_engine** out) {
+  if (!model_path || !out) return fail(MX_ERR_ARG, "null argument");
+  *out = nullptr;
+  return engine_create(model_path, opts, nullptr, 0.f, out);
+}
+
+int mx_engine_create_lora(const char* model_path, const mx_opts* opts, const char* lora_path, float lora_scale,
+                          mx_engine** out) {
+  if (!model_path || !lora_path || !out) return fail(MX_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (!std::isfinite(lora_scale)) return fail(MX_ERR_ARG, "lora_scale must be finite");
+  std::unique_ptr<LoraAdapter> ad;
+  if (int rc = lora_open(model_path, lora_path, ad)) return rc;  // before any device allocation
+  return engine_create(model_path, opts, std::move(ad), lora_scale, out);
+}
+
+int mx_lora_check(const char* model_path, const char* lora_path) {
+  std::unique_ptr<LoraAdapter> ad;
+  return lora_open(model_path, lora_path, ad);
+}
+
+int mx_engine_lora_info(const mx_engine* e, mx_lora_info* o) {
+  if (!e || !o) return fail(MX_ERR_ARG, "null argument");
+  o->n_tensors = e->lora_merged;
+  o->rank_max = e->lora_rank_max;
+  o->alpha = e->has_lora ? e->lora_alpha : 0.f;
+  o->lora_scale = e->has_lora ? e->lora_scale : 0.f;
   return 0;
 }
 

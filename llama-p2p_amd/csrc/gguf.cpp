@@ -181,4 +181,101 @@ const GGUFTensor* GGUFFile::tensor(const std::string& name) const {
   return it == tensors.end() ? nullptr : &it->second;
 }
 
+namespace {
+// blk.N.<one of the seven layer matrices>.weight -> N, else -1
+int lora_target_layer(const std::string& name) {
+  static const char* kinds[] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"};
+  if (name.rfind("blk.", 0) != 0) return -1;
+  const size_t dot = name.find('.', 4);
+  if (dot == std::string::npos || dot == 4 || dot > 4 + 6) return -1;
+  int layer = 0;
+  for (size_t i = 4; i < dot; i++) {
+    if (name[i] < '0' || name[i] > '9') return -1;
+    layer = layer * 10 + (name[i] - '0');
+  }
+  const std::string rest = name.substr(dot + 1);
+  for (const char* k : kinds)
+    if (rest == std::string(k) + ".weight") return layer;
+  return -1;
+}
+bool ends_with(const std::string& s, const char* suf) {
+  const size_t n = strlen(suf);
+  return s.size() > n && s.compare(s.size() - n, n, suf) == 0;
+}
+}  // namespace
+
+std::string LoraAdapter::open(const std::string& path, const GGUFFile& base) {
+  const std::string err = file.open(path);
+  if (!err.empty()) return err;
+  const auto str = [&](const char* key) {
+    const GGUFValue* v = file.get(key);
+    return v && v->type == T_STRING ? v->str : std::string();
+  };
+  if (str("general.type") != "adapter") return "LoRA adapter: general.type must be 'adapter', got '" + str("general.type") + "'";
+  if (str("adapter.type") != "lora") return "LoRA adapter: adapter.type must be 'lora', got '" + str("adapter.type") + "'";
+  if (str("general.architecture") != "llama")
+    return "LoRA adapter: general.architecture must be 'llama', got '" + str("general.architecture") + "'";
+  alpha = (float)file.get_num("adapter.lora.alpha", 0.0);
+  if (!(alpha == alpha) || alpha - alpha != 0.f) return "LoRA adapter: adapter.lora.alpha is not finite";
+  pairs.clear();
+  for (const auto& kvp : file.tensors) {
+    const GGUFTensor& t = kvp.second;
+    const bool is_a = ends_with(t.name, ".lora_a"), is_b = ends_with(t.name, ".lora_b");
+    if (!is_a && !is_b) return "LoRA adapter: tensor " + t.name + " is neither a .lora_a nor a .lora_b";
+    if (t.type != 0 && t.type != 1 && t.type != 30)
+      return "LoRA adapter: tensor " + t.name + " has ggml type " + std::to_string(t.type) +
+             " (F32, F16 and BF16 adapters are supported, quantised ones are not)";
+    const std::string target = t.name.substr(0, t.name.size() - 7);
+    if (!file.tensor(target + (is_a ? ".lora_b" : ".lora_a")))
+      return "LoRA adapter: tensor " + t.name + " has no " + target + (is_a ? ".lora_b" : ".lora_a");
+    if (!is_a) continue;  // the pair is checked once, at its .lora_a
+    const GGUFTensor& b = *file.tensor(target + ".lora_b");
+    const int layer = lora_target_layer(target);
+    if (layer < 0)
+      return "LoRA adapter: target " + target +
+             " is not supported (blk.N.{attn_q,attn_k,attn_v,attn_output,ffn_gate,ffn_up,ffn_down}.weight are)";
+    const GGUFTensor* w = base.tensor(target);
+    if (!w) return "LoRA adapter: target " + target + " is not a tensor of the base model";
+    if (w->ne.size() != 2 || t.ne.size() != 2 || b.ne.size() != 2)
+      return "LoRA adapter: " + target + ": the base tensor, .lora_a and .lora_b must have two dimensions";
+    if (b.ne[0] < 1 || t.ne[1] < 1) return "LoRA adapter: " + target + " has rank 0";
+    if (t.ne[0] != w->ne[0]) return "LoRA adapter: " + t.name + " ne[0] does not match " + target + " ne[0]";
+    if (b.ne[1] != w->ne[1]) return "LoRA adapter: " + b.name + " ne[1] does not match " + target + " ne[1]";
+    if (t.ne[1] != b.ne[0]) return "LoRA adapter: " + t.name + " ne[1] and " + b.name + " ne[0] (the rank) differ";
+    if (b.ne[0] > (1u << 16) || w->ne[0] > (1u << 30) || w->ne[1] > (1u << 30))
+      return "LoRA adapter: " + target + " is too large";
+    LoraPair p;
+    p.a = &t;
+    p.b = &b;
+    p.layer = layer;
+    p.r = (int)b.ne[0];
+    p.n_in = (int)w->ne[0];
+    p.n_out = (int)w->ne[1];
+    pairs[target] = p;
+  }
+  return "";
+}
+
+void LoraAdapter::to_f32(const GGUFTensor& t, float* dst) const {
+  uint64_t n = 1;
+  for (uint64_t d : t.ne) n *= d;
+  const uint8_t* src = file.data(t);
+  if (t.type == 0) {
+    memcpy(dst, src, n * 4);
+  } else if (t.type == 1) {
+    for (uint64_t i = 0; i < n; i++) {
+      _Float16 h;
+      memcpy(&h, src + 2 * i, 2);
+      dst[i] = (float)h;
+    }
+  } else {  // BF16
+    for (uint64_t i = 0; i < n; i++) {
+      uint16_t h;
+      memcpy(&h, src + 2 * i, 2);
+      const uint32_t u = (uint32_t)h << 16;
+      memcpy(dst + i, &u, 4);
+    }
+  }
+}
+
 }  // namespace mx

@@ -197,6 +197,11 @@ void launch_synth_q8_rowmajor(uint8_t* dst, int N, int K, uint64_t seed, uint64_
 // n elements (ggml dequantize_row_*, then RNE to bf16); -1 for an unsupported type or ragged n
 int ggml_block_elems(int type);
 int launch_dequant_bf16(uint16_t* dst, const uint8_t* src, int type, size_t n, hipStream_t s);
+// LoRA merge at load (lora.hip), in place on a bf16 row-major matrix w [rows][cols]:
+// w' = bf16_rne(f32(w) + scale * sum_j B[n][j] A[j][k]), the sum and the update in f32 (plain VALU FMAs); A f32
+// [r][cols], B f32 [rows][r], any rows, cols, r >= 1 (16-byte accesses when cols % 8 == 0).  -1: nothing launched.
+int launch_lora_merge(uint16_t* w, const float* A, const float* B, int rows, int cols, int r, float scale,
+                      hipStream_t s);
 void launch_embed_q8(float* x, const uint8_t* tok_embd_blocks, const int* ids, int M, int n_embd, float* ssq,
                      hipStream_t s);
 // RMS_NORM + MUL, quantised to Q8_0 activation rows (xq [M][n], xd [M][n/32])

@@ -1531,6 +1531,55 @@ int mx_kv_pack_probe(int device, int dir, int n_layer, int n_slots, int n_head_k
   return 0;
 }
 
+int mx_lora_merge_probe(int device, int rows, int cols, int r, const uint16_t* w, const float* A, const float* B,
+                        float scale, uint16_t* out, int iters, double* us_per_launch) {
+  if (!w || !A || !B || !out || rows < 1 || rows > 65536 || cols < 1 || cols > 65536 ||
+      (size_t)rows * cols > ((size_t)1 << 28) || r < 1 || r > 4096 || !std::isfinite(scale) || iters < 0 ||
+      (iters > 0 && !us_per_launch))
+    return fail(MX_ERR_ARG, "mx_lora_merge_probe: rows, cols 1..65536, rows * cols <= 2^28, r 1..4096, a finite "
+                            "scale, iters >= 0 with us_per_launch");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const size_t n = (size_t)rows * cols;
+  DevBufs dev;
+  uint16_t* d_w = nullptr;
+  float *d_a = nullptr, *d_b = nullptr;
+  if (!dev.alloc_ff(&d_w, (n + GLUE_GUARD_FLAT) * 2) || !dev.alloc(&d_a, (size_t)r * cols * 4) ||
+      !dev.alloc(&d_b, (size_t)rows * r * 4))
+    return fail(MX_ERR_HIP, "mx_lora_merge_probe: device allocation");
+  HIPC(hipMemcpy(d_w, w, n * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_a, A, (size_t)r * cols * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_b, B, (size_t)rows * r * 4, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  if (launch_lora_merge(d_w, d_a, d_b, rows, cols, r, scale, nullptr))
+    return fail(MX_ERR_ARG, "mx_lora_merge_probe: launch_lora_merge refused");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(out, d_w, (n + GLUE_GUARD_FLAT) * 2, hipMemcpyDeviceToHost));
+  if (iters > 0) {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    hipError_t err = hipEventCreate(&t0);
+    if (err == hipSuccess) err = hipEventCreate(&t1);
+    for (int i = 0; i < 2 && err == hipSuccess; i++) {
+      launch_lora_merge(d_w, d_a, d_b, rows, cols, r, scale, nullptr);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipEventRecord(t0, nullptr);
+    for (int i = 0; i < iters && err == hipSuccess; i++) {
+      launch_lora_merge(d_w, d_a, d_b, rows, cols, r, scale, nullptr);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipEventRecord(t1, nullptr);
+    if (err == hipSuccess) err = hipEventSynchronize(t1);
+    float ms = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+    if (t0) hipEventDestroy(t0);
+    if (t1) hipEventDestroy(t1);
+    if (err != hipSuccess) return fail(MX_ERR_HIP, std::string("mx_lora_merge_probe: ") + hipGetErrorString(err));
+    *us_per_launch = (double)ms * 1e3 / iters;
+  }
+  return 0;
+}
+
 int mx_probe_copy(int device, size_t bytes, int iters, double* gbs, char* desc, int desc_len) {
   return probe_hbm(device, bytes, iters, false, gbs, desc, desc_len);
 }

@@ -40,6 +40,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_sampling_ext_default", "mx_submit_ext", "mx_submit_ext_batch", "mx_sample_probe",
     "mx_sample_plan", "mx_sampler_stats",
     "mx_glue_probe",
+    "mx_engine_create_lora", "mx_lora_check", "mx_engine_lora_info", "mx_lora_merge_probe",
 ]
 # the Q8_0 / Q4_0 kernel probes: names with a digit, listed apart (tests/test_gguf_abi.py checks both lists)
 EXPORTS_Q8 = ["mx_q8_matmul_probe", "mx_q8_matmul_plan", "mx_q8_side_probe"]
@@ -130,6 +131,11 @@ class MxSamplerCounts(ctypes.Structure):
 class MxSharingStats(ctypes.Structure):
     _fields_ = [("shared_prompt_tokens", ctypes.c_uint64), ("copies", ctypes.c_uint64),
                 ("copied_bytes", ctypes.c_uint64), ("follower_requests", ctypes.c_uint64)]
+
+
+class MxLoraInfo(ctypes.Structure):
+    _fields_ = [("n_tensors", ctypes.c_int32), ("rank_max", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("lora_scale", ctypes.c_float)]
 
 
 class MxKvCopy(ctypes.Structure):
@@ -342,6 +348,10 @@ def lib() -> ctypes.CDLL:
         L.mx_sample_plan.argtypes = [P(MxSamplingExt), i32, P(i32)]
         L.mx_sampler_stats.argtypes = [vp, P(MxSamplerCounts)]
         L.mx_sample_probe.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mx_engine_create_lora.argtypes = [ctypes.c_char_p, P(MxOpts), ctypes.c_char_p, ctypes.c_float, P(vp)]
+        L.mx_lora_check.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+        L.mx_engine_lora_info.argtypes = [vp, P(MxLoraInfo)]
+        L.mx_lora_merge_probe.argtypes = [i32, i32, i32, i32, vp, vp, vp, ctypes.c_float, vp, i32, P(ctypes.c_double)]
         for name in EXPORTS + EXPORTS_Q8:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_sampling_ext_default", "mx_last_error",
                             "mx_engine_destroy",
@@ -365,6 +375,43 @@ def device_count() -> int:
 def gguf_check(path: str):
     """Validate a GGUF container (no GPU needed); raises MxError(MX_ERR_MODEL) with the reason."""
     _check(lib().mx_gguf_check(path.encode()))
+
+
+def lora_check(model_path: str, lora_path: str):
+    """Validate a GGUF LoRA adapter against its base model (no GPU needed; include/mx_engine.h mx_lora_check);
+    raises MxError(MX_ERR_MODEL) with the offending tensor or key named."""
+    _check(lib().mx_lora_check(model_path.encode(), lora_path.encode()))
+
+
+LORA_GUARD = 4096  # elements of 0xFF bytes mx_lora_merge_probe returns behind the merged matrix
+
+
+def lora_merge_probe(w, A, B, scale: float, iters: int = 0, rows: Optional[int] = None, cols: Optional[int] = None,
+                     r: Optional[int] = None, out=None, device: int = 0):
+    """The load-time LoRA merge kernel on caller-supplied data (no engine; include/mx_engine.h
+    mx_lora_merge_probe): w bf16 bits (uint16) [rows][cols], A f32 [r][cols], B f32 [rows][r].  Returns (merged
+    bf16 bits [rows][cols], guard [LORA_GUARD] uint16: must be all-ones bits, microseconds per launch or None
+    when iters == 0).  rows / cols / r override what the arrays imply and out (a flat uint16 buffer of rows * cols +
+    LORA_GUARD) is worked on directly: what a test of a refusal passes and reads afterwards."""
+    wa = np.ascontiguousarray(w, dtype=np.uint16)
+    aa = np.ascontiguousarray(A, dtype=np.float32)
+    ba = np.ascontiguousarray(B, dtype=np.float32)
+    rows = wa.shape[0] if rows is None else rows
+    cols = wa.shape[1] if cols is None else cols
+    r = aa.shape[0] if r is None else r
+    n = max(rows, 0) * max(cols, 0)
+    if out is None:
+        if wa.shape != (rows, cols) or aa.shape != (r, cols) or ba.shape != (rows, r):
+            raise ValueError("w [rows][cols], A [r][cols], B [rows][r] expected")
+        ob = np.zeros(n + LORA_GUARD, dtype=np.uint16)
+    else:
+        ob = out
+        if ob.dtype != np.uint16 or ob.ndim != 1 or not ob.flags.c_contiguous or ob.size < wa.size + LORA_GUARD:
+            raise ValueError("out: a flat contiguous uint16 buffer of w.size + LORA_GUARD elements")
+    us = ctypes.c_double(0.0)
+    _check(lib().mx_lora_merge_probe(device, rows, cols, r, wa.ctypes.data, aa.ctypes.data, ba.ctypes.data,
+                                     float(scale), ob.ctypes.data, int(iters), ctypes.byref(us)))
+    return ob[:n].reshape(rows, cols), ob[n:n + LORA_GUARD], (us.value if iters > 0 else None)
 
 
 def probe_copy(device: int = 0, gib: int = 4, iters: int = 10, read_only: bool = False):
@@ -1400,7 +1447,10 @@ class Engine:
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
-                 handoff_bf16: bool = False, prefix_sharing: bool = False, host_cache_bytes: int = 0):
+                 handoff_bf16: bool = False, prefix_sharing: bool = False, host_cache_bytes: int = 0,
+                 lora_path: Optional[str] = None, lora_scale: float = 1.0):
+        """lora_path: a GGUF LoRA adapter merged into the weights while the model loads, scaled by
+        lora_scale * alpha / r; a quantised base is then dequantised to bf16 (info.weight_type 30)."""
         L = lib()
         opts = MxOpts()
         L.mx_opts_default(ctypes.byref(opts))
@@ -1410,7 +1460,11 @@ class Engine:
         opts.handoff_bf16 = int(handoff_bf16)
         self.handoff_bf16 = bool(handoff_bf16)
         h = ctypes.c_void_p()
-        _check(L.mx_engine_create(model_path.encode(), ctypes.byref(opts), ctypes.byref(h)))
+        if lora_path is None:
+            _check(L.mx_engine_create(model_path.encode(), ctypes.byref(opts), ctypes.byref(h)))
+        else:
+            _check(L.mx_engine_create_lora(model_path.encode(), ctypes.byref(opts), os.fsencode(lora_path),
+                                           float(lora_scale), ctypes.byref(h)))
         self._h = h
         info = MxModelInfo()
         _check(L.mx_engine_info(self._h, ctypes.byref(info)))
@@ -1422,6 +1476,13 @@ class Engine:
             self.set_prefix_sharing(True)
         if host_cache_bytes:
             self.set_host_cache(host_cache_bytes)
+
+    def lora_info(self) -> dict:
+        """n_tensors (matrices of this engine's layers the adapter was merged into), rank_max, alpha, lora_scale
+        (include/mx_engine.h mx_lora_info); all 0 for an engine created without an adapter."""
+        st = MxLoraInfo()
+        _check(lib().mx_engine_lora_info(self._h, ctypes.byref(st)))
+        return {k: getattr(st, k) for k, _ in MxLoraInfo._fields_}
 
     def set_host_cache(self, capacity_bytes: int):
         """The host-RAM tier behind the KV slots (off by default): slot records about to be

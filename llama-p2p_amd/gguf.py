@@ -455,7 +455,8 @@ def _mixed_type(wtype: str, name: str) -> int:
 
 def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = None, wtype: str = "bf16",
                          dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None,
-                         pooling_type: int = None, eos_token_id: int = 2, eot_token_id: int = None):
+                         pooling_type: int = None, eos_token_id: int = 2, eot_token_id: int = None,
+                         merge_lora=None):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
     "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
@@ -468,7 +469,9 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     --token-embedding-type).  pooling_type: written as llama.pooling_type (an embedding model's default pooling,
     llama.h enum llama_pooling_type).  eos_token_id: tokenizer.ggml.eos_token_id; eot_token_id: written as
     tokenizer.ggml.eot_token_id when given (the end-of-turn token, which ends a request as EOS does) -- the
-    defaults leave the file as it always was."""
+    defaults leave the file as it always was.  merge_lora: (adapter_path, lora_scale): the matrices the adapter
+    (write_lora_gguf) covers are written already merged (lora_merge_bf16 with scale lora_scale * alpha / r, or
+    lora_scale when alpha is 0), after dequant_from where both are given; only for matrices written as BF16."""
     from . import synth
 
     if wtype not in ("bf16", "q8_0", "q4_0_synth") and wtype not in MIXED:
@@ -508,6 +511,16 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     w.add_bool("tokenizer.ggml.add_bos_token", True)
     arrays = []
     src = GGUFReader(dequant_from) if dequant_from else None
+    lora = read_lora_gguf(merge_lora[0]) if merge_lora is not None else None
+
+    def merged(name, bits):
+        if lora is None or name not in lora[0] or merge_lora[1] == 0:
+            return bits
+        A, B = lora[0][name]
+        return lora_merge_bf16(bits, A, B, lora_effective_scale(merge_lora[1], lora[1], A.shape[0]))
+
+    if lora is not None and wtype != "bf16" and src is None:
+        raise ValueError("merge_lora needs matrices written as BF16 (wtype 'bf16' or dequant_from)")
     for name, kind, arr in synth.synth_tensors(shape, seed):
         if name == "token_embd.weight" and embd_type is not None:
             w.add_tensor_info(name, arr.shape, embd_type)
@@ -518,7 +531,7 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
             info = src.tensors[name]
             y = dequantize(info["type"], src.tensor(name), arr.shape)
             w.add_tensor_info(name, arr.shape, GGML_BF16)
-            arrays.append(synth.f32_to_bf16_bits(y))
+            arrays.append(merged(name, synth.f32_to_bf16_bits(y)))
         elif kind == "bf16" and (wtype == "q8_0" or (wtype == "q4_0_synth" and name.count(".") == 1)):
             w.add_tensor_info(name, arr.shape, GGML_Q8_0)
             arrays.append(synth_q8_0_tensor(arr))
@@ -544,7 +557,7 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
                 arrays.append(random_blocks(t, arr.shape[0], arr.shape[1], rng))
         else:
             w.add_tensor_info(name, arr.shape, GGML_BF16 if kind == "bf16" else GGML_F32)
-            arrays.append(arr)
+            arrays.append(merged(name, arr) if kind == "bf16" else arr)
     if rope_freqs is not None:
         rf = np.ascontiguousarray(rope_freqs, dtype=np.float32)
         assert rf.shape == (shape.head_dim // 2,)
@@ -552,3 +565,67 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
         arrays.append(rf)
     w.write(arrays)
     return path
+
+
+# ---------------------------------------------------------------------------
+# LoRA adapters: the GGUF layout convert_lora_to_gguf.py writes.  For a base tensor T of
+# ne = {n_in, n_out}: T.lora_a, ne = {n_in, r}, row-major A[r][n_in]; T.lora_b, ne = {r, n_out}, row-major
+# B[n_out][r]; W' = W + scale * B A.
+# ---------------------------------------------------------------------------
+def write_lora_gguf(path: str, tensors, alpha: float, dtype: int = GGML_F32):
+    """tensors: {base tensor name: (A[r][n_in], B[n_out][r])}; dtype: GGML_F32, GGML_F16 or GGML_BF16 (the values
+    rounded to it, bf16 by RNE)."""
+    from . import synth
+
+    if dtype not in (GGML_F32, GGML_F16, GGML_BF16):
+        raise ValueError("adapter tensors are F32, F16 or BF16")
+    w = GGUFWriter(path)
+    w.add_string("general.type", "adapter")
+    w.add_string("general.architecture", "llama")
+    w.add_string("adapter.type", "lora")
+    w.add_float32("adapter.lora.alpha", alpha)
+    arrays = []
+    for name, (A, B) in tensors.items():
+        for suffix, m in ((".lora_a", A), (".lora_b", B)):
+            m = np.ascontiguousarray(m, dtype=np.float32)
+            if m.ndim != 2:
+                raise ValueError(f"{name}{suffix}: a 2-D array expected")
+            w.add_tensor_info(name + suffix, m.shape, dtype)
+            arrays.append(m if dtype == GGML_F32 else m.astype(np.float16) if dtype == GGML_F16
+                          else synth.f32_to_bf16_bits(m))
+    w.write(arrays)
+    return path
+
+
+def read_lora_gguf(path: str):
+    """({base tensor name: (A f32 [r][n_in], B f32 [n_out][r])}, alpha) of an adapter file."""
+    r = GGUFReader(path)
+    out = {}
+    for name, info in r.tensors.items():
+        if name.endswith(".lora_a"):
+            base = name[:-7]
+            A = dequantize(info["type"], r.tensor(name), tuple(reversed(info["ne"])))
+            ib = r.tensors[base + ".lora_b"]
+            B = dequantize(ib["type"], r.tensor(base + ".lora_b"), tuple(reversed(ib["ne"])))
+            out[base] = (np.ascontiguousarray(A, dtype=np.float32), np.ascontiguousarray(B, dtype=np.float32))
+    return out, float(r.metadata.get("adapter.lora.alpha", 0.0))
+
+
+def lora_effective_scale(lora_scale: float, alpha: float, r: int) -> np.float32:
+    """llama.cpp's per-tensor scale in f32: lora_scale * alpha / r, or lora_scale alone when alpha is 0."""
+    s, a = np.float32(lora_scale), np.float32(alpha)
+    return np.float32(s * a / np.float32(r)) if a != 0 else s
+
+
+def lora_merge_bf16(w_bits: np.ndarray, A: np.ndarray, B: np.ndarray, scale: float) -> np.ndarray:
+    """The load-time merge in numpy float32: acc = B A in f32, w' = bf16_rne(f32(w) + scale * acc).  w_bits: bf16
+    bits (uint16) [n_out][n_in]; A f32 [r][n_in]; B f32 [n_out][r].  Returns the merged bf16 bits."""
+    from . import synth
+
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    B = np.ascontiguousarray(B, dtype=np.float32)
+    w = synth.bf16_bits_to_f32(np.asarray(w_bits, dtype=np.uint16))
+    if A.ndim != 2 or B.ndim != 2 or B.shape != (w.shape[0], A.shape[0]) or A.shape[1] != w.shape[1]:
+        raise ValueError("w [n_out][n_in], A [r][n_in], B [n_out][r] expected")
+    acc = (B @ A).astype(np.float32)
+    return synth.f32_to_bf16_bits((w + (np.float32(scale) * acc).astype(np.float32)).astype(np.float32))

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 import threading
 import time
 import uuid
@@ -49,9 +50,15 @@ _POOLING_TYPES = (LLAMA_POOLING_TYPE_NONE, LLAMA_POOLING_TYPE_MEAN, LLAMA_POOLIN
 class Llama:
     def __init__(self, model_path: str, *, n_gpu_layers: int = -1, seed: int = LLAMA_DEFAULT_SEED, n_ctx: int = 512,
                  n_batch: int = 512, n_threads: Optional[int] = None, n_threads_batch: Optional[int] = None,
+                 lora_base: Optional[str] = None, lora_scale: float = 1.0, lora_path: Optional[str] = None,
                  verbose: bool = True, n_seq_max: int = 64, device: int = -1, synthetic_seed: int = 0,
                  draft_model: Optional[LlamaDraftModel] = None, embedding: bool = False,
                  pooling_type: int = LLAMA_POOLING_TYPE_UNSPECIFIED, **kwargs: Any):
+        """lora_path: a GGUF LoRA adapter (convert_lora_to_gguf.py), scaled by lora_scale * alpha / r.  It is
+        merged into the weights on the device while the model loads: the model served is the one
+        a BF16 file of the merged weights would give, and a quantised base is dequantised to bf16 for it.
+        lora_base is accepted and ignored: it named an f16 base for llama.cpp's old merge of an adapter into a
+        quantised model, and here the quantised base itself is dequantised."""
         # n_gpu_layers / n_threads are accepted for signature compatibility: the whole model always runs on
         # the GPU.  n_batch only bounds the tokens of one embed() input, as in llama-cpp-python.
         self._check_pooling_type(pooling_type)
@@ -65,14 +72,51 @@ class Llama:
         syn = _synth.parse_synthetic_path(model_path)
         if syn is None and not os.path.exists(model_path):
             raise ValueError(f"Model path does not exist: {model_path}")
-        self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
-                                      seed=synthetic_seed)
+        self.lora_base = lora_base
+        self.lora_scale = lora_scale
+        self.lora_path = lora_path
+        if lora_path:
+            try:
+                self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
+                                              seed=synthetic_seed, lora_path=lora_path, lora_scale=lora_scale)
+            except _engine.MxError as err:
+                if err.code not in (_engine.MX_ERR_MODEL, _engine.MX_ERR_ARG):
+                    raise
+                raise RuntimeError(f"Failed to initialize LoRA adapter from lora path: {lora_path}") from err
+            if verbose:
+                self._print_lora_line(model_path)
+        else:
+            self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
+                                          seed=synthetic_seed)
         self._n_ctx = n_ctx
         self.cache = None
         self.n_batch = min(n_batch, n_ctx)
         self._embedding = bool(embedding)
         self._init_tokenizer(model_path, self._engine.info.n_vocab)
         self._pooling_type = self._resolve_pooling_type(pooling_type)
+
+    def _print_lora_line(self, model_path: str):
+        """One line on stderr: how many tensors the adapter was merged into and, for a quantised base, that the
+        model now runs as bf16 and what that costs."""
+        from .gguf import BLOCKS, GGML_BF16, GGUFReader, type_nbytes
+
+        li = self._engine.lora_info()
+        line = (f"llama_lora: merged {li['n_tensors']} tensors from {self.lora_path} (rank <= {li['rank_max']}, "
+                f"alpha {li['alpha']:g}, scale {li['lora_scale']:g})")
+        file_bytes = bf16_bytes = 0
+        quantised = False
+        for info in GGUFReader(model_path).tensors.values():
+            n = 1
+            for d in info["ne"]:
+                n *= int(d)
+            file_bytes += type_nbytes(info["type"], n)
+            matrix = len(info["ne"]) == 2
+            bf16_bytes += type_nbytes(GGML_BF16 if matrix else info["type"], n)
+            quantised |= matrix and info["type"] in BLOCKS
+        if quantised:
+            line += (f"; the quantised base is dequantised: the model runs as bf16, {bf16_bytes} bytes of weights "
+                     f"instead of {file_bytes}")
+        print(line, file=sys.stderr)
 
     @staticmethod
     def _check_pooling_type(pooling_type: int):
