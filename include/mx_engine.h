@@ -796,6 +796,59 @@ int mx_engine_stats(mx_engine* e, mx_stats* out);
 /* Number of visible HIP devices (serving: one engine replica per GPU). */
 int mx_device_count(int32_t* n);
 
+/* Grammar-constrained sampling (llama-cpp-python's create_completion(grammar=LlamaGrammar)).
+ * The matcher runs on the host; a request's allowed tokens reach the device as a bit mask, and a kernel sets the
+ * logit of every other token to -inf before the request's sampler reads the row.
+ *
+ * mx_vocab: what a grammar is matched against -- the piece bytes of the n_vocab tokens (token t: blob[offsets[t],
+ * offsets[t + 1]), offsets[0] == 0, at most 4096 bytes each; an empty piece is never allowed) and the
+ * end-of-generation ids (allowed exactly where the grammar may end).  Copied; MX_ERR_ARG for anything malformed.
+ * mx_grammar: a compiled GBNF grammar over one vocabulary, immutable and shared by any number of requests and
+ * states.  Syntax errors, undefined rules, a missing root, {m,n} with n < m and left-recursive rules are MX_ERR_ARG
+ * with the rule or position in mx_last_error().  cache_entries: masks kept per grammar, least recently used out
+ * first (< 0: the default of 256; 0: none).  Both handles are reference-counted: destroying one while a grammar,
+ * a state or a request still uses it is safe.  No GPU touched. */
+typedef struct mx_vocab mx_vocab;
+typedef struct mx_grammar mx_grammar;
+typedef struct mx_grammar_state mx_grammar_state;
+int mx_vocab_create(int n_vocab, const uint8_t* blob, const uint64_t* offsets, const int32_t* eog_ids, int n_eog,
+                    mx_vocab** out);
+void mx_vocab_destroy(mx_vocab* v);
+int mx_grammar_create(const mx_vocab* v, const char* gbnf, int cache_entries, mx_grammar** out);
+void mx_grammar_destroy(mx_grammar* g);
+/* A state outside any engine (what a request holds; CPU probing): starts at root.  mask: the allowed tokens as
+ * n_words = ceil(n_vocab / 32) words, bit t & 31 of word t >> 5; *status MX_GRAMMAR_OK, MX_GRAMMAR_DEAD_END (no
+ * token is allowed) or MX_GRAMMAR_CAP (more than 4096 simultaneous grammar positions), the words all zero for the
+ * last two.  accept: MX_ERR_ARG when the token is not allowed (the state is unchanged).  may_end: the grammar can
+ * end here (and no UTF-8 sequence is open). */
+#define MX_GRAMMAR_OK 0
+#define MX_GRAMMAR_DEAD_END 1
+#define MX_GRAMMAR_CAP 2
+int mx_grammar_state_create(const mx_grammar* g, mx_grammar_state** out);
+int mx_grammar_state_mask(mx_grammar_state* s, uint32_t* words, int n_words, int32_t* status);
+int mx_grammar_state_accept(mx_grammar_state* s, int32_t token);
+int mx_grammar_state_may_end(const mx_grammar_state* s, int32_t* may_end);
+void mx_grammar_state_destroy(mx_grammar_state* s);
+/* mask lookups of the grammar served from its cache / computed by a walk of the vocabulary, and the masks held */
+int mx_grammar_cache_stats(const mx_grammar* g, uint64_t* hits, uint64_t* misses, uint64_t* entries);
+/* As mx_submit_ext (s NULL: the defaults) with a grammar.  Generated tokens advance it from root (prompt tokens do
+ * not); every pick -- argmax, chain, wide, Mirostat, host sampler -- runs on the masked row; log-probabilities
+ * stay those of the raw row.  An end-of-generation token ends the request with MX_FINISH_STOP.  A step at which no
+ * token is allowed, or whose state is over the position cap, ends it with MX_FINISH_ERROR (mx_wait: MX_ERR_STATE)
+ * and leaves the other requests alone.  A round with a grammar row runs one step; such a request never
+ * speculates.  MX_ERR_ARG when the grammar's vocabulary is not of the engine's size, MX_ERR_STATE on a
+ * pipeline-stage engine. */
+int mx_submit_grammar(mx_engine* e, const int32_t* ids, int n, const mx_sampling_ext* s, int max_tokens,
+                      int n_logprobs, int prompt_logprobs, const mx_grammar* grammar, uint64_t* req);
+/* The mask kernel on caller-supplied rows, no engine: logits_host [n][ldl] f32 with V <= ldl valid columns,
+ * n <= 64; masks [n][ceil(V / 32)]; on [n] (0: the row is left alone).  out [n][ldl]: where(on && bit clear,
+ * -inf, x) in columns < V, columns >= V bit-identical.  Anything else: MX_ERR_ARG, nothing launched. */
+int mx_grammar_mask_probe(int device, const float* logits_host, int n, int V, int ldl, const uint32_t* masks,
+                          const uint32_t* on, float* out);
+/* The same launch timed: masks [n][ceil(V / 32)] on resident buffers (rows of zeros, every row on), 3 warm-up
+ * launches, then `iters` launches between two HIP events; *us_per_launch their mean.  Benchmark support. */
+int mx_grammar_mask_time(int device, int n, int V, int ldl, const uint32_t* masks, int iters, double* us_per_launch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,8 +18,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MX_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = [("kernels.hip", "hip"), ("kquant.hip", "hip"), ("kvpack.hip", "hip"), ("lora.hip", "hip"),
-           ("engine.cpp", "hip"),
-           ("probes.cpp", "hip"), ("gguf.cpp", "c++")]
+           ("grammar.hip", "hip"), ("engine.cpp", "hip"),
+           ("probes.cpp", "hip"), ("gguf.cpp", "c++"), ("grammar.cpp", "c++")]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-result", "-Wno-unused-value"]
 # gfx950's packed-FP32 VALU instructions (v_pk_{fma,mul,add}_f32, v_pk_mov_b32) are switched off for the

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "engine_shared.h"
+#include "grammar.h"
 #include "gguf.h"
 
 using namespace mx;
@@ -224,6 +225,12 @@ struct Request {
   bool has_ext = false;
   SampExt ext{};
   float mu = 0.f;
+  // grammar (mx_submit_grammar): the request's place in its grammar, the mask of the step about to
+  // be picked, and how the grammar ended the request during a prefill (0: it did not; MX_FINISH_STOP + 1 /
+  // MX_FINISH_ERROR + 1, applied by the scheduler loop once the slot's record is written)
+  std::unique_ptr<gram::State> gram;
+  std::shared_ptr<const std::vector<uint32_t>> gram_mask;
+  int gram_end = 0;
   // one entry [tok_lp | kr top log-probs | kr top ids as int bits] of a round that ran with kr >= lp_k
   void lp_append(const float* entry, int kr) {
     lp_tok.push_back(entry[0]);
@@ -384,6 +391,59 @@ struct mx_engine {
   float *d_bias_raw = nullptr, *d_mu = nullptr, *d_mu_hist = nullptr, *miro_wf = nullptr;
   double* miro_wd = nullptr;
   int* miro_wi = nullptr;
+  // grammar masks: pick_gram set when some row of the run has a grammar -- the mask kernel then
+  // runs between the log-prob statistics and the pick.  d_gmask [MAX_ROWS][gmask_words], d_gon [MAX_ROWS] and
+  // their pinned mirror h_gmask ([MAX_ROWS][gmask_words] then the on words) come with the first grammar request
+  bool pick_gram = false;
+  bool gram_refused = false;  // launch_grammar_mask refused a launch of pick(): the step's tokens are not kept
+  uint32_t *d_gmask = nullptr, *d_gon = nullptr, *h_gmask = nullptr;
+  int gmask_words = 0;
+  // the mask of the step a grammar request is about to take (from its state, or its grammar's cache); false with
+  // its error text set: no token is allowed, or the state is over the position cap
+  static bool gram_step_mask(Request* r) {
+    const int st = r->gram->mask(&r->gram_mask);
+    if (st == gram::STATE_OK) return true;
+    r->error = st == gram::STATE_CAP
+                   ? "grammar: more than " + std::to_string(gram::MAX_POSITIONS) + " simultaneous positions, or a mask past "
+                         "the work budget"
+                   : "grammar: dead end, no token of the vocabulary is allowed after " + std::to_string(r->out.size()) +
+                         " generated tokens";
+    return false;
+  }
+  static bool gram_row(const Request* r) { return r->gram && !r->gram_end && r->gram_mask; }
+  // on words of rows[0..n) and the masks of its grammar rows (those only) to the device; 1 when there is one
+  // (pick_gram set), 0 when none (nothing copied), < 0 on an error
+  int upload_gram(Request* const* rows, int n, hipStream_t s) {
+    pick_gram = false;
+    bool any = false;
+    for (int i = 0; i < n; i++) any |= gram_row(rows[i]);
+    if (!any) return 0;
+    const int nw = (n_vocab + 31) / 32;
+    // each buffer once: what a failed attempt did allocate is kept for the next one
+    if (!d_gmask && alloc((void**)&d_gmask, (size_t)MAX_ROWS * nw * 4)) return d_gmask = nullptr, -1;
+    if (!d_gon && alloc((void**)&d_gon, (size_t)MAX_ROWS * 4)) return d_gon = nullptr, -1;
+    if (!h_gmask && hipHostMalloc((void**)&h_gmask, ((size_t)MAX_ROWS * nw + MAX_ROWS) * 4) != hipSuccess)
+      return h_gmask = nullptr, -1;
+    gmask_words = nw;
+    uint32_t* h_on = h_gmask + (size_t)MAX_ROWS * nw;
+    for (int i = 0; i < n; i++) {
+      h_on[i] = gram_row(rows[i]) ? 1u : 0u;
+      if (!h_on[i]) continue;
+      memcpy(h_gmask + (size_t)i * nw, rows[i]->gram_mask->data(), (size_t)nw * 4);
+      if (hipMemcpyAsync(d_gmask + (size_t)i * nw, h_gmask + (size_t)i * nw, (size_t)nw * 4, hipMemcpyHostToDevice, s) !=
+          hipSuccess)
+        return -1;
+    }
+    if (hipMemcpyAsync(d_gon, h_on, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    pick_gram = true;
+    return 1;
+  }
+  // the same mask on a host copy of a row (host-sampled rounds)
+  void gram_mask_host(const Request* r, float* x) const {
+    const std::vector<uint32_t>& w = *r->gram_mask;
+    for (int t = 0; t < n_vocab; t++)
+      if (!((w[t >> 5] >> (t & 31)) & 1u)) x[t] = -INFINITY;
+  }
   std::vector<SampExt> h_sext;  // host staging of upload_ext
   std::vector<float> h_mu;
   // SampExt rows and mu of a run over rows[0..n) to the device and pick_ext / pick_miro / pick_wide set; returns
@@ -433,6 +493,7 @@ struct mx_engine {
     if (lp)
       launch_logprob_stats(logits, n_vocab, n_out, n_vocab, pick_lp, tk_ws_val, tk_ws_idx, lp_part, lp_ms, lp_top,
                            lp_idx, s);
+    if (pick_gram && launch_grammar_mask(logits, n_vocab, n_out, n_vocab, d_gmask, d_gon, s)) gram_refused = true;
     if (pick_samp)
       launch_sample_chain(logits, n_vocab, n_out, n_vocab, pick_samp, pick_k, tk_ws_val, tk_ws_idx, tk_val, tk_idx,
                           d_tok, ids_next, pos_next, hist, hist_stride, hist_count, max_hist, s,
@@ -620,6 +681,7 @@ mx_engine::~mx_engine() {
   while (!host_entries.empty()) host_drop(host_entries.size() - 1);
   host_free_trash();
   if (h_pack_tab) hipHostFree(h_pack_tab);
+  if (h_gmask) hipHostFree(h_gmask);
   if (ev_packed) hipEventDestroy(ev_packed);
   if (ev_stage_free) hipEventDestroy(ev_stage_free);
   if (stream2) hipStreamDestroy(stream2);
@@ -2379,6 +2441,10 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
   // every sampling request fits the device chain: first tokens are drawn on the device (the same
   // samp_pick and counter-based draw 0 as the host sampler), no logits rows cross PCIe
   dev_pick &= any_sampling;
+  // grammar requests: the first token goes through the mask of the initial state; one that has
+  // no first token is evaluated like the others, gets none and ends with its error after the prefill
+  for (Request* r : reqs)
+    if (r->gram && !gram_step_mask(r)) r->gram_end = MX_FINISH_ERROR + 1;
   std::vector<float> lg;
   std::vector<SampRow> sr;
   size_t q0 = 0;  // first request whose last row is not yet evaluated
@@ -2409,8 +2475,9 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
     pick_lp = lpk;
     struct ResetLp {
       mx_engine* e;
-      ~ResetLp() { e->pick_lp = -1; }
+      ~ResetLp() { e->pick_lp = -1, e->pick_gram = false; }
     } reset_lp{this};
+    if (n_out && upload_gram(reqs.data() + q0, n_out, st) < 0) return fail(MX_ERR_HIP, "grammar mask copy");
     if (n_out && dev_pick) {
       sr.resize(n_out);
       for (int k = 0; k < n_out; k++) {
@@ -2435,7 +2502,7 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       }
       HIPC(hipMemcpyAsync(tok.data() + q0, d_tok, n_out * 4, hipMemcpyDeviceToHost, st));
     } else if (n_out) {
-      if (lpk >= 0)
+      if (lpk >= 0 || pick_gram)
         pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);  // pick_samp is null: argmax
       else
         launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, nullptr, nullptr, nullptr, 0, nullptr,
@@ -2445,6 +2512,11 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
         lg.resize((size_t)n_out * n_vocab);
         HIPC(hipMemcpyAsync(lg.data(), logits, lg.size() * 4, hipMemcpyDeviceToHost, st));
       }
+    }
+    if (gram_refused) {
+      gram_refused = false;
+      hipStreamSynchronize(st);
+      return fail(MX_ERR_ARG, "grammar mask launch shape");
     }
     const size_t lps = (size_t)SCHED_KMAX * (1 + 2 * std::max(lpk, 0));  // floats per row of lp_hist
     std::vector<float> lph, lpms;
@@ -2458,8 +2530,10 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
     std::lock_guard<std::mutex> lk(mu);
     for (int k = 0; k < n_out; k++) {
       Request* r = reqs[q0 + k];
+      if (r->gram_end) continue;  // no first token: a grammar at a dead end from the start
       int32_t t = tok[q0 + k];
       const bool host_pick = !dev_pick && needs_chain(r);
+      if (host_pick && r->gram) gram_mask_host(r, lg.data() + (size_t)k * n_vocab);
       if (host_pick) t = sample_host(r, lg.data() + (size_t)k * n_vocab);
       else if (int kw = 0; dev_pick && needs_chain(r) && req_path(r, n_vocab, &kw) == MX_PICK_WIDE) stat_wide_rows++;
       if (!mu_new.empty() && r->has_ext && r->ext.miro == 2) r->mu = mu_new[k];
@@ -2470,6 +2544,14 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
         // host-sampled: the same formula over the raw logit of the copied row
         if (host_pick) ent[0] = (lg[(size_t)k * n_vocab + t] - lpms[2 * k]) - lpms[2 * k + 1];
         r->lp_append(ent, lpk);
+      }
+      if (r->gram) {
+        if (!r->gram->accept(t)) {
+          r->error = "grammar: the picked token " + std::to_string(t) + " is not allowed";
+          r->gram_end = MX_FINISH_ERROR + 1;
+        } else if (r->gram->ended()) {
+          r->gram_end = MX_FINISH_STOP + 1;
+        }
       }
     }
     q0 = q1;
@@ -2650,7 +2732,7 @@ int mx_engine::prefill_embed(std::vector<Request*>& reqs) {
 // log-probabilities, on a whole bf16 model -- the path whose rows are bitwise independent of the row count.
 bool mx_engine::spec_eligible(const Request* r) const {
   return r->spec_d > 0 && spec_ctx && r->samp.temperature <= 0.f && !has_penalties(r->samp) && r->lp_k < 0 &&
-         !r->has_ext &&
+         !r->has_ext && !r->gram &&
          !embd_q8 && !out_q8 && !embd_kq_type && !out_kq_head;
 }
 
@@ -2784,6 +2866,21 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
 // order (a row that finishes early ignores the rest).  Otherwise one step, with the sampler chain
 // on the host (top-k candidates from the device when possible).
 int mx_engine::sched_step(std::vector<Request*>& rows) {
+  // grammar rows: the mask of this step, on the host, before anything is enqueued; a row at a dead
+  // end leaves the round with an error and the others run as if it had never been there
+  bool any_gram = false;
+  for (size_t i = 0; i < rows.size();) {
+    Request* r = rows[i];
+    if (r->gram && !gram_step_mask(r)) {
+      std::lock_guard<std::mutex> lk(mu);
+      finish(r, MX_FINISH_ERROR);
+      rows.erase(rows.begin() + i);
+      continue;
+    }
+    any_gram |= r->gram != nullptr;
+    i++;
+  }
+  if (rows.empty()) return 0;
   if (const int sp = sched_step_spec(rows)) return sp < 0 ? sp : 0;
   const int M = (int)rows.size();
   std::vector<int32_t> ids(M), pos(M), slots(M);
@@ -2812,6 +2909,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     std::lock_guard<std::mutex> lk(mu);
     if (!pending.empty() && !free_slots.empty()) K = 1;  // admit waiting requests at the next round
   }
+  if (any_gram) K = 1;  // the next mask depends on the token this step picks
   hipStream_t s = stream;
   HIPC(hipMemcpyAsync(d_ids, ids.data(), M * 4, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(d_pos, pos.data(), M * 4, hipMemcpyHostToDevice, s));
@@ -2827,12 +2925,15 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
     mx_engine* e;
     ~Reset() {
       e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1;
-      e->pick_ext = nullptr; e->pick_miro = false; e->pick_wide = false;
+      e->pick_ext = nullptr; e->pick_miro = false; e->pick_wide = false; e->pick_gram = false;
     }
   } reset_flags{this};
   // rows with the extended settings: their SampExt and mu beside the SampRows; the level joins the graph key
   const int xl = dev_chain ? upload_ext(rows.data(), M, s) : 0;
   if (xl < 0) return fail(MX_ERR_HIP, "sampler settings copy");
+  // grammar rows: their masks beside them; one more level bit of the graph key
+  const int gl = any_gram ? upload_gram(rows.data(), M, s) : 0;
+  if (gl < 0) return fail(MX_ERR_HIP, "grammar mask copy");
   rows_distinct = true;  // one row per active request, each its own slot
   pick_samp = dev_chain ? d_samp : nullptr;
   pick_k = dev_chain ? ktop : 0;
@@ -2844,7 +2945,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;  // per-round timing on stderr
   const auto t0 = std::chrono::steady_clock::now();
   bool captured = false;
-  const std::tuple<int, int, int, int> gkey(M, pick_k, pick_lp, xl);
+  const std::tuple<int, int, int, int> gkey(M, pick_k, pick_lp, xl | (gl ? 8 : 0));
   auto it = sched_graphs.find(gkey);
   if (use_graphs && it == sched_graphs.end()) {
     captured = true;
@@ -2862,6 +2963,11 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   for (int k = 0; k < K; k++) {
     if (use_graphs) HIPC(hipGraphLaunch(it->second, s));
     else if (int rc = step()) return rc;
+  }
+  if (gram_refused) {
+    gram_refused = false;
+    hipStreamSynchronize(s);
+    return fail(MX_ERR_ARG, "grammar mask launch shape");
   }
   std::vector<int32_t> hist((size_t)M * SCHED_KMAX);
   std::vector<float> lg, tkv;
@@ -2935,6 +3041,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
           for (size_t j = 0; j < c.size(); j++)
             if (tki[(size_t)i * TK + j] == t) raw = tkv[(size_t)i * TK + j];
         } else {
+          if (r->gram) gram_mask_host(r, lg.data() + (size_t)i * n_vocab);
           t = sample_host(r, lg.data() + (size_t)i * n_vocab);
           raw = lg[(size_t)i * n_vocab + t];
         }
@@ -2946,6 +3053,15 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
         if (host_pick) ent[0] = (raw - lpms[2 * i]) - lpms[2 * i + 1];
         r->lp_append(ent, lpk);
       }
+      if (r->gram) {  // the token moves the grammar on; an end-of-generation token ends it and the request
+        if (!r->gram->accept(t)) {
+          r->error = "grammar: the picked token " + std::to_string(t) + " is not allowed";
+          finish(r, MX_FINISH_ERROR);
+        } else if (r->gram->ended()) {
+          finish(r, MX_FINISH_STOP);
+        }
+      }
+      if (r->done) continue;
       if ((is_eog(t) && !r->samp.ignore_eos) || r->cancel) finish(r, MX_FINISH_STOP);
       else if ((int)r->out.size() >= r->max_tokens || r->pos >= n_ctx) finish(r, MX_FINISH_LENGTH);
     }
@@ -3131,6 +3247,10 @@ void mx_engine::scheduler_loop() {
         slot_tokens[r->slot] = r->prompt;
         if (r->embd) {  // no tokens: its vectors are in embd_out, the slot keeps the prompt's K/V
           finish(r, MX_FINISH_STOP);
+          continue;
+        }
+        if (r->gram_end) {  // the grammar ended it in the prefill: a dead end, or its first token ends the grammar
+          finish(r, r->gram_end - 1);
           continue;
         }
         const int32_t t = r->out.back();
@@ -3605,6 +3725,104 @@ int mx_submit_ext_batch(mx_engine* e, int n_req, const int32_t* const* ids, cons
     rs[i]->mu = 2.0f * s[i].mirostat_tau;
   }
   return enqueue_requests(e, rs.data(), n_req, reqs);
+}
+
+// ---- grammar.  The handles hold shared pointers: a grammar keeps its vocabulary alive, a state
+// and a request their grammar.
+struct mx_vocab {
+  std::shared_ptr<const gram::Vocab> p;
+};
+struct mx_grammar {
+  std::shared_ptr<gram::Grammar> p;
+};
+struct mx_grammar_state {
+  gram::State s;
+};
+constexpr int GRAMMAR_CACHE_DEFAULT = 256;
+
+int mx_vocab_create(int n_vocab, const uint8_t* blob, const uint64_t* offsets, const int32_t* eog_ids, int n_eog,
+                    mx_vocab** out) {
+  if (!out) return fail(MX_ERR_ARG, "mx_vocab_create: null out");
+  std::shared_ptr<const gram::Vocab> v;
+  const std::string err = gram::Vocab::create(n_vocab, blob, offsets, eog_ids, n_eog, &v);
+  if (!err.empty()) return fail(MX_ERR_ARG, "mx_vocab_create: " + err);
+  *out = new mx_vocab{std::move(v)};
+  return 0;
+}
+
+void mx_vocab_destroy(mx_vocab* v) { delete v; }
+
+int mx_grammar_create(const mx_vocab* v, const char* gbnf, int cache_entries, mx_grammar** out) {
+  if (!v || !gbnf || !out) return fail(MX_ERR_ARG, "mx_grammar_create: null argument");
+  std::shared_ptr<gram::Grammar> g;
+  const std::string err =
+      gram::Grammar::create(v->p, gbnf, cache_entries < 0 ? GRAMMAR_CACHE_DEFAULT : cache_entries, &g);
+  if (!err.empty()) return fail(MX_ERR_ARG, err);
+  *out = new mx_grammar{std::move(g)};
+  return 0;
+}
+
+void mx_grammar_destroy(mx_grammar* g) { delete g; }
+
+int mx_grammar_state_create(const mx_grammar* g, mx_grammar_state** out) {
+  if (!g || !out) return fail(MX_ERR_ARG, "mx_grammar_state_create: null argument");
+  *out = new mx_grammar_state{gram::State(g->p)};
+  return 0;
+}
+
+int mx_grammar_state_mask(mx_grammar_state* s, uint32_t* words, int n_words, int32_t* status) {
+  if (!s || !words || !status) return fail(MX_ERR_ARG, "mx_grammar_state_mask: null argument");
+  const int nw = (s->s.grammar()->vocab->n_vocab + 31) / 32;
+  if (n_words != nw) return fail(MX_ERR_ARG, "mx_grammar_state_mask: n_words must be " + std::to_string(nw));
+  std::shared_ptr<const std::vector<uint32_t>> m;
+  *status = s->s.mask(&m);
+  memcpy(words, m->data(), (size_t)nw * 4);
+  return 0;
+}
+
+int mx_grammar_state_accept(mx_grammar_state* s, int32_t token) {
+  if (!s) return fail(MX_ERR_ARG, "mx_grammar_state_accept: null state");
+  if (!s->s.accept(token)) return fail(MX_ERR_ARG, "grammar: token " + std::to_string(token) + " is not allowed here");
+  return 0;
+}
+
+int mx_grammar_state_may_end(const mx_grammar_state* s, int32_t* may_end) {
+  if (!s || !may_end) return fail(MX_ERR_ARG, "mx_grammar_state_may_end: null argument");
+  *may_end = s->s.may_end() ? 1 : 0;
+  return 0;
+}
+
+void mx_grammar_state_destroy(mx_grammar_state* s) { delete s; }
+
+int mx_grammar_cache_stats(const mx_grammar* g, uint64_t* hits, uint64_t* misses, uint64_t* entries) {
+  if (!g) return fail(MX_ERR_ARG, "mx_grammar_cache_stats: null grammar");
+  g->p->stats(hits, misses, entries);
+  return 0;
+}
+
+int mx_submit_grammar(mx_engine* e, const int32_t* ids, int n, const mx_sampling_ext* s, int max_tokens,
+                      int n_logprobs, int prompt_logprobs, const mx_grammar* grammar, uint64_t* req) {
+  if (!e || !ids || n < 1 || !req || !grammar) return fail(MX_ERR_ARG, "bad arguments");
+  if (n_logprobs < -1 || n_logprobs > TOPK_MAX) return fail(MX_ERR_ARG, "mx_submit_grammar: n_logprobs must be -1..64");
+  if (n_logprobs < 0 && prompt_logprobs)
+    return fail(MX_ERR_ARG, "mx_submit_grammar: prompt_logprobs needs n_logprobs >= 0");
+  if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "mx_submit needs a full-model engine");
+  if (grammar->p->vocab->n_vocab != e->n_vocab)
+    return fail(MX_ERR_ARG, "mx_submit_grammar: the grammar's vocabulary has " +
+                                std::to_string(grammar->p->vocab->n_vocab) + " tokens, the model " +
+                                std::to_string(e->n_vocab));
+  mx_sampling_ext dflt;
+  if (!s) mx_sampling_ext_default(&dflt), s = &dflt;
+  std::unique_ptr<Request> r;
+  if (int rc = make_request(e, ids, n, &s->base, max_tokens, &r)) return rc;
+  if (int rc = check_sampling_ext(s, e->n_vocab, &r->ext, &r->has_ext)) return rc;
+  r->mu = 2.0f * s->mirostat_tau;
+  if (n_logprobs >= 0) {
+    r->lp_k = std::min(n_logprobs, e->n_vocab);
+    r->lp_prompt = prompt_logprobs != 0;
+  }
+  r->gram = std::make_unique<gram::State>(grammar->p);
+  return enqueue_requests(e, &r, 1, req);
 }
 
 int mx_submit_spec(mx_engine* e, const int32_t* ids, int n, const mx_sampling* s, int max_tokens, int num_pred_tokens,

@@ -202,6 +202,11 @@ int launch_dequant_bf16(uint16_t* dst, const uint8_t* src, int type, size_t n, h
 // [r][cols], B f32 [rows][r], any rows, cols, r >= 1 (16-byte accesses when cols % 8 == 0).  -1: nothing launched.
 int launch_lora_merge(uint16_t* w, const float* A, const float* B, int rows, int cols, int r, float scale,
                       hipStream_t s);
+// Grammar mask (grammar.hip) on logits [M][ldl] with V valid columns: row i with on[i] != 0 gets
+// -inf in every column t < V whose bit (masks[i][t >> 5] >> (t & 31)) & 1 is clear; nothing else is written and
+// the rows are never read.  masks [M][ceil(V / 32)].  M 1..MAX_ROWS, ldl >= V.  -1: nothing launched.
+int launch_grammar_mask(float* logits, int ldl, int M, int V, const uint32_t* masks, const uint32_t* on,
+                        hipStream_t s);
 void launch_embed_q8(float* x, const uint8_t* tok_embd_blocks, const int* ids, int M, int n_embd, float* ssq,
                      hipStream_t s);
 // RMS_NORM + MUL, quantised to Q8_0 activation rows (xq [M][n], xd [M][n/32])

@@ -1580,6 +1580,69 @@ int mx_lora_merge_probe(int device, int rows, int cols, int r, const uint16_t* w
   return 0;
 }
 
+int mx_grammar_mask_probe(int device, const float* logits_host, int n, int V, int ldl, const uint32_t* masks,
+                          const uint32_t* on, float* out) {
+  if (!logits_host || !masks || !on || !out || n < 1 || n > MAX_ROWS || V < 1 || V > (1 << 20) || ldl < V ||
+      ldl > (1 << 20) + 64)
+    return fail(MX_ERR_ARG, "mx_grammar_mask_probe: 1 <= n <= 64 rows, 1 <= V <= 2^20, V <= ldl <= 2^20 + 64, masks, on and out");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const size_t elems = (size_t)n * ldl, nw = ((size_t)V + 31) / 32;
+  DevBufs dev;
+  float* d_l = nullptr;
+  uint32_t *d_m = nullptr, *d_on = nullptr;
+  if (!dev.alloc(&d_l, elems * 4) || !dev.alloc(&d_m, (size_t)n * nw * 4) || !dev.alloc(&d_on, (size_t)n * 4))
+    return fail(MX_ERR_HIP, "mx_grammar_mask_probe: device allocation");
+  HIPC(hipMemcpy(d_l, logits_host, elems * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_m, masks, (size_t)n * nw * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_on, on, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  if (launch_grammar_mask(d_l, ldl, n, V, d_m, d_on, nullptr))
+    return fail(MX_ERR_ARG, "mx_grammar_mask_probe: launch_grammar_mask refused");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(out, d_l, elems * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mx_grammar_mask_time(int device, int n, int V, int ldl, const uint32_t* masks, int iters, double* us_per_launch) {
+  if (!masks || !us_per_launch || n < 1 || n > MAX_ROWS || V < 1 || V > (1 << 20) || ldl < V || ldl > (1 << 20) + 64 ||
+      iters < 1 || iters > 100000)
+    return fail(MX_ERR_ARG, "mx_grammar_mask_time: 1 <= n <= 64 rows, 1 <= V <= 2^20, V <= ldl <= 2^20 + 64, masks, "
+                            "1 <= iters <= 100000 and us_per_launch");
+  if (device >= 0) HIPC(hipSetDevice(device));
+  const size_t elems = (size_t)n * ldl, nw = ((size_t)V + 31) / 32;
+  DevBufs dev;
+  float* d_l = nullptr;
+  uint32_t *d_m = nullptr, *d_on = nullptr;
+  if (!dev.alloc(&d_l, elems * 4) || !dev.alloc(&d_m, (size_t)n * nw * 4) || !dev.alloc(&d_on, (size_t)n * 4))
+    return fail(MX_ERR_HIP, "mx_grammar_mask_time: device allocation");
+  HIPC(hipMemset(d_l, 0, elems * 4));
+  HIPC(hipMemset(d_on, 1, (size_t)n * 4));  // every row on
+  HIPC(hipMemcpy(d_m, masks, (size_t)n * nw * 4, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  hipError_t err = hipEventCreate(&t0);
+  if (err == hipSuccess) err = hipEventCreate(&t1);
+  for (int i = 0; i < 3 && err == hipSuccess; i++) {
+    if (launch_grammar_mask(d_l, ldl, n, V, d_m, d_on, nullptr)) err = hipErrorInvalidValue;
+    else err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipEventRecord(t0, nullptr);
+  for (int i = 0; i < iters && err == hipSuccess; i++) {
+    launch_grammar_mask(d_l, ldl, n, V, d_m, d_on, nullptr);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipEventRecord(t1, nullptr);
+  if (err == hipSuccess) err = hipEventSynchronize(t1);
+  float ms = 0.f;
+  if (err == hipSuccess) err = hipEventElapsedTime(&ms, t0, t1);
+  if (t0) hipEventDestroy(t0);
+  if (t1) hipEventDestroy(t1);
+  if (err != hipSuccess) return fail(MX_ERR_HIP, std::string("mx_grammar_mask_time: ") + hipGetErrorString(err));
+  *us_per_launch = (double)ms * 1e3 / iters;
+  return 0;
+}
+
 int mx_probe_copy(int device, size_t bytes, int iters, double* gbs, char* desc, int desc_len) {
   return probe_hbm(device, bytes, iters, false, gbs, desc, desc_len);
 }

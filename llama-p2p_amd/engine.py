@@ -41,6 +41,10 @@ EXPORTS = EXPORTS_KQ + [
     "mx_sample_plan", "mx_sampler_stats",
     "mx_glue_probe",
     "mx_engine_create_lora", "mx_lora_check", "mx_engine_lora_info", "mx_lora_merge_probe",
+    "mx_vocab_create", "mx_vocab_destroy", "mx_grammar_create", "mx_grammar_destroy", "mx_grammar_state_create",
+    "mx_grammar_state_mask", "mx_grammar_state_accept", "mx_grammar_state_may_end", "mx_grammar_state_destroy",
+    "mx_grammar_cache_stats", "mx_submit_grammar", "mx_grammar_mask_probe",
+    "mx_grammar_mask_time",
 ]
 # the Q8_0 / Q4_0 kernel probes: names with a digit, listed apart (tests/test_gguf_abi.py checks both lists)
 EXPORTS_Q8 = ["mx_q8_matmul_probe", "mx_q8_matmul_plan", "mx_q8_side_probe"]
@@ -352,9 +356,22 @@ def lib() -> ctypes.CDLL:
         L.mx_lora_check.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         L.mx_engine_lora_info.argtypes = [vp, P(MxLoraInfo)]
         L.mx_lora_merge_probe.argtypes = [i32, i32, i32, i32, vp, vp, vp, ctypes.c_float, vp, i32, P(ctypes.c_double)]
+        L.mx_vocab_create.argtypes = [i32, vp, vp, vp, i32, P(vp)]
+        L.mx_vocab_destroy.argtypes = [vp]
+        L.mx_grammar_create.argtypes = [vp, ctypes.c_char_p, i32, P(vp)]
+        L.mx_grammar_destroy.argtypes = [vp]
+        L.mx_grammar_state_create.argtypes = [vp, P(vp)]
+        L.mx_grammar_state_mask.argtypes = [vp, vp, i32, P(i32)]
+        L.mx_grammar_state_accept.argtypes = [vp, i32]
+        L.mx_grammar_state_may_end.argtypes = [vp, P(i32)]
+        L.mx_grammar_state_destroy.argtypes = [vp]
+        L.mx_grammar_cache_stats.argtypes = [vp, P(u64), P(u64), P(u64)]
+        L.mx_submit_grammar.argtypes = [vp, vp, i32, P(MxSamplingExt), i32, i32, i32, vp, P(u64)]
+        L.mx_grammar_mask_probe.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp]
+        L.mx_grammar_mask_time.argtypes = [i32, i32, i32, i32, vp, i32, P(ctypes.c_double)]
         for name in EXPORTS + EXPORTS_Q8:
             if name not in ("mx_opts_default", "mx_sampling_default", "mx_sampling_ext_default", "mx_last_error",
-                            "mx_engine_destroy",
+                            "mx_engine_destroy", "mx_vocab_destroy", "mx_grammar_destroy", "mx_grammar_state_destroy",
                             "mx_batch_destroy", "mx_batch_ids_device"):
                 getattr(L, name).restype = i32
         _lib = L
@@ -1431,8 +1448,148 @@ def _check(rc: int):
         raise MxError(rc, lib().mx_last_error().decode(errors="replace"))
 
 
+# ---- grammar-constrained sampling (include/mx_engine.h mx_vocab_create ...) -- no GPU touched
+GRAMMAR_OK, GRAMMAR_DEAD_END, GRAMMAR_CAP = 0, 1, 2  # mx_engine.h MX_GRAMMAR_*: what GrammarState.mask() reports
+
+
+class GrammarVocab:
+    """What grammars are matched against: the piece bytes of every token (an empty piece is never allowed) and the
+    end-of-generation ids (allowed exactly where a grammar may end)."""
+
+    def __init__(self, pieces: Sequence[bytes], eog_ids: Sequence[int]):
+        self.n_vocab = len(pieces)
+        off = np.zeros(self.n_vocab + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(p) for p in pieces], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(pieces) or b"\0", dtype=np.uint8)
+        eog = _i32(list(eog_ids))
+        h = ctypes.c_void_p()
+        _check(lib().mx_vocab_create(self.n_vocab, blob.ctypes.data, off.ctypes.data, eog.ctypes.data if len(eog) else None,
+                                     len(eog), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mx_vocab_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CompiledGrammar:
+    """A GBNF grammar compiled over one vocabulary: immutable, shared by any number of requests and states, and
+    reference-counted in the library -- closing it, or its vocabulary, while a request still uses it is safe.
+    What GBNF refuses (syntax, undefined rules, no root, {m,n} with n < m, left recursion) raises ValueError with
+    the rule or position.  cache_entries: masks kept (None: the library's default; 0: no cache)."""
+
+    def __init__(self, vocab: GrammarVocab, gbnf: str, cache_entries: Optional[int] = None):
+        h = ctypes.c_void_p()
+        rc = lib().mx_grammar_create(vocab._h, gbnf.encode("utf-8"), -1 if cache_entries is None else int(cache_entries),
+                                     ctypes.byref(h))
+        if rc == MX_ERR_ARG:
+            raise ValueError(lib().mx_last_error().decode(errors="replace"))
+        _check(rc)
+        self._h = h
+        self.n_vocab = vocab.n_vocab
+
+    def state(self) -> "GrammarState":
+        return GrammarState(self)
+
+    def cache_stats(self) -> dict:
+        """hits / misses (mask lookups served from the cache / computed by a walk of the vocabulary), entries."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().mx_grammar_cache_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"hits": a.value, "misses": b.value, "entries": c.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mx_grammar_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GrammarState:
+    """A place in a grammar, as a request holds one (for probing on the CPU): starts at root."""
+
+    def __init__(self, grammar: CompiledGrammar):
+        h = ctypes.c_void_p()
+        _check(lib().mx_grammar_state_create(grammar._h, ctypes.byref(h)))
+        self._h = h
+        self.n_vocab = grammar.n_vocab
+
+    def mask(self):
+        """(words uint32 [ceil(V / 32)], status): bit t & 31 of word t >> 5 set = token t is allowed; status
+        GRAMMAR_OK, GRAMMAR_DEAD_END or GRAMMAR_CAP (the words all zero for the last two)."""
+        w = np.zeros((self.n_vocab + 31) // 32, dtype=np.uint32)
+        st = ctypes.c_int32()
+        _check(lib().mx_grammar_state_mask(self._h, w.ctypes.data, len(w), ctypes.byref(st)))
+        return w, st.value
+
+    def allowed(self) -> np.ndarray:
+        """The mask as booleans [V]."""
+        w, _ = self.mask()
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[: self.n_vocab].astype(bool)
+
+    def accept(self, token: int):
+        """Moves on by one token; MxError(MX_ERR_ARG) when it is not allowed (the state is unchanged)."""
+        _check(lib().mx_grammar_state_accept(self._h, int(token)))
+
+    def may_end(self) -> bool:
+        e = ctypes.c_int32()
+        _check(lib().mx_grammar_state_may_end(self._h, ctypes.byref(e)))
+        return bool(e.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mx_grammar_state_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def grammar_mask_probe(logits, masks, on, V: Optional[int] = None, device: int = 0) -> np.ndarray:
+    """The grammar mask kernel on caller-supplied f32 rows (no engine; include/mx_engine.h mx_grammar_mask_probe):
+    logits [n][ldl] with V <= ldl valid columns (default all), n <= 64; masks uint32 [n][ceil(V / 32)]; on [n].
+    Returns the rows as the kernel left them, [n][ldl]."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    n, ldl = lg.shape
+    V = ldl if V is None else V
+    mk = np.ascontiguousarray(masks, dtype=np.uint32)
+    ov = np.ascontiguousarray(on, dtype=np.uint32)
+    if mk.shape != (n, (V + 31) // 32) or ov.shape != (n,):
+        raise ValueError("masks [n][ceil(V / 32)] and on [n] expected")
+    out = np.empty_like(lg)
+    _check(lib().mx_grammar_mask_probe(device, lg.ctypes.data, n, V, ldl, mk.ctypes.data, ov.ctypes.data,
+                                       out.ctypes.data))
+    return out
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def grammar_mask_time(masks, V: int, ldl: Optional[int] = None, iters: int = 200, device: int = 0) -> float:
+    """Microseconds per launch of the grammar mask kernel over masks uint32 [n][ceil(V / 32)], every row on, on
+    resident buffers between two HIP events (include/mx_engine.h mx_grammar_mask_time)."""
+    mk = np.ascontiguousarray(masks, dtype=np.uint32)
+    if mk.ndim != 2 or mk.shape[1] != (V + 31) // 32:
+        raise ValueError("masks [n][ceil(V / 32)] expected")
+    us = ctypes.c_double()
+    _check(lib().mx_grammar_mask_time(device, mk.shape[0], V, V if ldl is None else ldl, mk.ctypes.data, int(iters),
+                                      ctypes.byref(us)))
+    return us.value
 
 
 class Engine:
@@ -1444,6 +1601,7 @@ class Engine:
     supports_prefix_sharing = True  # set_prefix_sharing() / sharing_stats(): what Llama.set_cache needs
     supports_sampler_ext = True  # submit(typical_p=, tfs_z=, mirostat_*=, logit_bias=): the whole sampler chain
     supports_host_cache = True  # set_host_cache() / host_cache_stats(): the host-RAM tier of Llama.set_cache
+    supports_grammar = True  # submit(grammar=): what Llama.create_completion(grammar=) needs
 
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
@@ -1584,8 +1742,12 @@ class Engine:
                seed: Optional[int] = None, ignore_eos: bool = False, frequency_penalty: float = 0.0,
                presence_penalty: float = 0.0, logprobs: Optional[int] = None, prompt_logprobs: bool = False,
                draft: Optional[Sequence[int]] = None, typical_p: float = 1.0, tfs_z: float = 1.0,
-               mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1, logit_bias=None) -> int:
-        """typical_p / tfs_z / mirostat_mode=2 (mirostat_tau, mirostat_eta) / logit_bias={id: bias}: the rest of
+               mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1, logit_bias=None,
+               grammar: Optional["CompiledGrammar"] = None) -> int:
+        """grammar: a CompiledGrammar over a vocabulary of the model's size -- every token is picked
+        among those the grammar allows after the tokens generated so far, whatever the sampler settings; such a
+        request never speculates (draft is ignored for it) and its rounds run one step.
+        typical_p / tfs_z / mirostat_mode=2 (mirostat_tau, mirostat_eta) / logit_bias={id: bias}: the rest of
         llama-cpp-python's sampler chain, on the device (mx_submit_ext); such a request never
         speculates.
         draft=(num_pred_tokens 1..15, max_ngram_size >= 1): prompt-lookup speculative decoding on the device --
@@ -1602,7 +1764,16 @@ class Engine:
         if seed is not None and seed >= 0:
             s.seed = seed
         req = ctypes.c_uint64()
-        if typical_p != 1.0 or tfs_z != 1.0 or mirostat_mode != 0 or logit_bias:
+        if grammar is not None:
+            if not isinstance(grammar, CompiledGrammar):
+                raise TypeError("grammar must be a CompiledGrammar")
+            if prompt_logprobs and logprobs is None:
+                raise ValueError("prompt_logprobs needs logprobs=k")
+            x, keep = sampling_ext(s, typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
+            _check(lib().mx_submit_grammar(self._h, ids.ctypes.data, len(ids), ctypes.byref(x), max_tokens,
+                                           -1 if logprobs is None else int(logprobs), int(bool(prompt_logprobs)),
+                                           grammar._h, ctypes.byref(req)))
+        elif typical_p != 1.0 or tfs_z != 1.0 or mirostat_mode != 0 or logit_bias:
             if prompt_logprobs and logprobs is None:
                 raise ValueError("prompt_logprobs needs logprobs=k")
             x, keep = sampling_ext(s, typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
@@ -1639,6 +1810,13 @@ class Engine:
                                          idx.ctypes.data if kk else None, cap, ctypes.byref(n), ctypes.byref(k)))
         return tok, top, idx
 
+    @staticmethod
+    def grammar_cache_stats(grammar: "CompiledGrammar") -> dict:
+        """hits / misses / entries of a compiled grammar's mask cache (mx_grammar_cache_stats)."""
+        return grammar.cache_stats()
+
+    grammar_mask_probe = staticmethod(grammar_mask_probe)
+
     def sampler_stats(self) -> dict:
         """device_steps / host_steps (decode steps picked on the device / by the host sampler), wide_rows (row-steps
         of the wide kernel: more than 64 candidates) and rounds (the scheduler rounds behind the
@@ -1659,6 +1837,8 @@ class Engine:
         keywords as submit() (or ``per_request``: one keyword dict per prompt), one seed per prompt,
         max_tokens one value or one per prompt.  Returns the request ids."""
         n = len(prompts)
+        if "grammar" in kw or any("grammar" in d for d in (per_request or [])):
+            raise ValueError("submit_many takes no grammar: a grammar request is queued with submit()")
         arrs = [_i32(p) for p in prompts]
         ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
         lens = _i32([len(a) for a in arrs])

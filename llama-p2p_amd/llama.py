@@ -34,6 +34,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 from . import engine as _engine
 from . import synth as _synth
 from .llama_cache import BaseLlamaCache, LlamaDiskCache
+from .llama_grammar import LlamaGrammar
 from .speculative import LlamaDraftModel, LlamaPromptLookupDecoding
 from .tokenizer import Tokenizer
 
@@ -246,13 +247,21 @@ class Llama:
                           presence_penalty: float = 0.0, repeat_penalty: float = 1.0, top_k: int = 40,
                           stream: bool = False, seed: Optional[int] = None, tfs_z: float = 1.0,
                           mirostat_mode: int = 0, mirostat_tau: float = 5.0, mirostat_eta: float = 0.1,
-                          logit_bias: Optional[Dict[int, float]] = None,
+                          logit_bias: Optional[Dict[int, float]] = None, grammar: Optional[LlamaGrammar] = None,
                           **kwargs: Any) -> Union[Dict[str, Any], Iterator[Dict[str, Any]]]:
         """llama-cpp-python's create_completion.  Every sampler setting is applied on the device, several decode
         steps per host round trip; top_k takes any value (<= 0 or at least the vocabulary size: every token is a
         candidate, as in llama-cpp-python).  Only a penalty window over 64 tokens, and tfs_z / typical_p over
-        more than 64 candidates, are sampled on the host (engine.sample_plan tells)."""
+        more than 64 candidates, are sampled on the host (engine.sample_plan tells).
+        grammar: a LlamaGrammar (GBNF) -- every generated token is one the grammar allows after
+        the ones before it, and once the grammar has ended only an end-of-generation token is.  A request whose
+        grammar reaches a point where no token of the vocabulary is allowed raises RuntimeError."""
         ext_kw = self._sampler_ext_kw(typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias)
+        if grammar is not None:
+            if not isinstance(grammar, LlamaGrammar):
+                raise TypeError("grammar must be a LlamaGrammar (LlamaGrammar.from_string(gbnf))")
+            if not getattr(self._engine, "supports_grammar", False):
+                raise NotImplementedError("grammar is not supported by this engine front")
         if logprobs is not None:
             if logprobs < 0 or logprobs > _engine.TOPK_MAX:
                 raise ValueError(f"logprobs must be 0..{_engine.TOPK_MAX} (llama-cpp-python has no cap; the "
@@ -278,6 +287,8 @@ class Llama:
         if draft is not None:  # only when set: engine fronts without the keyword keep working
             lp_kw["draft"] = draft
         lp_kw.update(ext_kw)  # only the non-default ones, as draft
+        if grammar is not None:  # only when given, as draft
+            lp_kw["grammar"] = grammar.compiled_for(self, self._grammar_vocab())
         req = self._engine.submit(prompt_tokens, max_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
                                   min_p=min_p, repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty,
                                   presence_penalty=presence_penalty, seed=None if sd == LLAMA_DEFAULT_SEED else sd,
@@ -334,6 +345,17 @@ class Llama:
             "usage": {"prompt_tokens": len(prompt_tokens), "completion_tokens": len(toks),
                       "total_tokens": len(prompt_tokens) + len(toks)},
         }
+
+    def _grammar_vocab(self) -> "_engine.GrammarVocab":
+        """The vocabulary grammars are matched against, built once: every token's piece as detokenize writes it
+        (control, unknown and unused tokens have none and are never allowed) and the end-of-generation ids."""
+        with self._lock:
+            v = getattr(self, "_gvocab", None)
+            if v is None:
+                tk, n = self.tokenizer_, self._engine.n_vocab
+                v = self._gvocab = _engine.GrammarVocab([tk.token_to_piece(t) for t in range(n)],
+                                                         [t for t in range(n) if tk.is_eog(t)])
+            return v
 
     def _sampler_ext_kw(self, typical_p, tfs_z, mirostat_mode, mirostat_tau, mirostat_eta, logit_bias) -> Dict[str, Any]:
         """The keywords of the extended sampler chain (typical_p, tfs_z, Mirostat v2, logit_bias) that are off
