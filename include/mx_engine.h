@@ -501,7 +501,7 @@ int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers
  * w: raw GGUF blocks, row-major [N][K/32]: Q8_0 (34 bytes) or, wq4 = 1, Q4_0 (18 bytes); N % 16, K % 64; SWIGLU:
  * rows [0, N/2) ffn_gate, [N/2, N) ffn_up.  Packed on the device with launch_pack_q8 / launch_pack_q4 as at model
  * load (packed_out, optional, receives the packed bytes).
- * Activations (act), from f32 rows xf as enqueue_forward_q8's operand makes them: 0 launch_quantize_q8 of xf
+ * Activations (act), from f32 rows xf as the engine's quant_operand makes them: 0 launch_quantize_q8 of xf
  * [M][ldx] (ldx >= K, 0 = K); 1 launch_rmsnorm_q8 of xf [xrows][K] with norm_w [K], eps, optional row_map [M]
  * (entries in [0, xrows); without it xrows = M) or fold_slabs [nslab][xrows][K], nslab 0..8, folded into x first
  * (x_out, optional, receives the folded rows); 2 quantise on load (path 0, mq8_can_quantize_on_load(M, K, norm)):
@@ -575,7 +575,7 @@ int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, con
  * increasing, the last 16 * it = N; K % 256.  Each segment is packed on the device with launch_pack_kq at its own
  * byte offset, as at model load (packed_out, optional, receives the packed bytes).  SWIGLU: one segment, rows
  * [0, N/2) ffn_gate (PACK_GATE), [N/2, N) ffn_up (PACK_UP), N % 32.
- * Activations (act), from f32 rows xf as enqueue_forward_kq's operand makes them: 0 launch_quantize_q8k of xf
+ * Activations (act), from f32 rows xf as the engine's quant_operand makes them: 0 launch_quantize_q8k of xf
  * [M][ldx] (ldx >= K, 0 = K); 1 launch_rmsnorm_q8k of xf [xrows][K] with norm_w [K], eps and optional row_map [M]
  * (entries in [0, xrows); without it xrows = M); 2 one token quantised on load (path 0, M 1,
  * mkq_can_quantize_on_load(1, K, norm)): xf [K], optional norm_w with the sum-of-squares partials ssq_in [K/16]

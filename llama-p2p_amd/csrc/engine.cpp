@@ -257,6 +257,30 @@ struct GraphKey {
     return stream < o.stream;
   }
 };
+
+// Where a pick's tokens go besides d_tok: the next step's ids / positions and a per-row history (the device
+// loops).  All-zero: tokens to d_tok only.
+struct PickOut {
+  int *ids_next, *pos_next, *hist;
+  int hist_stride;
+  int* hist_count;
+  int max_hist;
+};
+
+// One forward of M rows through this stage's layers (mx_engine::enqueue_forward).  ids or x_in feed it; x_out
+// takes the residual stream for the next stage; head: logits of n_out rows (the rowmap's, or all M), and with
+// argmax their picks.  Call sites name what they set; the rest is zero.
+struct Forward {
+  int M;
+  const int *ids, *pos, *slot;
+  const void* x_in;
+  void* x_out;
+  bool head;
+  const int* rowmap;
+  int n_out;
+  bool argmax;
+  PickOut out;
+};
 }  // namespace
 
 struct mx_batch {
@@ -482,8 +506,7 @@ struct mx_engine {
     pick_ext = d_sext;
     return (pick_miro ? 2 : 1) + (pick_wide ? 4 : 0);
   }
-  void pick(int n_out, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count, int max_hist,
-            hipStream_t s) {
+  void pick(int n_out, const PickOut& o, hipStream_t s) {
     const bool lp = pick_lp >= 0;
     SampExtArgs xa;
     xa.ext = pick_samp ? pick_ext : nullptr;
@@ -496,13 +519,13 @@ struct mx_engine {
     if (pick_gram && launch_grammar_mask(logits, n_vocab, n_out, n_vocab, d_gmask, d_gon, s)) gram_refused = true;
     if (pick_samp)
       launch_sample_chain(logits, n_vocab, n_out, n_vocab, pick_samp, pick_k, tk_ws_val, tk_ws_idx, tk_val, tk_idx,
-                          d_tok, ids_next, pos_next, hist, hist_stride, hist_count, max_hist, s,
+                          d_tok, o.ids_next, o.pos_next, o.hist, o.hist_stride, o.hist_count, o.max_hist, s,
                           lp ? lp_side_tok : nullptr, lp ? lp_side_val : nullptr, xa.ext ? &xa : nullptr);
     else
-      launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, ids_next, pos_next, hist, hist_stride,
-                    hist_count, max_hist, s);
+      launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, o.ids_next, o.pos_next, o.hist,
+                    o.hist_stride, o.hist_count, o.max_hist, s);
     if (lp)
-      launch_logprob_gather(logits, n_vocab, n_out, n_vocab, pick_lp, d_tok, hist ? hist_count : nullptr, SCHED_KMAX,
+      launch_logprob_gather(logits, n_vocab, n_out, n_vocab, pick_lp, d_tok, o.hist ? o.hist_count : nullptr, SCHED_KMAX,
                             pick_samp ? lp_side_tok : nullptr, lp_side_val, lp_ms, lp_top, lp_idx, lp_hist,
                             (size_t)SCHED_KMAX * (1 + 2 * pick_lp), s, xa.ext, d_bias_raw);
   }
@@ -604,9 +627,7 @@ struct mx_engine {
   int init_common();
   int load_synthetic(const Shape& s, uint64_t seed, bool q8 = false, int kq_base = 0, bool q4 = false);
   int load_gguf(const std::string& path);
-  int enqueue_forward(int M, const int* ids, const int* pos, const int* slot, const void* x_in, void* x_out,
-                      bool head, const int* rowmap, int n_out, bool argmax, int* ids_next, int* pos_next, int* hist,
-                      int hist_stride, int* hist_count, int max_hist, hipStream_t s);
+  int enqueue_forward(const Forward& f, hipStream_t s);
   bool q8_on_load(int M) const {
     return wq8 && q8_ql && mq8_can_quantize_on_load(M, n_embd, true) && mq8_can_quantize_on_load(M, n_ff, false);
   }
@@ -614,14 +635,14 @@ struct mx_engine {
   bool kq_on_load(int M) const {
     return wkq && mkq_can_quantize_on_load(M, n_embd, true) && mkq_can_quantize_on_load(M, n_ff, false);
   }
-  int enqueue_forward_q8(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap, int n_out,
-                         bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count,
-                         int max_hist, hipStream_t s);
-  int enqueue_forward_kq(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap, int n_out,
-                         bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride, int* hist_count,
-                         int max_hist, hipStream_t s);
-  int enqueue_forward_gemm(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap,
-                           int n_out, hipStream_t s);
+  int enqueue_forward_quant(const Forward& f, hipStream_t s);
+  int quant_operand(MMArgs& m, const KqMat* km, bool ql, int& nslab, const float* src, int K, const float* norm_w,
+                    int rows, const int* rmap, hipStream_t s);
+  int quant_head(const Forward& f, int& nslab, hipStream_t s);
+  // what every walk's q|k|v GEMV and attention launch of layer li share; the walk adds its operand and outputs
+  MMArgs qkv_args(const Layer& L, int li, const Forward& f) const;
+  AttnArgs attn_args(int li, const Forward& f) const;
+  int enqueue_forward_gemm(const Forward& f, hipStream_t s);
   bool gemm_shapes() const {  // the bf16 prefill GEMM takes every matrix of a layer
     return gemm_supported(n_embd + 2 * n_embd_kv, n_embd) && gemm_supported(n_embd, n_embd) &&
            gemm_supported(2 * n_ff, n_embd) && gemm_supported(n_embd, n_ff);
@@ -629,9 +650,7 @@ struct mx_engine {
   bool gemm_ok() const {  // chunks of PREFILL_ROWS rows can run (the Q8_0 / K-quant paths take any row count)
     return wq8 || wkq || gemm_shapes();
   }
-  int enqueue_forward_wide(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap,
-                           int n_out, bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride,
-                           int* hist_count, int max_hist, hipStream_t s, bool full_chain = false);
+  int enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_chain = false);
   int forward_rows_chunk(int n, const int32_t* slots, const int32_t* pos, const int32_t* ids, const void* x_in,
                          void* x_out, float* logits_host, hipStream_t s, bool last_row_only = false);
   void scheduler_loop();
@@ -1360,11 +1379,31 @@ out:
   return rc;
 }
 
+MMArgs mx_engine::qkv_args(const Layer& L, int li, const Forward& f) const {
+  MMArgs a{};
+  a.W = L.qkv; a.N = n_embd + 2 * n_embd_kv; a.K = n_embd; a.M = f.M;
+  a.out = q; a.ldo = n_embd; a.n_q = n_embd; a.n_kv = n_embd_kv; a.head_dim = head_dim; a.pos = f.pos; a.slot = f.slot;
+  a.rope_cs = rope_cs; a.kc = kcache + layer_kv_stride * li; a.vc = vcache + layer_kv_stride * li; a.n_ctx = n_ctx;
+  a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv; a.slot_stride = slot_stride;
+  return a;
+}
+
+AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
+  AttnArgs at{};
+  at.q = q; at.kc = kcache + layer_kv_stride * li; at.vc = vcache + layer_kv_stride * li; at.pos = f.pos; at.slot = f.slot;
+  at.ldo = n_embd; at.M = f.M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
+  at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
+  at.scale = 1.0f / sqrtf((float)head_dim);
+  return at;
+}
+
 // One forward of M <= MAX_ROWS rows through this stage's layers.
-int mx_engine::enqueue_forward(int M, const int* ids, const int* pos, const int* slot, const void* x_in, void* x_out,
-                               bool head, const int* rowmap, int n_out, bool argmax, int* ids_next, int* pos_next,
-                               int* hist, int hist_stride, int* hist_count, int max_hist, hipStream_t s) {
-  const int h = n_embd, kv = n_embd_kv, ff = n_ff;
+int mx_engine::enqueue_forward(const Forward& f, hipStream_t s) {
+  const int M = f.M, n_out = f.n_out, h = n_embd, ff = n_ff;
+  const int *ids = f.ids, *rowmap = f.rowmap;
+  const void* x_in = f.x_in;
+  void* x_out = f.x_out;
+  const bool head = f.head, argmax = f.argmax;
   const bool wide = use_wide && M > 16;
   // RMS_NORM applied on load by the consuming GEMV (M <= 16); the residual-stream writers
   // (embedding, attn_output, ffn_down, or ssq_kernel for a stage's x_in) leave per-tile partials
@@ -1388,26 +1427,21 @@ int mx_engine::enqueue_forward(int M, const int* ids, const int* pos, const int*
     }
   }
   if (wkq && !kq_ggml_prefill && M > MAX_ROWS && kqd_qkv && !argmax && !(head && n_out > MAX_ROWS))
-    return enqueue_forward_gemm(M, pos, slot, x_out, head, rowmap, n_out, s);  // dequantised bf16 GEMMs
+    return enqueue_forward_gemm(f, s);  // dequantised bf16 GEMMs
   // Q8_0 prefill chunks as dequantised bf16 GEMMs (llama.cpp's GPU-backend route for large batches):
   // ~5x the default's rate, but bf16 activations instead of ggml's Q8_0 rows, so opt-in
   // (MX_Q8_GEMM_PREFILL=1; tests/test_q8_gpu.py bounds its deviation)
   if (wq8 && !wq4 && q8_gemm_prefill && M > MAX_ROWS && kqd_qkv && !argmax && !(head && n_out > MAX_ROWS))
-    return enqueue_forward_gemm(M, pos, slot, x_out, head, rowmap, n_out, s);
-  if (wkq) return enqueue_forward_kq(M, pos, slot, x_out, head, rowmap, n_out, argmax, ids_next, pos_next, hist,
-                                     hist_stride, hist_count, max_hist, s);
-  if (wq8) return enqueue_forward_q8(M, pos, slot, x_out, head, rowmap, n_out, argmax, ids_next, pos_next, hist,
-                                     hist_stride, hist_count, max_hist, s);
+    return enqueue_forward_gemm(f, s);
+  if (wkq || wq8) return enqueue_forward_quant(f, s);
   if (prefill_gemm && M <= MAX_ROWS && use_wide && gemm_shapes() && !argmax)  // small prompt chunk, GEMM order
-    return enqueue_forward_wide(M, pos, slot, x_out, head, rowmap, n_out, false, nullptr, nullptr, nullptr, 0,
-                                nullptr, 0, s, true);
+    return enqueue_forward_wide(f, s, true);
   if (M > MAX_ROWS || (prefill_gemm && gemm_shapes() && !argmax)) {
     if (!gemm_ok() || argmax || (head && n_out > MAX_ROWS))
       return fail(MX_ERR_ARG, "forward of > 64 rows: GEMM shapes only, logits for <= 64 rows");
-    return enqueue_forward_gemm(M, pos, slot, x_out, head, rowmap, n_out, s);
+    return enqueue_forward_gemm(f, s);
   }
-  if (wide) return enqueue_forward_wide(M, pos, slot, x_out, head, rowmap, n_out, argmax, ids_next,
-                                        pos_next, hist, hist_stride, hist_count, max_hist, s);
+  if (wide) return enqueue_forward_wide(f, s);
   // on-load only for attn_norm -> qkv: qkv's 384 work-groups run 1.5 rounds, so its per-work-group
   // prologue costs less than a norm launch; gate/up (7 rounds) and lm_head (31) keep the norm kernel
   // (tools/kernel_probe.py, profiles/round1_norm_on_load.txt)
@@ -1421,19 +1455,10 @@ int mx_engine::enqueue_forward(int M, const int* ids, const int* pos, const int*
   };
   for (int li = 0; li < (int)layers.size(); li++) {
     const Layer& L = layers[li];
-    _Float16* kc = kcache + layer_kv_stride * li;
-    _Float16* vc = vcache + layer_kv_stride * li;
-    MMArgs a{};
-    a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.M = M;
+    MMArgs a = qkv_args(L, li, f);
     norm_operand(a, L.attn_norm, true);
-    a.out = q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = head_dim; a.pos = pos; a.slot = slot;
-    a.rope_cs = rope_cs; a.kc = kc; a.vc = vc; a.n_ctx = n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv;
-    a.slot_stride = slot_stride;
-    AttnArgs at{};
-    at.q = q; at.kc = kc; at.vc = vc; at.pos = pos; at.slot = slot;
-    at.out = attn_out; at.ldo = h; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
-    at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
-    at.scale = 1.0f / sqrtf((float)head_dim);
+    AttnArgs at = attn_args(li, f);
+    at.out = attn_out;
     const bool pers_qkv = use_pers && a.X == nullptr && mm_pers_supported(EPI_QKV, M, a.N, h);
     if ((pers_qkv ? launch_mm_pers(EPI_QKV, a, s) : -1) != 0 && launch_mm(EPI_QKV, a, s))
       return fail(MX_ERR_ARG, "qkv launch shape");
@@ -1476,9 +1501,7 @@ int mx_engine::enqueue_forward(int M, const int* ids, const int* pos, const int*
     }
     if ((pers_head ? launch_mm_pers(EPI_F32, g, s) : -1) != 0 && launch_mm(EPI_F32, g, s))
       return fail(MX_ERR_ARG, "lm_head launch shape");
-    if (argmax)
-      pick(n_out, ids_next, pos_next, hist, hist_stride,
-                    hist_count, max_hist, s);
+    if (argmax) pick(n_out, f.out, s);
   }
   HIPC(hipGetLastError());
   return 0;
@@ -1489,24 +1512,20 @@ int mx_engine::enqueue_forward(int M, const int* ids, const int* pos, const int*
 // full_chain: a prompt chunk of <= 64 rows (prefill_gemm) -- every GEMV one MFMA chain over K, the
 // prefill GEMM's order, so a prompt row's values do not depend on whether its chunk had 40 rows or 4000;
 // the prompt's 16-row blocks take the prefill attention as in the GEMM path
-int mx_engine::enqueue_forward_wide(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap,
-                                    int n_out, bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride,
-                                    int* hist_count, int max_hist, hipStream_t s, bool full_chain) {
-  const int h = n_embd, kv = n_embd_kv, ff = n_ff;
+int mx_engine::enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_chain) {
+  const int M = f.M, n_out = f.n_out, h = n_embd, ff = n_ff;
+  const int* rowmap = f.rowmap;
+  void* x_out = f.x_out;
+  const bool head = f.head;
   int nslab = 0;  // partial slabs not yet folded into x
   dbg_count = 0;
   for (int li = 0; li < (int)layers.size(); li++) {
     const Layer& L = layers[li];
-    _Float16* kc = kcache + layer_kv_stride * li;
-    _Float16* vc = vcache + layer_kv_stride * li;
     launch_resid_norm(xn, h, x, slabs, nslab, slab_stride, L.attn_norm, M, h, eps, s);
     nslab = 0;
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
-    MMArgs a{};
-    a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.M = M; a.X = xn; a.ldx = h;
-    a.out = q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = head_dim; a.pos = pos; a.slot = slot;
-    a.rope_cs = rope_cs; a.kc = kc; a.vc = vc; a.n_ctx = n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv;
-    a.slot_stride = slot_stride;
+    MMArgs a = qkv_args(L, li, f);
+    a.X = xn; a.ldx = h;
     const int qsplit = launch_mm_wide(EPI_QKV, a, slabs, slab_stride, s, false, full_chain);
     if (qsplit < 0) return fail(MX_ERR_ARG, "wide qkv launch shape");
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
@@ -1514,15 +1533,12 @@ int mx_engine::enqueue_forward_wide(int M, const int* pos, const int* slot, void
       launch_qkv_finish(a, slabs, qsplit, slab_stride, s);
       if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
     }
-    AttnArgs at{};
+    AttnArgs at = attn_args(li, f);
+    at.out = attn_out;
     if (rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
-      at.slabs = slabs; at.nslab = qsplit; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = kc;
-      at.vc_w = vc;
+      at.slabs = slabs; at.nslab = qsplit; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
+      at.vc_w = a.vc;
     }
-    at.q = q; at.kc = kc; at.vc = vc; at.pos = pos; at.slot = slot;
-    at.out = attn_out; at.ldo = h; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
-    at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
-    at.scale = 1.0f / sqrtf((float)head_dim);
     if (full_chain && rows_blocked) launch_attention_prefill(at, s);
     else launch_attention(at, s);
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
@@ -1563,9 +1579,7 @@ int mx_engine::enqueue_forward_wide(int M, const int* pos, const int* slot, void
     g.W = output; g.N = n_vocab; g.K = h; g.M = n_out; g.X = xn; g.ldx = h; g.out = logits; g.ldo = n_vocab;
     const int rc = n_out > 16 ? launch_mm_wide(EPI_F32, g, slabs, slab_stride, s) : launch_mm(EPI_F32, g, s);
     if (rc < 0) return fail(MX_ERR_ARG, "lm_head launch shape");
-    if (argmax)
-      pick(n_out, ids_next, pos_next, hist, hist_stride,
-                    hist_count, max_hist, s);
+    if (f.argmax) pick(n_out, f.out, s);
   } else if (nslab) {
     launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, M, h, eps, s);
   }
@@ -1573,221 +1587,137 @@ int mx_engine::enqueue_forward_wide(int M, const int* pos, const int* slot, void
   return 0;
 }
 
-// Q8_0 model, any M <= PREFILL_ROWS: every MUL_MAT takes Q8_0 activation rows made by the norm
-// (RMS_NORM + MUL + quantise) or by launch_quantize_q8 from the f32 attention output / SwiGLU
-// product -- ggml's conversion of src1 to the weight's vec_dot_type.
-int mx_engine::enqueue_forward_q8(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap,
-                                  int n_out, bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride,
-                                  int* hist_count, int max_hist, hipStream_t s) {
-  const int h = n_embd, kv = n_embd_kv, ff = n_ff;
-  if (head && n_out > MAX_ROWS) return fail(MX_ERR_ARG, "logits for at most 64 rows per forward");
-  // <= 4 rows: every GEMV quantises its operand on load (RMS_NORM from the ssq partials the
-  // residual writers leave); more rows: Q8_0 rows made once per GEMV by a norm / quantise launch
-  const bool ql = q8_on_load(M);
-  // 17..32 rows: attn_output / ffn_down as split-K slabs (launch_mq8_slab) folded by the next
-  // RMS_NORM + quantise launch; nslab = partials not yet folded into x
-  int nslab = 0;
-  auto operand = [&](MMArgs& m, const float* src, int K, const float* norm_w, int rows, const int* rmap) {
-    if (ql && !rmap) {
-      m.xq = nullptr; m.xf = src; m.norm_w = norm_w; m.eps = eps; m.ssq = norm_w ? ssq : nullptr; m.np = K / 16;
-    } else {
-      if (norm_w && src == x && nslab) {
-        launch_rmsnorm_q8(xq8, xqd, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
-        nslab = 0;
-      } else if (norm_w) {
-        launch_rmsnorm_q8(xq8, xqd, src, norm_w, rmap, rows, K, eps, s);
-      } else {
-        launch_quantize_q8(xq8, xqd, src, K, rows, K, s);
-      }
-      m.xq = xq8; m.xd = xqd;
-    }
-  };
-  auto resid = [&](MMArgs& m) -> int {
-    if (!ql && M > 16 && M <= 32) {
-      const int ks = launch_mq8_slab(m, slabs, slab_stride, s);
-      if (ks > 0) return nslab = ks, 0;
-    }
-    return launch_mq8(EPI_RESID, m, s);
-  };
-  for (int li = 0; li < (int)layers.size(); li++) {
-    const Layer& L = layers[li];
-    _Float16* kc = kcache + layer_kv_stride * li;
-    _Float16* vc = vcache + layer_kv_stride * li;
-    MMArgs a{};
-    a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.M = M; a.wq4 = wq4;
-    operand(a, x, h, L.attn_norm, M, nullptr);
-    a.out = q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = head_dim; a.pos = pos; a.slot = slot;
-    a.rope_cs = rope_cs; a.kc = kc; a.vc = vc; a.n_ctx = n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv;
-    a.slot_stride = slot_stride;
-    AttnArgs at{};
-    const int qs = (!ql && M > 16 && M <= 32) ? launch_mq8_slab(a, slabs, slab_stride, s) : -1;
-    if (qs > 0 && rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
-      at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = kc;
-      at.vc_w = vc;
-    } else if (qs > 0) {
-      launch_qkv_finish(a, slabs, qs, slab_stride, s);
-    } else if (launch_mq8(EPI_QKV, a, s)) {
-      return fail(MX_ERR_ARG, "q8 qkv launch shape");
-    }
-    at.q = q; at.kc = kc; at.vc = vc; at.pos = pos; at.slot = slot;
-    at.outf = attn_f; at.ldo = h; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
-    at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
-    at.scale = 1.0f / sqrtf((float)head_dim);
-    if (M > MAX_ROWS && rows_blocked) launch_attention_prefill(at, s);
-    else launch_attention(at, s);
-    MMArgs b{};
-    b.W = L.o; b.N = h; b.K = h; b.M = M; b.out = x; b.ldo = h; b.wq4 = wq4;
-    operand(b, attn_f, h, nullptr, M, nullptr);
-    b.ssq = ql ? ssq : nullptr; b.np = h / 16;  // partials of the new residual for gate/up's norm
-    if (resid(b)) return fail(MX_ERR_ARG, "q8 attn_output launch shape");
-    MMArgs c{};
-    c.W = L.gu; c.N = 2 * ff; c.K = h; c.M = M; c.actf = act_f; c.lda = ff; c.wq4 = wq4;
-    // (a separate RMS_NORM + quantise launch for gate/up measured slower: profiles/round5_quant_batch1_onload.txt)
-    operand(c, x, h, L.ffn_norm, M, nullptr);
-    if (launch_mq8(EPI_SWIGLU, c, s)) return fail(MX_ERR_ARG, "q8 gate/up launch shape");
-    MMArgs d{};
-    d.W = L.down; d.N = h; d.K = ff; d.M = M; d.out = x; d.ldo = h; d.wq4 = wq4;
-    operand(d, act_f, ff, nullptr, M, nullptr);
-    d.ssq = ql ? ssq : nullptr; d.np = h / 16;  // for the next layer's qkv (or lm_head) norm
-    if (resid(d)) return fail(MX_ERR_ARG, "q8 ffn_down launch shape");
+// The operand of one quantised MUL_MAT, ggml's conversion of src1 to the weight's vec_dot_type:
+// Q8_K rows for a K-quant matrix (km), Q8_0 rows for a Q8_0 / Q4_0 one (km null).  ql: taken on load by the
+// GEMV itself (RMS_NORM from the Σx² partials the residual writers leave) -- never under a row map; otherwise made
+// by one launch, RMS_NORM + MUL + quantise (norm_w) or quantise alone.  A norm of the residual stream folds the
+// nslab pending split-K slabs into x on its way.
+int mx_engine::quant_operand(MMArgs& m, const KqMat* km, bool ql, int& nslab, const float* src, int K,
+                             const float* norm_w, int rows, const int* rmap, hipStream_t s) {
+  if (km) km->set(m);
+  if (ql && !rmap) {
+    m.xq = nullptr; m.xf = src; m.norm_w = norm_w; m.eps = eps; m.ssq = norm_w ? ssq : nullptr; m.np = K / 16;
+    return 0;
   }
-  if (nslab && (x_out || !(head && !rowmap && n_out == M))) {  // x itself is read next: fold
-    launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, M, h, eps, s);
-    nslab = 0;
-  }
-  if (x_out)
-    if (int rc = copy_out(x_out, M, s)) return rc;
-  if (head) {
-    if (!has_head) return fail(MX_ERR_STATE, "this stage has no output head");
-    MMArgs g{};
-    g.W = output; g.N = n_vocab; g.K = h; g.M = n_out; g.out = logits; g.ldo = n_vocab;
-    if (out_kq_head) {  // K-quant output (Q4_0 files): Q8_K rows of the normed rows, ggml's q6_K.q8_K
-      if (nslab) {
-        launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, M, h, eps, s);
-        nslab = 0;
-      }
-      kq_out.set(g);
-      if (launch_rmsnorm_q8k(xq8, xqd, xkb, x, out_norm, (rowmap || n_out != M) ? rowmap : nullptr, n_out, h, eps, s))
-        return fail(MX_ERR_ARG, "kq head norm");
-      g.xq = xq8; g.xd = xqd; g.xb = xkb;
-      if (launch_mkq(EPI_F32, g, s)) return fail(MX_ERR_ARG, "kq lm_head launch shape");
-    } else {
-      g.wq4 = out_q4;
-      operand(g, x, h, out_norm, n_out, (rowmap || n_out != M) ? rowmap : nullptr);
-      if (launch_mq8(EPI_F32, g, s)) return fail(MX_ERR_ARG, "q8 lm_head launch shape");
-    }
-    if (argmax)
-      pick(n_out, ids_next, pos_next, hist, hist_stride,
-                    hist_count, max_hist, s);
-  }
-  HIPC(hipGetLastError());
-  return 0;
-}
-
-// K-quant model, any M <= PREFILL_ROWS: every MUL_MAT takes Q8_K activation rows made by the norm
-// (RMS_NORM + MUL + quantise) or by launch_quantize_q8k from the f32 attention output / SwiGLU
-// product -- ggml's conversion of src1 to the K-quants' vec_dot_type.
-int mx_engine::enqueue_forward_kq(int M, const int* pos, const int* slot, void* x_out, bool head, const int* rowmap,
-                                  int n_out, bool argmax, int* ids_next, int* pos_next, int* hist, int hist_stride,
-                                  int* hist_count, int max_hist, hipStream_t s) {
-  const int h = n_embd, kv = n_embd_kv, ff = n_ff;
-  if (head && n_out > MAX_ROWS) return fail(MX_ERR_ARG, "logits for at most 64 rows per forward");
-  // One token: every GEMV quantises its Q8_K operand on load (RMS_NORM from the Σx² partials the
-  // residual writers leave); otherwise one norm / quantise launch per GEMV.  (A v_dot4 kernel
-  // quantising on load measured slower: 3.09 vs 2.80 ms per 8B token.)
-  const bool ql = kq_on_load(M);
-  // 17..32 rows: attn_output / ffn_down run split-K into slabs (launch_mkq_slab) and the next
-  // RMS_NORM + Q8_K launch folds them into x; nslab = partials not yet folded
-  int nslab = 0;
-  auto operand = [&](MMArgs& m, const KqMat& km, const float* src, int K, const float* norm_w, int rows,
-                     const int* rmap) -> int {
-    km.set(m);
-    if (ql && !rmap) {
-      m.xq = nullptr; m.xf = src; m.norm_w = norm_w; m.eps = eps; m.ssq = norm_w ? ssq : nullptr; m.np = K / 16;
-      return 0;
-    }
-    int rc;
-    if (norm_w && src == x && nslab) {
-      if (K > 16 * 256) {  // launch_rmsnorm_q8k folds in one work-group per row, n <= 4096 (h 8192: Llama-3-70B): fold first
-        launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, rows, K, eps, s);
-        rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s);
-      } else {
-        rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
-      }
-      nslab = 0;
+  const bool fold = norm_w && src == x && nslab;
+  int rc = 0;
+  if (km) {
+    if (fold && K > 16 * 256) {  // launch_rmsnorm_q8k folds in one work-group per row, n <= 4096 (h 8192: Llama-3-70B): fold first
+      launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, rows, K, eps, s);
+      rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s);
+    } else if (fold) {
+      rc = launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
     } else {
       rc = norm_w ? launch_rmsnorm_q8k(xq8, xqd, xkb, src, norm_w, rmap, rows, K, eps, s)
                   : launch_quantize_q8k(xq8, xqd, xkb, src, K, rows, K, s);
     }
-    m.xq = xq8; m.xd = xqd; m.xb = xkb;
-    return rc;
+    m.xb = xkb;
+  } else if (fold) {
+    launch_rmsnorm_q8(xq8, xqd, src, norm_w, rmap, rows, K, eps, s, slabs, nslab, slab_stride);
+  } else if (norm_w) {
+    launch_rmsnorm_q8(xq8, xqd, src, norm_w, rmap, rows, K, eps, s);
+  } else {
+    launch_quantize_q8(xq8, xqd, src, K, rows, K, s);
+  }
+  if (fold) nslab = 0;
+  m.xq = xq8; m.xd = xqd;
+  return rc;
+}
+
+// The head of a quantised model: the output norm as the operand of the output matrix, Q8_K rows when that is a
+// K-quant (a K-quant model, or a Q4_0 file with its Q6_K output: out_kq_head, ggml's q6_K.q8_K), Q8_0 rows
+// otherwise.  nslab: slabs of the last ffn_down still pending (all M rows are read, no row map).
+int mx_engine::quant_head(const Forward& f, int& nslab, hipStream_t s) {
+  const int h = n_embd;
+  const KqMat* km = (wkq || out_kq_head) ? &kq_out : nullptr;
+  MMArgs g{};
+  g.W = output; g.N = n_vocab; g.K = h; g.M = f.n_out; g.out = logits; g.ldo = n_vocab;
+  if (!km) g.wq4 = out_q4;
+  bool ql = wkq ? kq_on_load(f.M) : q8_on_load(f.M);
+  if (!wkq && km) {  // the Q8_0 walk's K-quant head: always a norm launch, on x with the slabs folded
+    if (nslab) launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, f.M, h, eps, s);
+    nslab = 0;
+    ql = false;
+  }
+  if (quant_operand(g, km, ql, nslab, x, h, out_norm, f.n_out, (f.rowmap || f.n_out != f.M) ? f.rowmap : nullptr, s))
+    return fail(MX_ERR_ARG, "kq head norm");
+  if (km ? launch_mkq(EPI_F32, g, s) : launch_mq8(EPI_F32, g, s))
+    return fail(MX_ERR_ARG, std::string(km ? "kq" : "q8") + " lm_head launch shape");
+  return 0;
+}
+
+// Q8_0 / Q4_0 or K-quant model, any M <= PREFILL_ROWS: every MUL_MAT takes quantised activation rows
+// (quant_operand; Q8_0 rows or Q8_K rows, by the weights' format).  The format shows only in the four helpers.
+int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
+  const int M = f.M, h = n_embd, ff = n_ff;
+  const std::string fmt = wkq ? "kq" : "q8";
+  if (f.head && f.n_out > MAX_ROWS) return fail(MX_ERR_ARG, "logits for at most 64 rows per forward");
+  // Q8_0 at <= 4 rows, K-quants at one: every GEMV quantises its operand on load; more rows: one norm / quantise
+  // launch per GEMV.  (A separate launch for gate/up measured slower at Q8_0: profiles/round5_quant_batch1_onload.txt;
+  // a v_dot4 K-quant kernel quantising on load measured slower: 3.09 vs 2.80 ms per 8B token.)
+  const bool ql = wkq ? kq_on_load(M) : q8_on_load(M);
+  // 17..32 rows: q|k|v, attn_output and ffn_down as split-K slabs; the attention (distinct sequences) or
+  // launch_qkv_finish finishes q|k|v, the next norm + quantise launch folds the other two into x
+  const bool slab_rows = !ql && M > 16 && M <= 32;
+  int nslab = 0;  // partials not yet folded into x
+  auto operand = [&](MMArgs& m, const KqMat& km, const float* src, int K, const float* norm_w) -> int {
+    if (!wkq) m.wq4 = wq4;
+    return quant_operand(m, wkq ? &km : nullptr, ql, nslab, src, K, norm_w, M, nullptr, s);
   };
-  auto resid = [&](MMArgs& m) -> int {  // x += W . operand, in place or as slabs for the next operand()
-    if (!ql && M > 16 && M <= 32) {
-      const int ks = launch_mkq_slab(m, slabs, slab_stride, s);
+  auto mm = [&](int epi, const MMArgs& m) -> int { return wkq ? launch_mkq(epi, m, s) : launch_mq8(epi, m, s); };
+  auto qkv_slab = [&](const MMArgs& m) -> int {  // not resid's launcher for the K-quants
+    if (!slab_rows) return -1;
+    return wkq ? launch_mkq_qkv_slab(m, slabs, slab_stride, s) : launch_mq8_slab(m, slabs, slab_stride, s);
+  };
+  auto resid = [&](const MMArgs& m) -> int {  // x += W . operand, in place or as slabs for the next norm
+    if (slab_rows) {
+      const int ks = wkq ? launch_mkq_slab(m, slabs, slab_stride, s) : launch_mq8_slab(m, slabs, slab_stride, s);
       if (ks > 0) return nslab = ks, 0;
     }
-    return launch_mkq(EPI_RESID, m, s);
+    return mm(EPI_RESID, m);
   };
   for (int li = 0; li < (int)layers.size(); li++) {
     const Layer& L = layers[li];
-    _Float16* kc = kcache + layer_kv_stride * li;
-    _Float16* vc = vcache + layer_kv_stride * li;
-    MMArgs a{};
-    a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.M = M;
-    if (operand(a, L.kq_qkv, x, h, L.attn_norm, M, nullptr)) return fail(MX_ERR_ARG, "kq norm shape");
-    a.out = q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = head_dim; a.pos = pos; a.slot = slot;
-    a.rope_cs = rope_cs; a.kc = kc; a.vc = vc; a.n_ctx = n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv;
-    a.slot_stride = slot_stride;
-    AttnArgs at{};
-    // 17..32 rows: q|k|v as split-K slabs, finished by the attention kernel (distinct sequences) or
-    // by launch_qkv_finish
-    const int qs = (!ql && M > 16 && M <= 32) ? launch_mkq_qkv_slab(a, slabs, slab_stride, s) : -1;
-    if (qs > 0 && rows_distinct) {
-      at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = kc;
-      at.vc_w = vc;
+    MMArgs a = qkv_args(L, li, f);
+    if (operand(a, L.kq_qkv, x, h, L.attn_norm)) return fail(MX_ERR_ARG, fmt + " norm shape");
+    AttnArgs at = attn_args(li, f);
+    at.outf = attn_f;
+    const int qs = qkv_slab(a);
+    if (qs > 0 && rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
+      at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
+      at.vc_w = a.vc;
     } else if (qs > 0) {
       launch_qkv_finish(a, slabs, qs, slab_stride, s);
-    } else if (launch_mkq(EPI_QKV, a, s)) {
-      return fail(MX_ERR_ARG, "kq qkv launch shape");
+    } else if (mm(EPI_QKV, a)) {
+      return fail(MX_ERR_ARG, fmt + " qkv launch shape");
     }
-    at.q = q; at.kc = kc; at.vc = vc; at.pos = pos; at.slot = slot;
-    at.outf = attn_f; at.ldo = h; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
-    at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
-    at.scale = 1.0f / sqrtf((float)head_dim);
     if (M > MAX_ROWS && rows_blocked) launch_attention_prefill(at, s);
     else launch_attention(at, s);
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.M = M; b.out = x; b.ldo = h;
-    if (operand(b, L.kq_o, attn_f, h, nullptr, M, nullptr)) return fail(MX_ERR_ARG, "kq quantise shape");
-    b.ssq = ql ? ssq : nullptr; b.np = h / 16;  // Σx² partials of the new residual for gate/up
-    if (resid(b)) return fail(MX_ERR_ARG, "kq attn_output launch shape");
+    if (operand(b, L.kq_o, attn_f, h, nullptr)) return fail(MX_ERR_ARG, fmt + " quantise shape");
+    b.ssq = ql ? ssq : nullptr; b.np = h / 16;  // Σx² partials of the new residual for gate/up's norm
+    if (resid(b)) return fail(MX_ERR_ARG, fmt + " attn_output launch shape");
     MMArgs c{};
     c.W = L.gu; c.N = 2 * ff; c.K = h; c.M = M; c.actf = act_f; c.lda = ff;
-    if (operand(c, L.kq_gu, x, h, L.ffn_norm, M, nullptr) || launch_mkq(EPI_SWIGLU, c, s))
-      return fail(MX_ERR_ARG, "kq gate/up launch shape");
+    if (operand(c, L.kq_gu, x, h, L.ffn_norm) || mm(EPI_SWIGLU, c))
+      return fail(MX_ERR_ARG, fmt + " gate/up launch shape");
     MMArgs d{};
     d.W = L.down; d.N = h; d.K = ff; d.M = M; d.out = x; d.ldo = h;
-    if (operand(d, L.kq_down, act_f, ff, nullptr, M, nullptr)) return fail(MX_ERR_ARG, "kq quantise shape");
-    d.ssq = ql ? ssq : nullptr; d.np = h / 16;  // ... for the next layer's qkv (and the head)
-    if (resid(d)) return fail(MX_ERR_ARG, "kq ffn_down launch shape");
+    if (operand(d, L.kq_down, act_f, ff, nullptr)) return fail(MX_ERR_ARG, fmt + " quantise shape");
+    d.ssq = ql ? ssq : nullptr; d.np = h / 16;  // ... for the next layer's qkv (or lm_head) norm
+    if (resid(d)) return fail(MX_ERR_ARG, fmt + " ffn_down launch shape");
   }
-  if (nslab && (x_out || !(head && !rowmap && n_out == M))) {  // x itself is read next: fold the partials
+  if (nslab && (f.x_out || !(f.head && !f.rowmap && f.n_out == M))) {  // x itself is read next: fold the partials
     launch_resid_norm(nullptr, 0, x, slabs, nslab, slab_stride, nullptr, M, h, eps, s);
     nslab = 0;
   }
-  if (x_out)
-    if (int rc = copy_out(x_out, M, s)) return rc;
-  if (head) {
+  if (f.x_out)
+    if (int rc = copy_out(f.x_out, M, s)) return rc;
+  if (f.head) {
     if (!has_head) return fail(MX_ERR_STATE, "this stage has no output head");
-    MMArgs g{};
-    g.W = output; g.N = n_vocab; g.K = h; g.M = n_out; g.out = logits; g.ldo = n_vocab;
-    if (operand(g, kq_out, x, h, out_norm, n_out, (rowmap || n_out != M) ? rowmap : nullptr) ||
-        launch_mkq(EPI_F32, g, s))
-      return fail(MX_ERR_ARG, "kq lm_head launch shape");
-    if (argmax)
-      pick(n_out, ids_next, pos_next, hist, hist_stride,
-                    hist_count, max_hist, s);
+    if (int rc = quant_head(f, nslab, s)) return rc;
+    if (f.argmax) pick(f.n_out, f.out, s);
   }
   HIPC(hipGetLastError());
   return 0;
@@ -1798,9 +1728,11 @@ int mx_engine::enqueue_forward_kq(int M, const int* pos, const int* slot, void* 
 // model's layer is first dequantised to bf16 tiles (launch_dequant_kq: ~0.6 GB of HBM traffic per
 // Llama-3-8B layer, a few % of a 4096-row chunk's GEMM time) -- the route llama.cpp's GPU backends
 // take for large batches; decode keeps the int8-MFMA K-quant GEMVs with Q8_K activations.
-int mx_engine::enqueue_forward_gemm(int M, const int* pos, const int* slot, void* x_out, bool head,
-                                    const int* rowmap, int n_out, hipStream_t s) {
-  const int h = n_embd, kv = n_embd_kv, ff = n_ff;
+int mx_engine::enqueue_forward_gemm(const Forward& f, hipStream_t s) {
+  const int M = f.M, n_out = f.n_out, h = n_embd, kv = n_embd_kv, ff = n_ff;
+  const int* rowmap = f.rowmap;
+  void* x_out = f.x_out;
+  const bool head = f.head;
   const size_t gstride = (size_t)M * h;  // RESID partial slabs [S][M][h]
   int nslab = 0;                         // ... not yet folded into x
   auto dequant = [&](uint16_t* dst, const KqMat& km, const uint16_t* w, int K) -> int {
@@ -1808,8 +1740,6 @@ int mx_engine::enqueue_forward_gemm(int M, const int* pos, const int* slot, void
   };
   for (int li = 0; li < (int)layers.size(); li++) {
     const Layer& L = layers[li];
-    _Float16* kc = kcache + layer_kv_stride * li;
-    _Float16* vc = vcache + layer_kv_stride * li;
     const uint16_t *Wqkv = L.qkv, *Wo = L.o, *Wgu = L.gu, *Wdown = L.down;
     if (wkq) {
       if (dequant(kqd_qkv, L.kq_qkv, L.qkv, h) || dequant(kqd_o, L.kq_o, L.o, h) || dequant(kqd_gu, L.kq_gu, L.gu, h) ||
@@ -1826,17 +1756,11 @@ int mx_engine::enqueue_forward_gemm(int M, const int* pos, const int* slot, void
       Wqkv = kqd_qkv, Wo = kqd_o, Wgu = kqd_gu, Wdown = kqd_down;
     }
     launch_resid_norm(xn, h, x, gslabs, nslab, gstride, L.attn_norm, M, h, eps, s);
-    MMArgs a{};
-    a.W = Wqkv; a.N = h + 2 * kv; a.K = h; a.M = M; a.X = xn; a.ldx = h;
-    a.out = q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = head_dim; a.pos = pos; a.slot = slot;
-    a.rope_cs = rope_cs; a.kc = kc; a.vc = vc; a.n_ctx = n_ctx; a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv;
-    a.slot_stride = slot_stride;
+    MMArgs a = qkv_args(L, li, f);
+    a.W = Wqkv; a.X = xn; a.ldx = h;
     if (launch_gemm_split(EPI_QKV, a, gslabs, GSLAB_FLOATS, gemm_split_target, s) < 0) return fail(MX_ERR_ARG, "prefill qkv GEMM shape");
-    AttnArgs at{};
-    at.q = q; at.kc = kc; at.vc = vc; at.pos = pos; at.slot = slot;
-    at.out = attn_out; at.ldo = h; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
-    at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
-    at.scale = 1.0f / sqrtf((float)head_dim);
+    AttnArgs at = attn_args(li, f);
+    at.out = attn_out;
     if (rows_blocked) launch_attention_prefill(at, s);
     else launch_attention(at, s);
     MMArgs b{};
@@ -1859,18 +1783,12 @@ int mx_engine::enqueue_forward_gemm(int M, const int* pos, const int* slot, void
   if (head) {
     if (!has_head) return fail(MX_ERR_STATE, "this stage has no output head");
     if (!rowmap) return fail(MX_ERR_ARG, "prefill head needs a row map");
-    MMArgs g{};
-    g.W = output; g.N = n_vocab; g.K = h; g.M = n_out; g.out = logits; g.ldo = n_vocab;
-    if (wkq || out_kq_head) {  // the K-quant head as at decode: Q8_K rows of the normed last rows
-      kq_out.set(g);
-      if (launch_rmsnorm_q8k(xq8, xqd, xkb, x, out_norm, rowmap, n_out, h, eps, s)) return fail(MX_ERR_ARG, "kq norm");
-      g.xq = xq8; g.xd = xqd; g.xb = xkb;
-      if (launch_mkq(EPI_F32, g, s)) return fail(MX_ERR_ARG, "kq lm_head launch shape");
-    } else if (wq8) {  // the Q8_0 head as at decode
-      launch_rmsnorm_q8(xq8, xqd, x, out_norm, rowmap, n_out, h, eps, s);
-      g.xq = xq8; g.xd = xqd; g.wq4 = out_q4;
-      if (launch_mq8(EPI_F32, g, s)) return fail(MX_ERR_ARG, "q8 lm_head launch shape");
+    if (wkq || out_kq_head || wq8) {  // the quantised head as at decode, on the normed last rows
+      int folded = 0;  // the slabs went into x above
+      if (int rc = quant_head(f, folded, s)) return rc;
     } else {
+      MMArgs g{};
+      g.W = output; g.N = n_vocab; g.K = h; g.M = n_out; g.out = logits; g.ldo = n_vocab;
       launch_rmsnorm(xn, h, x, out_norm, rowmap, n_out, h, eps, s);
       g.X = xn; g.ldx = h;
       // the decode GEMVs (canonical K order at every row count), so a prompt's first token does not
@@ -1929,8 +1847,9 @@ int mx_engine::forward_rows_chunk(int n, const int32_t* slots, const int32_t* po
     const int32_t last = n - 1;
     if (int rc = h2d(d_rowmap, &last, 1, 3)) return rc;
   }
-  const int frc = enqueue_forward(n, d_ids, d_pos, d_slot, x_in, x_out, head, head && last_row_only ? d_rowmap : nullptr,
-                                  n_out, false, nullptr, nullptr, nullptr, 0, nullptr, 0, s);
+  const int frc = enqueue_forward({.M = n, .ids = d_ids, .pos = d_pos, .slot = d_slot, .x_in = x_in, .x_out = x_out,
+                                   .head = head, .rowmap = head && last_row_only ? d_rowmap : nullptr, .n_out = n_out},
+                                  s);
   rows_distinct = false;
   rows_blocked = false;
   if (frc) {  // the index copies enqueued above still read h_idx: drain them before it is reused
@@ -2465,8 +2384,9 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data() + i, pos.data() + i, ids.data() + i, m);
     prefill_gemm = true;
-    const int frc = enqueue_forward(m, d_ids, d_pos, d_slot, nullptr, nullptr, n_out > 0, n_out ? d_rowmap : nullptr,
-                                    n_out, false, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
+    const int frc = enqueue_forward({.M = m, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = n_out > 0,
+                                     .rowmap = n_out ? d_rowmap : nullptr, .n_out = n_out},
+                                    st);
     rows_blocked = false;
     prefill_gemm = false;
     if (frc) return frc;
@@ -2492,7 +2412,7 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       if (xl < 0) return fail(MX_ERR_HIP, "sampler settings copy");
       pick_samp = d_samp;
       pick_k = ktop;
-      pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
+      pick(n_out, PickOut{}, st);
       pick_samp = nullptr;
       pick_k = 0;
       pick_ext = nullptr, pick_miro = false, pick_wide = false;
@@ -2503,7 +2423,7 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
       HIPC(hipMemcpyAsync(tok.data() + q0, d_tok, n_out * 4, hipMemcpyDeviceToHost, st));
     } else if (n_out) {
       if (lpk >= 0 || pick_gram)
-        pick(n_out, nullptr, nullptr, nullptr, 0, nullptr, 0, st);  // pick_samp is null: argmax
+        pick(n_out, PickOut{}, st);  // pick_samp is null: argmax
       else
         launch_argmax(logits, n_vocab, n_out, n_vocab, am_val, am_idx, d_tok, nullptr, nullptr, nullptr, 0, nullptr,
                       0, st);
@@ -2585,8 +2505,8 @@ int mx_engine::prefill_prompt_logprobs(Request* r) {
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data(), pos.data(), ids.data(), mp);
     prefill_gemm = true;
-    const int frc = enqueue_forward(mp, d_ids, d_pos, d_slot, nullptr, nullptr, true, d_rowmap, m, false, nullptr,
-                                    nullptr, nullptr, 0, nullptr, 0, st);
+    const int frc = enqueue_forward(
+        {.M = mp, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = true, .rowmap = d_rowmap, .n_out = m}, st);
     rows_blocked = false;
     prefill_gemm = false;
     if (frc) {
@@ -2655,8 +2575,7 @@ int mx_engine::prefill_embed(std::vector<Request*>& reqs) {
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data() + i, pos.data() + i, ids.data() + i, m);
     prefill_gemm = true;
-    const int frc = enqueue_forward(m, d_ids, d_pos, d_slot, nullptr, nullptr, false, nullptr, 0, false, nullptr,
-                                    nullptr, nullptr, 0, nullptr, 0, st);
+    const int frc = enqueue_forward({.M = m, .ids = d_ids, .pos = d_pos, .slot = d_slot}, st);
     rows_blocked = false;
     prefill_gemm = false;
     if (frc) {
@@ -2794,8 +2713,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
     launch_spec_draft(spec_ctx, n_ctx, spec_len, spec_par, R, D, d_ids, d_pos, d_slot, spec_ndraft, s);
     // rows of one slot: the plain <= 16-row path, whose q|k|v epilogue stores every row's K/V before the
     // attention launch reads them (rows_distinct stays false)
-    if (int rc = enqueue_forward(M, d_ids, d_pos, d_slot, nullptr, nullptr, true, nullptr, M, false, nullptr, nullptr,
-                                 nullptr, 0, nullptr, 0, s))
+    if (int rc = enqueue_forward({.M = M, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = true, .n_out = M}, s))
       return rc;
     launch_argmax_stage1(logits, n_vocab, M, n_vocab, am_val, am_idx, s);
     launch_spec_accept(am_val, am_idx, R, D, d_ids, d_pos, spec_ndraft, spec_ctx, n_ctx, spec_len, spec_hist, HS,
@@ -2939,8 +2857,11 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   pick_k = dev_chain ? ktop : 0;
   pick_lp = lpk;
   auto step = [&]() -> int {
-    return enqueue_forward(M, d_ids, d_pos, d_slot, nullptr, nullptr, true, nullptr, M, true, d_ids, d_pos,
-                           sched_hist, SCHED_KMAX, sched_hist_count, SCHED_KMAX, s);
+    return enqueue_forward({.M = M, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = true, .n_out = M,
+                            .argmax = true,
+                            .out = {.ids_next = d_ids, .pos_next = d_pos, .hist = sched_hist, .hist_stride = SCHED_KMAX,
+                                    .hist_count = sched_hist_count, .max_hist = SCHED_KMAX}},
+                           s);
   };
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;  // per-round timing on stderr
   const auto t0 = std::chrono::steady_clock::now();
@@ -4041,8 +3962,12 @@ int mx_batch_step(mx_engine* e, mx_batch* b, const void* x_in, void* x_out, void
       mx_engine* e;
       ~Reset() { e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; }
     } reset_flags{e};
-    if (int rc = e->enqueue_forward(b->M, b->d_ids, b->d_pos, b->d_slot, x_in, x_out, head, nullptr, b->M, head,
-                                    b->d_ids, b->d_pos, b->d_hist, b->max_steps, b->d_hist_count, b->max_steps, s))
+    if (int rc = e->enqueue_forward(
+            {.M = b->M, .ids = b->d_ids, .pos = b->d_pos, .slot = b->d_slot, .x_in = x_in, .x_out = x_out, .head = head,
+             .n_out = b->M, .argmax = head,
+             .out = {.ids_next = b->d_ids, .pos_next = b->d_pos, .hist = b->d_hist, .hist_stride = b->max_steps,
+                     .hist_count = b->d_hist_count, .max_hist = b->max_steps}},
+            s))
       return rc;
     if (!head) advance_pos_kernel<<<(b->M + 63) / 64, 64, 0, s>>>(b->d_pos, b->M);
     return 0;
@@ -4205,12 +4130,13 @@ int mx_stage_rows_pick(mx_engine* e, int n, const int32_t* slots, const int32_t*
     e->pick_k = ktop;
     const char* xi = (const char*)x_in;
     char* xo = (char*)x_out;
-    const int frc = e->enqueue_forward(m, e->d_ids, e->d_pos, e->d_slot, xi ? xi + i * xb : nullptr,
-                                       xo ? xo + i * xb : nullptr, no > 0, no ? e->d_rowmap : nullptr, no, false,
-                                       nullptr, nullptr, nullptr, 0, nullptr, 0, s);
+    const int frc = e->enqueue_forward({.M = m, .ids = e->d_ids, .pos = e->d_pos, .slot = e->d_slot,
+                                        .x_in = xi ? xi + i * xb : nullptr, .x_out = xo ? xo + i * xb : nullptr,
+                                        .head = no > 0, .rowmap = no ? e->d_rowmap : nullptr, .n_out = no},
+                                       s);
     e->rows_blocked = false;
     e->prefill_gemm = false;
-    if (!frc && no) e->pick(no, nullptr, nullptr, nullptr, 0, nullptr, 0, s);  // logits rows [no][V]
+    if (!frc && no) e->pick(no, PickOut{}, s);  // logits rows [no][V]
     e->pick_samp = nullptr;
     e->pick_k = 0;
     if (frc) return frc;

@@ -719,7 +719,7 @@ int mx_q8_matmul_probe(int device, const mx_q8_matmul_args* pa) {
     if (int rc = qkv.upload("mx_q8_matmul_probe", p, M, dev, a)) return rc;
   HIPC(hipDeviceSynchronize());
 
-  // the operand, as enqueue_forward_q8's `operand` makes it
+  // the operand, as mx_engine::quant_operand makes it (Q8_0 rows)
   if (act == 2) {
     a.xq = nullptr; a.xf = d_xf; a.norm_w = d_nw; a.np = p.np ? p.np : K / 16;
     if (nol) {
@@ -980,7 +980,7 @@ int mx_kq_matmul_probe(int device, const mx_kq_matmul_args* pa) {
   if (mm && epi == EPI_QKV)
     if (int rc = qkv.upload("mx_kq_matmul_probe", p, M, dev, a)) return rc;
 
-  // the operand, as enqueue_forward_kq's `operand` makes it
+  // the operand, as mx_engine::quant_operand makes it (Q8_K rows)
   int rc = 0;
   const char* who = "";
   if (act == 2) {

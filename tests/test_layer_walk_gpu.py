@@ -1,5 +1,5 @@
 """Every branch of the engine's layer walks (engine.cpp enqueue_forward: the <= 16-row walk, enqueue_forward_wide,
-_q8, _kq, _gemm) against the CPU oracle, through whole two-layer models.
+_quant (Q8_0 / Q4_0 and K-quants), _gemm) against the CPU oracle, through whole two-layer models.
 
 The kernels are tested alone elsewhere; this file tests what the walks decide between them: which operand a GEMV
 gets (normed / quantised on load from the residual stream's sum-of-squares partials, or by a launch), whether
@@ -77,10 +77,10 @@ row 0, whose history the one-sequence chunk run in between had just rewritten.
 
 Mutations tried on scratch copies of engine.cpp (values only; none committed), each run against this file, with the
 first test that failed:
-  enqueue_forward_q8's end-of-walk fold skipped when rowmap is set -> test_picks_of_a_rowmap_subset[q8_0-test-d128-mixed-17]
+  enqueue_forward_quant's end-of-walk fold skipped when rowmap is set (a Q8_0 model) -> test_picks_of_a_rowmap_subset[q8_0-test-d128-mixed-17]
   operand() handed nullptr for the q8 head's rmap -> test_picks_of_a_rowmap_subset[q8_0-test-d128-one-17]
   b.ssq / d.ssq left null on the <= 4-row q8 walk -> test_logits_of_every_row[q8_0-test-d128-distinct-1]
-  nslab not reset after the folding norm in enqueue_forward_kq -> test_logits_of_every_row[q4_k_m-test-d128-distinct-17]
+  nslab not reset after the folding norm in quant_operand (a K-quant model) -> test_logits_of_every_row[q4_k_m-test-d128-distinct-17]
   the rows_distinct tests inverted in enqueue_forward_wide -> test_logits_of_every_row[bf16-test-d128-distinct-4]
     (its 42 history rows of four slots are one wide forward)
   launch_f32_in given a null ssq -> test_hidden_state_in[bf16-test-d128-f32-1]
