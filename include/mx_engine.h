@@ -360,7 +360,7 @@ int mx_pool_probe(int device, int rows, int n, const float* x, const float* w, f
                   const int32_t* seq_begin, int chunk_rows, int pooling, int normalize, float* out);
 
 /* The production attention launchers on caller-supplied q / K / V, no engine (tests on inputs no model
- * produces).  Geometry: head_dim 64 or 128, n_head / n_head_kv in {1, 2, 4, 8}; caches of n_slots slots with
+ * produces).  Geometry: head_dim 64 or 128, n_head / n_head_kv in {1, 2, 4, 5, 6, 7, 8}; caches of n_slots slots with
  * ctx_stride = n_ctx rounded up to 64 positions; M rows (1..4096) at pos[i] in [0, n_ctx] (n_ctx: the kernels
  * clamp it) of slot[i]; scale = 1/sqrt(head_dim).  kcache / vcache: the raw tiled bytes,
  * n_slots * n_head_kv * ctx_stride * head_dim f16 each, copied to the device verbatim and copied back after
@@ -369,10 +369,12 @@ int mx_pool_probe(int device, int rows, int n, const float* x, const float* w, f
  * finishing q/k/v from split-K slabs [nslab][M][(n_head + 2 n_head_kv) * head_dim] (1 <= nslab <= 8, M <= 64,
  * every row its own slot) with rope_cs [n_ctx][head_dim/2][cos, sin] -- it stores each row's K/V into the
  * caches; mode 2: the prefill attention on final q (rows in 16-row blocks of consecutive positions of one
- * slot, a block may end in copies of its last row).  Anything else is MX_ERR_ARG and nothing is launched. */
+ * slot, a block may end in copies of its last row).  bias (mode 1, optional): the q/k/v bias, f32 [(n_head + 2
+ * n_head_kv) * head_dim], added to the summed slabs before RoPE; NULL: none.
+ * Anything else is MX_ERR_ARG and nothing is launched. */
 int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
-                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out);
+                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out, const float* bias);
 
 /* Prefix sharing across KV slots (llama-cpp-python's Llama.set_cache(LlamaRAMCache())), DESIGN.md §12.  Off by
  * default.  On: at admission a request whose prompt shares a longer prefix with the tokens another slot holds
@@ -486,6 +488,7 @@ typedef struct {
   uint64_t slabs_cap;
   int32_t* split_out;
   void* packed_out;
+  const float* bias; /* QKV, optional: f32 [N] added to each finished row sum before RoPE (q/k/v bias); NULL: none */
 } mx_matmul_args;
 int mx_matmul_probe(int device, const mx_matmul_args* a);
 /* The dispatch facts of a bf16 matmul shape, no GPU needed: *kgroups = canon_kgroups(epi, N, K) (the K split
@@ -548,6 +551,7 @@ typedef struct {
   int32_t np; /* leave 0 (np = K / 16, the only value launch_mq8 accepts).  A test hook, not an operand: with act 2 and
                  norm_w, a multiple of 4 in [4, K / 16) is handed to launch_mq8 as MMArgs.np to show that it refuses
                  np * 16 != K; no kernel ever runs with it */
+  const float* bias; /* QKV, optional: f32 [N] added to each finished row sum before RoPE (q/k/v bias); NULL: none */
 } mx_q8_matmul_args;
 int mx_q8_matmul_probe(int device, const mx_q8_matmul_args* a);
 /* The kernel a Q8_0 / Q4_0 shape reaches, no GPU needed (the launchers dispatch on the same host functions).
@@ -623,6 +627,7 @@ typedef struct {
   void* nxq_out;
   float* nxd_out;
   float* nxb_out;
+  const float* bias; /* QKV, optional: f32 [N] added to each finished row sum before RoPE (q/k/v bias); NULL: none */
 } mx_kq_matmul_args;
 int mx_kq_matmul_probe(int device, const mx_kq_matmul_args* a);
 /* The kernel a K-quant shape reaches, no GPU needed: mkq_plan, the function launch_mkq and its sub-launchers

@@ -16,7 +16,8 @@ constexpr float LOG2E = 1.4426950408889634f;
 // the full chunks run the bare MFMA + softmax stream.
 
 // MS: slabs the FIN path loads (>= a.nslab; the ones past a.nslab re-read the last and add zero)
-template <int D, int G, int NW, bool FIN, int MS = ATTN_FIN_MAXSLAB>
+// QB (FIN only): the instance launched with a q/k/v bias
+template <int D, int G, int NW, bool FIN, int MS = ATTN_FIN_MAXSLAB, bool QB = false>
 __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int c) {
   constexpr int CH = ATTN_CHUNK;
   constexpr int QK = D / 32;  // k-steps of QK^T
@@ -79,11 +80,15 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int
       const int dd = i % D;
       const f32x4 csv =
           *reinterpret_cast<const f32x4*>(a.rope_cs + ((size_t)max(0, min(pos, a.n_ctx - 1)) * (D / 2) + dd / 2) * 2);
+      // the q/k/v bias of these rows, issued with the slab loads (QB: this instance runs only with one)
+      f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (QB) bv = *reinterpret_cast<const f32x4*>(a.qkv_bias + row);
       // slab order, as qkv_finish_kernel; the slabs past nslab add exact zeros (a branch per slab
       // would pull its load into the branch again)
       f32x4 v = sv[0];
 #pragma unroll
       for (int k = 1; k < MS; ++k) v += sv[k] * (k < a.nslab ? 1.0f : 0.0f);
+      if constexpr (QB) v += bv;  // on the finished sum, before RoPE: what qs, the K and the V stores below all take
       {  // RoPE (mode NORM: adjacent pairs) on q and k, as selects (a branch would pull csv's load into it)
         const bool rope = i < G * D + D && pos < a.n_ctx;
         const f32x4 s = v;

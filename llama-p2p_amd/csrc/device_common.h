@@ -95,6 +95,13 @@ __device__ __forceinline__ f32x4 qkv_cs(const MMArgs& a, int row, int pos) {
   return *reinterpret_cast<const f32x4*>(a.rope_cs + ((size_t)p * (d / 2) + (rl % d) / 2) * 2);
 }
 
+// The q/k/v bias of rows [row, row+4) (zeros for a model without one: the branch is uniform on a kernel argument).
+// Like the RoPE pairs it depends on the row alone, so the persistent GEMVs fetch it with them.
+__device__ __forceinline__ f32x4 qkv_bias4(const MMArgs& a, int row) {
+  if (!a.qkv_bias) return f32x4{0.f, 0.f, 0.f, 0.f};
+  return *reinterpret_cast<const f32x4*>(a.qkv_bias + row);
+}
+
 // ---------------------------------------------------------------------------
 // RMS_NORM sums of squares, one definition for every kernel that forms them (batch invariance:
 // a row's scale must not depend on which kernel -- RMS_NORM on load at <= 4 rows, norm_kernel at
@@ -161,12 +168,17 @@ __device__ __forceinline__ f32x4 rope4(f32x4 s, f32x4 c) {
   return o;
 }
 
-// q/k/v rows [row, row+4) of token column `col`: RoPE (mode NORM, adjacent pairs) on q and k,
-// q -> f32 buffer, k / v -> the f16 K / V caches (layout above).
+// q/k/v rows [row, row+4) of token column `col`: the bias `b` (qkv_bias4) on the finished sum `s`, RoPE (mode
+// NORM, adjacent pairs) on q and k, q -> f32 buffer, k / v -> the f16 K / V caches (layout above).
+// QB = false: the instance of a kernel that is launched only without a bias (the decode kernels of a model without
+// one are compiled from the code they had before there was a bias: mm_pers_kernel, attn_decode_kernel).
+template <bool QB = true>
 __device__ __forceinline__ void qkv_store_pre(const MMArgs& a, int row, int col, f32x4 s, int pos, int slot,
-                                              f32x4 csv) {
+                                              f32x4 csv, f32x4 b) {
   const int d = a.head_dim;
   if (pos < 0 || pos >= a.n_ctx) return;  // never write outside the slot's KV rows
+  if constexpr (QB)
+    if (a.qkv_bias) s += b;  // not unconditionally: -0 + 0 would turn a model without a bias's -0 into +0
   if (row < a.n_q + a.n_kv) {
     const bool is_q = row < a.n_q;
     const int rl = is_q ? row : row - a.n_q;
@@ -187,7 +199,7 @@ __device__ __forceinline__ void qkv_store_pre(const MMArgs& a, int row, int col,
 }
 __device__ __forceinline__ void qkv_store(const MMArgs& a, int row, int col, f32x4 s) {
   const int pos = a.pos[col], slot = a.slot[col];
-  qkv_store_pre(a, row, col, s, pos, slot, qkv_cs(a, row, pos));
+  qkv_store_pre(a, row, col, s, pos, slot, qkv_cs(a, row, pos), qkv_bias4(a, row));
 }
 
 // One C-layout unit of a finished 16-row tile: rows 16*tile + 4*(l>>4) + i (i < 4) of token

@@ -185,6 +185,7 @@ int kq_recipe_type(int base, int kind, int layer, int n_layer) {  // kind: L_* o
 struct Layer {
   uint16_t *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;
   float *attn_norm = nullptr, *ffn_norm = nullptr;
+  float* qkv_bias = nullptr;  // f32 [n_embd + 2 n_embd_kv] in the packed QKV row order, or nullptr
   KqMat kq_qkv, kq_o, kq_gu, kq_down;  // K-quant model: segments of the four packed matrices
 };
 
@@ -647,6 +648,9 @@ struct mx_engine {
     return gemm_supported(n_embd + 2 * n_embd_kv, n_embd) && gemm_supported(n_embd, n_embd) &&
            gemm_supported(2 * n_ff, n_embd) && gemm_supported(n_embd, n_ff);
   }
+  // launch_mm_wide walks K in chunks of 4 K tiles: a model whose n_embd or n_ff is no multiple of 128 (n_embd 448)
+  // runs its 17..64-row forwards through launch_mm, as it runs its <= 16-row ones
+  bool wide_shapes() const { return n_embd % (4 * TILE_K) == 0 && n_ff % (4 * TILE_K) == 0; }
   bool gemm_ok() const {  // chunks of PREFILL_ROWS rows can run (the Q8_0 / K-quant paths take any row count)
     return wq8 || wkq || gemm_shapes();
   }
@@ -718,7 +722,8 @@ int mx_engine::init_common() {
   if (n_embd > 8192) return fail(MX_ERR_ARG, "n_embd > 8192 is not supported");
   if (n_embd % 64) return fail(MX_ERR_ARG, "n_embd must be a multiple of 64 (RMS_NORM tile partials)");
   const int G = n_head / n_head_kv;
-  if (G != 1 && G != 2 && G != 4 && G != 8) return fail(MX_ERR_ARG, "n_head/n_head_kv must be 1,2,4 or 8");
+  // 5, 6, 7: the Qwen2.5 groups; 3 has no kernel instance and no model that needs one
+  if (G != 1 && G != 2 && (G < 4 || G > 8)) return fail(MX_ERR_ARG, "n_head/n_head_kv must be 1, 2 or 4..8");
   if (n_embd % 32 || n_ff % 32 || n_vocab % 16 || n_embd_kv % 16)
     return fail(MX_ERR_ARG, "n_embd, n_ff must be multiples of 32 and n_vocab, n_embd_kv of 16");
   if (wq8 && (n_embd % Q8_TILE_K || n_ff % Q8_TILE_K))
@@ -1023,28 +1028,32 @@ int mx_engine::load_gguf(const std::string& path) {
   std::string err = f.open(path);
   if (!err.empty()) return fail(MX_ERR_MODEL, err);
   const GGUFValue* arch = f.get("general.architecture");
-  if (!arch || arch->str != "llama") return fail(MX_ERR_MODEL, "general.architecture must be 'llama'");
-  n_embd = (int)f.get_num("llama.embedding_length", 0);
-  n_layer = (int)f.get_num("llama.block_count", 0);
-  n_head = (int)f.get_num("llama.attention.head_count", 0);
-  n_head_kv = (int)f.get_num("llama.attention.head_count_kv", n_head);
-  n_ff = (int)f.get_num("llama.feed_forward_length", 0);
-  eps = (float)f.get_num("llama.attention.layer_norm_rms_epsilon", 1e-5);
-  rope_base = (float)f.get_num("llama.rope.freq_base", 10000.0);
-  n_ctx_train = (int)f.get_num("llama.context_length", 2048);
+  if (!arch || (arch->str != "llama" && arch->str != "qwen2"))
+    return fail(MX_ERR_MODEL, "general.architecture must be 'llama' or 'qwen2', got '" + (arch ? arch->str : "") + "'");
+  const std::string A = arch->str + ".";  // every hyper-parameter is keyed by the architecture
+  // qwen2: NeoX RoPE, run as the kernels' adjacent-pair RoPE on attn_q / attn_k rows permuted at load
+  const bool neox = arch->str == "qwen2";
+  n_embd = (int)f.get_num(A + "embedding_length", 0);
+  n_layer = (int)f.get_num(A + "block_count", 0);
+  n_head = (int)f.get_num(A + "attention.head_count", 0);
+  n_head_kv = (int)f.get_num(A + "attention.head_count_kv", n_head);
+  n_ff = (int)f.get_num(A + "feed_forward_length", 0);
+  eps = (float)f.get_num(A + "attention.layer_norm_rms_epsilon", 1e-5);
+  rope_base = (float)f.get_num(A + "rope.freq_base", 10000.0);
+  n_ctx_train = (int)f.get_num(A + "context_length", 2048);
   bos = (int)f.get_num("tokenizer.ggml.bos_token_id", 1);
   eos = (int)f.get_num("tokenizer.ggml.eos_token_id", 2);
   eot = (int)f.get_num("tokenizer.ggml.eot_token_id", -1);
   const GGUFTensor* te = f.tensor("token_embd.weight");
   if (!te || te->ne.size() != 2) return fail(MX_ERR_MODEL, "missing token_embd.weight");
   n_vocab = (int)te->ne[1];
-  if (!n_embd || !n_layer || !n_head || !n_ff) return fail(MX_ERR_MODEL, "missing llama.* hyper-parameters");
-  if ((int)f.get_num("llama.rope.dimension_count", n_embd / n_head) != n_embd / n_head)
+  if (!n_embd || !n_layer || !n_head || !n_ff) return fail(MX_ERR_MODEL, "missing " + A + "* hyper-parameters");
+  if ((int)f.get_num(A + "rope.dimension_count", n_embd / n_head) != n_embd / n_head)
     return fail(MX_ERR_MODEL, "partial RoPE (rope.dimension_count != head_dim) is not supported");
   {  // RoPE scaling: llama.cpp's "linear" (freq_scale = 1/factor) and Llama-3.1 frequency factors
-    const GGUFValue* st = f.get("llama.rope.scaling.type");
+    const GGUFValue* st = f.get(A + "rope.scaling.type");
     const std::string stype = st ? st->str : "none";
-    const double factor = f.get_num("llama.rope.scaling.factor", 0.0);
+    const double factor = f.get_num(A + "rope.scaling.factor", 0.0);
     if (stype == "linear") {
       if (!(factor > 0)) return fail(MX_ERR_MODEL, "linear RoPE scaling without a positive factor");
       rope_freq_scale = (float)(1.0 / factor);
@@ -1125,6 +1134,29 @@ int mx_engine::load_gguf(const std::string& path) {
       raw_max = std::max(raw_max, (size_t)te->nbytes);
     }
   }
+  // q/k/v biases (qwen2; llama.cpp reads them for llama too): all three of a layer, F32 [h], [kv], [kv], or none
+  std::vector<char> has_bias;
+  {
+    const int b0 = lb < 0 ? 0 : lb, e0 = (le < 0 || le > n_layer) ? n_layer : le;
+    const int hd = n_head ? n_embd / n_head : 0;
+    for (int l = b0; l < e0; l++) {
+      static const char* nm[3] = {"attn_q.bias", "attn_k.bias", "attn_v.bias"};
+      int n = 0;
+      for (int k = 0; k < 3; k++) {
+        const std::string name = "blk." + std::to_string(l) + "." + nm[k];
+        const GGUFTensor* t = f.tensor(name);
+        if (!t) continue;
+        n++;
+        const uint64_t want = k == 0 ? (uint64_t)n_embd : (uint64_t)hd * n_head_kv;
+        if (t->type != 0) return fail(MX_ERR_MODEL, "tensor " + name + " must be F32, got ggml type " + std::to_string(t->type));
+        if (t->ne.size() != 1 || t->ne[0] != want)
+          return fail(MX_ERR_MODEL, "tensor " + name + " must have " + std::to_string(want) + " elements");
+      }
+      if (n != 0 && n != 3)
+        return fail(MX_ERR_MODEL, "blk." + std::to_string(l) + ": attn_q.bias, attn_k.bias and attn_v.bias come together or not at all");
+      has_bias.push_back(n == 3);
+    }
+  }
   if (int rc = init_common()) return rc;
   const int h = n_embd, kv = n_embd_kv, ff = n_ff, V = n_vocab;
   const int mat_type = wq4 ? 2 : wq8 ? 8 : 30;
@@ -1133,10 +1165,16 @@ int mx_engine::load_gguf(const std::string& path) {
   size_t stage_bytes = std::max({(size_t)V * h * 2, (size_t)ff * h * 2, (size_t)(h + 2 * kv) * h * 2});
   uint16_t* stage = nullptr;
   uint8_t* stage_raw = nullptr;
+  uint8_t* stage_perm = nullptr;  // neox: attn_q / attn_k with their rows permuted, what the pack kernels then read
   HIPC(hipMalloc((void**)&stage, stage_bytes));
+  if (neox && hipMalloc((void**)&stage_perm, std::max((size_t)h * h * 2, raw_max)) != hipSuccess) {
+    hipFree(stage);
+    return fail(MX_ERR_HIP, "staging buffer");
+  }
   if (raw_max && (deq || wkq || out_kq_head || (te->type != 30 && !embd_q8))) {
     if (hipMalloc((void**)&stage_raw, raw_max) != hipSuccess) {
       hipFree(stage);
+      if (stage_perm) hipFree(stage_perm);
       return fail(MX_ERR_HIP, "staging buffer");
     }
   }
@@ -1154,6 +1192,7 @@ int mx_engine::load_gguf(const std::string& path) {
     if (amax && (hipMalloc((void**)&lora_a, amax * 4) != hipSuccess || hipMalloc((void**)&lora_b, bmax * 4) != hipSuccess)) {
       hipFree(stage);
       if (stage_raw) hipFree(stage_raw);
+      if (stage_perm) hipFree(stage_perm);
       if (lora_a) hipFree(lora_a);
       return fail(MX_ERR_HIP, "LoRA staging buffers");
     }
@@ -1167,6 +1206,18 @@ int mx_engine::load_gguf(const std::string& path) {
     }
     HIPC(hipMemcpy(stage_raw, f.data(*t), t->nbytes, hipMemcpyHostToDevice));
     if (launch_dequant_bf16(stage, stage_raw, t->type, n, stream)) return fail(MX_ERR_MODEL, "dequantise " + t->name);
+    return 0;
+  };
+  // neox: the row-major image of attn_q / attn_k at `src` (bf16, or the raw blocks of each row) with its rows
+  // permuted into stage_perm; every other tensor, and every tensor of a llama file, is packed from where it is
+  auto qk_rows = [&](const std::string& name, const void* src, int rows, size_t nbytes, const void** out) -> int {
+    *out = src;
+    const size_t n = name.size();
+    const bool qk = n > 14 && (name.compare(n - 14, 14, ".attn_q.weight") == 0 || name.compare(n - 14, 14, ".attn_k.weight") == 0);
+    if (!neox || !qk) return 0;
+    if (nbytes % rows || launch_permute_rows_neox(stage_perm, src, rows, nbytes / rows, head_dim, stream))
+      return fail(MX_ERR_MODEL, "tensor " + name + ": rows cannot be permuted");
+    *out = stage_perm;
     return 0;
   };
   auto get_mat = [&](const std::string& name, int rows, int cols, const GGUFTensor** out, int type) -> int {
@@ -1188,8 +1239,10 @@ int mx_engine::load_gguf(const std::string& path) {
     if (int rc = get_mat(name, rows, cols, &t, mat_type)) return rc;
     if (wq8) {
       HIPC(hipMemcpy(stage, f.data(*t), t->nbytes, hipMemcpyHostToDevice));
-      if (t->type == 2) launch_pack_q4((uint8_t*)dst, (const uint8_t*)stage, rows, cols, mode, offset, stream);
-      else launch_pack_q8((uint8_t*)dst, (const uint8_t*)stage, rows, cols, mode, offset, stream);
+      const void* src = nullptr;
+      if (int rc = qk_rows(name, stage, rows, t->nbytes, &src)) return rc;
+      if (t->type == 2) launch_pack_q4((uint8_t*)dst, (const uint8_t*)src, rows, cols, mode, offset, stream);
+      else launch_pack_q8((uint8_t*)dst, (const uint8_t*)src, rows, cols, mode, offset, stream);
     } else {
       if (int rc = to_bf16(t, (size_t)rows * cols)) return rc;
       if (lora_a) {  // W' = bf16(W + scale B A) on the row-major matrix, before it is packed
@@ -1207,7 +1260,9 @@ int mx_engine::load_gguf(const std::string& path) {
           lora_rank_max = std::max(lora_rank_max, p.r);
         }
       }
-      launch_pack(dst, stage, rows, cols, mode, offset, stream);
+      const void* src = nullptr;  // dequantise -> merge -> permute -> pack: the adapter's B rows are in file order
+      if (int rc = qk_rows(name, stage, rows, (size_t)rows * cols * 2, &src)) return rc;
+      launch_pack(dst, (const uint16_t*)src, rows, cols, mode, offset, stream);
     }
     HIPC(hipStreamSynchronize(stream));
     return 0;
@@ -1226,9 +1281,32 @@ int mx_engine::load_gguf(const std::string& path) {
     if (t->ne.size() != 2 || (int)t->ne[0] != cols || (int)t->ne[1] != rows)
       return fail(MX_ERR_MODEL, "tensor " + name + " has unexpected shape");
     HIPC(hipMemcpy(stage_raw, f.data(*t), t->nbytes, hipMemcpyHostToDevice));
-    if (pack_kq_rows(km, dst, stage_raw, t->type, rows, cols, mode, row0, stream))
+    const void* src = nullptr;
+    if (int rc = qk_rows(name, stage_raw, rows, t->nbytes, &src)) return rc;
+    if (pack_kq_rows(km, dst, (const uint8_t*)src, t->type, rows, cols, mode, row0, stream))
       return fail(MX_ERR_MODEL, "tensor " + name + ": K-quant type does not match its matrix segment");
     HIPC(hipStreamSynchronize(stream));
+    return 0;
+  };
+  // the layer's q|k|v bias as one f32 vector in the packed QKV row order (neox: q and k permuted like their rows)
+  auto upload_bias = [&](int l, Layer& L) -> int {
+    if (!has_bias[l - lb]) return 0;
+    const std::string p = "blk." + std::to_string(l) + ".";
+    std::vector<float> b((size_t)h + 2 * kv);
+    const int off[3] = {0, h, h + kv}, len[3] = {h, kv, kv};
+    static const char* nm[3] = {"attn_q.bias", "attn_k.bias", "attn_v.bias"};
+    for (int k = 0; k < 3; k++) {
+      const float* src = reinterpret_cast<const float*>(f.data(*f.tensor(p + nm[k])));
+      const int d = head_dim;
+      for (int r = 0; r < len[k]; r++) {
+        const int rr = r % d;
+        const int sr = (neox && k < 2) ? r - rr + (rr & 1) * (d / 2) + (rr >> 1) : r;
+        memcpy(&b[off[k] + r], src + sr, 4);
+      }
+    }
+    if (int rc = alloc((void**)&L.qkv_bias, b.size() * 4)) return rc;
+    HIPC(hipMemcpy(L.qkv_bias, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    weight_bytes += b.size() * 4;
     return 0;
   };
   auto kq_layer_types = [&](int l, int t[9]) {
@@ -1288,6 +1366,7 @@ int mx_engine::load_gguf(const std::string& path) {
       if ((rc = alloc_layer_kq(this, L, t))) goto out;
       if ((rc = upload_norm(p + "attn_norm.weight", L.attn_norm))) goto out;
       if ((rc = upload_norm(p + "ffn_norm.weight", L.ffn_norm))) goto out;
+      if ((rc = upload_bias(l, L))) goto out;
       if ((rc = upload_kq(p + "attn_q.weight", h, h, L.kq_qkv, L.qkv, PACK_ROWS, 0))) goto out;
       if ((rc = upload_kq(p + "attn_k.weight", kv, h, L.kq_qkv, L.qkv, PACK_ROWS, h))) goto out;
       if ((rc = upload_kq(p + "attn_v.weight", kv, h, L.kq_qkv, L.qkv, PACK_ROWS, h + kv))) goto out;
@@ -1362,6 +1441,7 @@ int mx_engine::load_gguf(const std::string& path) {
     if ((rc = alloc_layer(this, L))) goto out;
     if ((rc = upload_norm(p + "attn_norm.weight", L.attn_norm))) goto out;
     if ((rc = upload_norm(p + "ffn_norm.weight", L.ffn_norm))) goto out;
+    if ((rc = upload_bias(l, L))) goto out;
     if ((rc = upload_packed(p + "attn_q.weight", h, h, L.qkv, PACK_ROWS, 0))) goto out;
     if ((rc = upload_packed(p + "attn_k.weight", kv, h, L.qkv, PACK_ROWS, h))) goto out;
     if ((rc = upload_packed(p + "attn_v.weight", kv, h, L.qkv, PACK_ROWS, h + kv))) goto out;
@@ -1374,6 +1454,7 @@ out:
   hipStreamSynchronize(stream);
   hipFree(stage);
   if (stage_raw) hipFree(stage_raw);
+  if (stage_perm) hipFree(stage_perm);
   if (lora_a) hipFree(lora_a);
   if (lora_b) hipFree(lora_b);
   return rc;
@@ -1385,6 +1466,7 @@ MMArgs mx_engine::qkv_args(const Layer& L, int li, const Forward& f) const {
   a.out = q; a.ldo = n_embd; a.n_q = n_embd; a.n_kv = n_embd_kv; a.head_dim = head_dim; a.pos = f.pos; a.slot = f.slot;
   a.rope_cs = rope_cs; a.kc = kcache + layer_kv_stride * li; a.vc = vcache + layer_kv_stride * li; a.n_ctx = n_ctx;
   a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv; a.slot_stride = slot_stride;
+  a.qkv_bias = L.qkv_bias;
   return a;
 }
 
@@ -1394,6 +1476,7 @@ AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
   at.ldo = n_embd; at.M = f.M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
   at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
   at.scale = 1.0f / sqrtf((float)head_dim);
+  at.qkv_bias = layers[li].qkv_bias;  // read by the FIN path alone (at.slabs)
   return at;
 }
 
@@ -1404,7 +1487,7 @@ int mx_engine::enqueue_forward(const Forward& f, hipStream_t s) {
   const void* x_in = f.x_in;
   void* x_out = f.x_out;
   const bool head = f.head, argmax = f.argmax;
-  const bool wide = use_wide && M > 16;
+  const bool wide = use_wide && M > 16 && wide_shapes();
   // RMS_NORM applied on load by the consuming GEMV (M <= 16); the residual-stream writers
   // (embedding, attn_output, ffn_down, or ssq_kernel for a stage's x_in) leave per-tile partials
   const bool nol = !wide && !wq8 && !wkq && norm_on_load && mm_can_norm_on_load(M, h);
@@ -4238,10 +4321,12 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
   const int nl = (int)e->layers.size();
   size_t per = 0;
   int launches = 0;
+  const bool wide = M > 16 && e->use_wide && e->wide_shapes();  // the bf16 forward's own choice (enqueue_forward)
   auto one = [&](int li) -> int {
     const Layer& L = e->layers[li];
     MMArgs a{};
     a.M = M;
+    a.qkv_bias = L.qkv_bias;  // read by the EPI_QKV epilogues alone
     if (e->wq8 && kind <= 4) {  // Q8_0 weights: the activations are Q8_0 rows in xq8/xqd
       a.xq = e->xq8; a.xd = e->xqd; a.wq4 = e->wq4;
       // <= 4 rows: the form the decode runs -- the GEMV quantises its operand on load (gate/up and q|k|v
@@ -4327,24 +4412,24 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
         a.ctx_stride = e->ctx_stride;
         a.n_head_kv = e->n_head_kv; a.slot_stride = e->slot_stride;
         per = (size_t)(h + 2 * kv) * h * 2;
-        return (M > 16 && e->use_wide) ? (launch_mm_wide(EPI_QKV, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_QKV, a, s);
+        return wide ?(launch_mm_wide(EPI_QKV, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_QKV, a, s);
       case 1:
         a.W = L.o; a.N = h; a.K = h; a.X = e->attn_out; a.ldx = h; a.out = e->x; a.ldo = h;
         per = (size_t)h * h * 2;
-        return (M > 16 && e->use_wide) ? (launch_mm_wide(EPI_RESID, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_RESID, a, s);
+        return wide ?(launch_mm_wide(EPI_RESID, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_RESID, a, s);
       case 2:
         a.W = L.gu; a.N = 2 * ff; a.K = h; a.X = e->xn; a.ldx = h; a.act = e->act; a.lda = ff;
         per = (size_t)2 * ff * h * 2;
-        return (M > 16 && e->use_wide) ? (launch_mm_wide(EPI_SWIGLU, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_SWIGLU, a, s);
+        return wide ?(launch_mm_wide(EPI_SWIGLU, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_SWIGLU, a, s);
       case 3:
         a.W = L.down; a.N = h; a.K = ff; a.X = e->act; a.ldx = ff; a.out = e->x; a.ldo = h;
         per = (size_t)h * ff * 2;
-        return (M > 16 && e->use_wide) ? (launch_mm_wide(EPI_RESID, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_RESID, a, s);
+        return wide ?(launch_mm_wide(EPI_RESID, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_RESID, a, s);
       case 4:
         if (!e->has_head) return -1;
         a.W = e->output; a.N = e->n_vocab; a.K = h; a.X = e->xn; a.ldx = h; a.out = e->logits; a.ldo = e->n_vocab;
         per = (size_t)e->n_vocab * h * 2;
-        return (M > 16 && e->use_wide) ? (launch_mm_wide(EPI_F32, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_F32, a, s);
+        return wide ?(launch_mm_wide(EPI_F32, a, e->slabs, e->slab_stride, s) < 0) : launch_mm(EPI_F32, a, s);
       case 5:  // qkv with the attention RMSNorm applied on load (M <= 16)
         a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.X = nullptr; a.xf = e->x; a.norm_w = L.attn_norm; a.eps = e->eps;
         a.ssq = e->ssq; a.np = h / 16;
@@ -4373,6 +4458,7 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
         at.pos = e->d_pos; at.slot = e->d_slot; at.out = e->attn_out; at.ldo = h; at.M = M; at.n_head = e->n_head;
         at.n_head_kv = e->n_head_kv; at.head_dim = e->head_dim; at.n_ctx = e->n_ctx; at.ctx_stride = e->ctx_stride;
         at.slot_stride = e->slot_stride; at.scale = 1.0f / sqrtf((float)e->head_dim);
+        at.qkv_bias = L.qkv_bias;
         if (prof_fin) {  // the 32-row decode's form: q/k/v still as 4 split-K slabs, finished here
           at.slabs = e->slabs; at.nslab = 4; at.slab_stride = e->slab_stride; at.rope_cs = e->rope_cs;
           at.kc_w = e->kcache + e->layer_kv_stride * li; at.vc_w = e->vcache + e->layer_kv_stride * li;
@@ -4416,6 +4502,7 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
     at.ldo = h; at.M = M; at.n_head = e->n_head; at.n_head_kv = e->n_head_kv; at.head_dim = e->head_dim;
     at.n_ctx = e->n_ctx; at.ctx_stride = e->ctx_stride; at.slot_stride = e->slot_stride;
     at.scale = 1.0f / sqrtf((float)e->head_dim); at.trace = tr;
+    at.qkv_bias = e->layers[0].qkv_bias;
     if (prof_fin) {
       at.slabs = e->slabs; at.nslab = 4; at.slab_stride = e->slab_stride; at.rope_cs = e->rope_cs;
       at.kc_w = e->kcache; at.vc_w = e->vcache;

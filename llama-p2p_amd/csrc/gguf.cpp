@@ -213,8 +213,13 @@ std::string LoraAdapter::open(const std::string& path, const GGUFFile& base) {
   };
   if (str("general.type") != "adapter") return "LoRA adapter: general.type must be 'adapter', got '" + str("general.type") + "'";
   if (str("adapter.type") != "lora") return "LoRA adapter: adapter.type must be 'lora', got '" + str("adapter.type") + "'";
-  if (str("general.architecture") != "llama")
-    return "LoRA adapter: general.architecture must be 'llama', got '" + str("general.architecture") + "'";
+  {  // the adapter's architecture is the base model's
+    const GGUFValue* ba = base.get("general.architecture");
+    const std::string want = ba && ba->type == T_STRING ? ba->str : std::string();
+    if (str("general.architecture") != want)
+      return "LoRA adapter: general.architecture must be the base model's '" + want + "', got '" +
+             str("general.architecture") + "'";
+  }
   alpha = (float)file.get_num("adapter.lora.alpha", 0.0);
   if (!(alpha == alpha) || alpha - alpha != 0.f) return "LoRA adapter: adapter.lora.alpha is not finite";
   pairs.clear();

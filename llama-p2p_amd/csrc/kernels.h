@@ -33,6 +33,7 @@ enum Epilogue : int {
   EPI_QKV = 2,     // rope(q,k); q -> f32 buffer, k/v -> f16 KV cache (attn_q/k/v)
   EPI_SWIGLU = 3,  // act = bf16(silu(gate) * up); tile = 8 gate + 8 up rows (ffn_gate/ffn_up)
   EPI_SLAB = 4,    // split-K partial: out = slab[ksplit][col][row] (reduced by resid_norm / qkv_finish)
+  EPI_QKV_BIAS = 5,  // template tag only (mm_pers_kernel): EPI_QKV's instance for a launch with a q/k/v bias
 };
 
 struct AttnArgs {
@@ -57,6 +58,9 @@ struct AttnArgs {
   // diagnosis only (mx_profile_kernel with MX_ATTN_TRACE): per (row, kv head, wave) 8 wall-clock
   // stamps (100 MHz) at the kernel's phases; nullptr normally
   unsigned long long* trace;
+  // q/k/v bias (Qwen2): f32 [n_q + 2*n_kv] in the packed QKV row order, added by the FIN path to
+  // the summed slabs before RoPE; nullptr = none
+  const float* qkv_bias;
 };
 
 struct MMArgs {
@@ -109,6 +113,9 @@ struct MMArgs {
   // (canon_kgroups), never by the row count.  mm_wide_kernel: kgrp < 0 = one MFMA chain over the
   // whole K range (no slices): the prefill GEMM's order, for prompt chunks of <= 64 rows
   int kgrp;
+  // EPI_QKV: q/k/v bias, f32 [N] in the packed row order, added to the finished sum before RoPE (ggml_add then
+  // rope); nullptr = none
+  const float* qkv_bias;
 };
 
 
@@ -122,6 +129,10 @@ void launch_synth_rowmajor(uint16_t* dst, size_t n, uint64_t seed, uint64_t tid,
 void launch_synth_norm(float* dst, size_t n, uint64_t seed, uint64_t tid, float scale, hipStream_t s);
 void launch_pack(uint16_t* dst, const uint16_t* src_rowmajor, int N, int K, int mode, int row_offset,
                  hipStream_t s);
+// Qwen2's NeoX RoPE as the kernels' adjacent-pair RoPE: the rows of attn_q / attn_k permuted inside each head of d
+// rows, dst row 2i + j = src row j*d/2 + i (llama.cpp's permute for HF-Llama checkpoints).  Rows are row_bytes
+// contiguous bytes (bf16, or the raw blocks of a row, before they are packed); dst != src.  -1 for bad arguments.
+int launch_permute_rows_neox(void* dst, const void* src, size_t n_rows, size_t row_bytes, int d, hipStream_t s);
 
 // forward-pass ops
 // ssq (optional): per-16-element-tile sums of squares of each embedded row, [M][n_embd/16]

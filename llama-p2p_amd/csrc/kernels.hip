@@ -67,6 +67,35 @@ void launch_synth_packed(uint16_t* dst, int N, int K, uint64_t seed, uint64_t ti
 void launch_pack(uint16_t* dst, const uint16_t* src, int N, int K, int mode, int offset, hipStream_t s) {
   pack_kernel<<<fill_grid((size_t)N * K), 256, 0, s>>>(dst, src, N, K, mode, offset);
 }
+// NeoX -> adjacent-pair row order inside each head of d rows: dst row 2i + j of a head = src row
+// j*d/2 + i, j in {0, 1}.  A row is row_bytes contiguous bytes of any supported type (bf16, or the blocks of that
+// row), moved as T units; grid-stride over the units, so any shape runs and nothing is written past n_rows rows.
+template <typename T>
+__global__ void permute_rows_kernel(T* dst, const T* src, size_t n_rows, size_t row_units, int d) {
+  const size_t total = n_rows * row_units;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / row_units, u = i % row_units;
+    const size_t head = row / d;
+    const int r = (int)(row % d);
+    const size_t srow = head * d + (size_t)(r & 1) * (d / 2) + (r >> 1);
+    dst[i] = src[srow * row_units + u];
+  }
+}
+int launch_permute_rows_neox(void* dst, const void* src, size_t n_rows, size_t row_bytes, int d, hipStream_t s) {
+  if (!dst || !src || dst == src || d < 2 || d % 2 || n_rows % d || row_bytes < 1) return -1;
+  const bool a16 = row_bytes % 16 == 0 && ((uintptr_t)dst | (uintptr_t)src) % 16 == 0;
+  const bool a2 = row_bytes % 2 == 0 && ((uintptr_t)dst | (uintptr_t)src) % 2 == 0;
+  if (a16)
+    permute_rows_kernel<u32x4><<<fill_grid(n_rows * (row_bytes / 16)), 256, 0, s>>>((u32x4*)dst, (const u32x4*)src,
+                                                                                    n_rows, row_bytes / 16, d);
+  else if (a2)  // e.g. a Q8_0 row of 448 columns: 14 blocks of 34 bytes
+    permute_rows_kernel<uint16_t><<<fill_grid(n_rows * (row_bytes / 2)), 256, 0, s>>>(
+        (uint16_t*)dst, (const uint16_t*)src, n_rows, row_bytes / 2, d);
+  else
+    permute_rows_kernel<uint8_t><<<fill_grid(n_rows * row_bytes), 256, 0, s>>>((uint8_t*)dst, (const uint8_t*)src,
+                                                                               n_rows, row_bytes, d);
+  return 0;
+}
 void launch_synth_rowmajor(uint16_t* dst, size_t n, uint64_t seed, uint64_t tid, float scale, hipStream_t s) {
   synth_rowmajor_kernel<<<fill_grid(n), 256, 0, s>>>(dst, n, seed, tid, scale);
 }
@@ -734,8 +763,12 @@ static int launch_mm_cfg(const MMArgs& a0, hipStream_t s) {
 // waves stream tile i+1.  Same epilogues (F32 / RESID + ssq partials / SWIGLU) and the same
 // summation order per tile (K-slices in wave order) as mm_kernel, so results are bit-identical.
 // ---------------------------------------------------------------------------
-template <int KS, int NKW, int TPW, int EPI, int U, bool XS, int KG>
+// EPI_ = EPI_QKV_BIAS: the EPI_QKV instance that is launched with a q/k/v bias (QB); a launch without one runs the
+// EPI_QKV instance, compiled from the code it had before there was a bias
+template <int KS, int NKW, int TPW, int EPI_, int U, bool XS, int KG>
 __global__ __launch_bounds__(64 * KS) void mm_pers_kernel(MMArgs a) {
+  constexpr bool QB = EPI_ == EPI_QKV_BIAS;
+  constexpr int EPI = QB ? (int)EPI_QKV : EPI_;
   static_assert(NKW % U == 0 || (U % NKW == 0 && U / NKW <= TPW), "ring depth vs per-wave K-slice");
   constexpr int XM = XS_MAX_M;
   const int lane = threadIdx.x & 63;
@@ -794,9 +827,11 @@ __global__ __launch_bounds__(64 * KS) void mm_pers_kernel(MMArgs a) {
   int qpos = 0, qslot = 0;
   if constexpr (EPI == EPI_QKV) qpos = a.pos[col], qslot = a.slot[col];
   f32x4 pre[TPW];
+  f32x4 qb[QB ? TPW : 1];  // QB (EPI_QKV, launched with a bias): the q|k|v bias of the tile's rows
   auto prefetch = [&](int i) {
     const int tile = min((int)blockIdx.x + i * G, ntiles - 1);
     if constexpr (EPI == EPI_QKV) pre[i] = qkv_cs(a, tile * 16 + (lane >> 4) * 4, qpos);
+    if constexpr (QB) qb[i] = qkv_bias4(a, tile * 16 + (lane >> 4) * 4);
     if constexpr (EPI == EPI_RESID)
       pre[i] = *reinterpret_cast<const f32x4*>(a.out + (size_t)col * a.ldo + tile * 16 + (lane >> 4) * 4);
   };
@@ -841,7 +876,7 @@ __global__ __launch_bounds__(64 * KS) void mm_pers_kernel(MMArgs a) {
         // per one-token step; profiles/round6_wide_cfg_ab.txt)
         s = up = kfold<KS, (TPW >= 3 ? 3 : KS), KG>([&](int ww) { return rb[ww][l]; }, a.kgrp);
       }
-      if constexpr (EPI == EPI_QKV) qkv_store_pre(a, tile * 16 + (l >> 4) * 4, col_raw, s, qpos, qslot, pre[i]);
+      if constexpr (EPI == EPI_QKV) qkv_store_pre<QB>(a, tile * 16 + (l >> 4) * 4, col_raw, s, qpos, qslot, pre[i], qb[QB ? i : 0]);
       else epi_store<EPI>(a, tile, l, col_raw, s, up);
     }
   };
@@ -879,9 +914,11 @@ static int launch_pers_kg(const MMArgs& a, hipStream_t s) {
     if (a.M > XS_MAX_M || !a.xf || !a.norm_w || !a.ssq || a.np * 16 != a.K || a.np > 512 || NKW * TILE_K > 512)
       return -1;
     const size_t lds = (size_t)KS * XS_MAX_M * (NKW * TILE_K + 8) * 2;
-    mm_pers_kernel<KS, NKW, TPW, EPI, U, true, KG><<<grid, 64 * KS, lds, s>>>(a);
+    if (EPI == EPI_QKV && a.qkv_bias) mm_pers_kernel<KS, NKW, TPW, EPI == EPI_QKV ? (int)EPI_QKV_BIAS : EPI, U, true, KG><<<grid, 64 * KS, lds, s>>>(a);
+    else mm_pers_kernel<KS, NKW, TPW, EPI, U, true, KG><<<grid, 64 * KS, lds, s>>>(a);
   } else {
-    mm_pers_kernel<KS, NKW, TPW, EPI, U, false, KG><<<grid, 64 * KS, 0, s>>>(a);
+    if (EPI == EPI_QKV && a.qkv_bias) mm_pers_kernel<KS, NKW, TPW, EPI == EPI_QKV ? (int)EPI_QKV_BIAS : EPI, U, false, KG><<<grid, 64 * KS, 0, s>>>(a);
+    else mm_pers_kernel<KS, NKW, TPW, EPI, U, false, KG><<<grid, 64 * KS, 0, s>>>(a);
   }
   return 0;
 }
@@ -1377,19 +1414,28 @@ bool mm_can_norm_on_load(int M, int K) {
 #include "attn_body.h"
 namespace mx {
 
-template <int D, int G, int NW, bool FIN, int MS>
+template <int D, int G, int NW, bool FIN, int MS, bool QB>
 __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs a) {
-  attn_decode_body<D, G, NW, FIN, MS>(a, blockIdx.x, blockIdx.y);
+  attn_decode_body<D, G, NW, FIN, MS, QB>(a, blockIdx.x, blockIdx.y);
+}
+// QB: the FIN instance that adds the q/k/v bias; a launch without one runs the instance without
+template <int D, int G, int NW, bool FIN, int MS>
+static void launch_attn_g(const AttnArgs& a, dim3 grid, hipStream_t s) {
+  if (FIN && a.qkv_bias) attn_decode_kernel<D, G, NW, FIN, MS, FIN><<<grid, 64 * NW, 0, s>>>(a);
+  else attn_decode_kernel<D, G, NW, FIN, MS, false><<<grid, 64 * NW, 0, s>>>(a);
 }
 
 template <int D, bool FIN, int NW, int MS = ATTN_FIN_MAXSLAB>
 static void launch_attn_dfw(const AttnArgs& a, hipStream_t s) {
   dim3 grid(a.n_head_kv, a.M);
   switch (a.n_head / a.n_head_kv) {
-    case 1: attn_decode_kernel<D, 1, NW, FIN, MS><<<grid, 64 * NW, 0, s>>>(a); break;
-    case 2: attn_decode_kernel<D, 2, NW, FIN, MS><<<grid, 64 * NW, 0, s>>>(a); break;
-    case 4: attn_decode_kernel<D, 4, NW, FIN, MS><<<grid, 64 * NW, 0, s>>>(a); break;
-    case 8: attn_decode_kernel<D, 8, NW, FIN, MS><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 1: launch_attn_g<D, 1, NW, FIN, MS>(a, grid, s); break;
+    case 2: launch_attn_g<D, 2, NW, FIN, MS>(a, grid, s); break;
+    case 4: launch_attn_g<D, 4, NW, FIN, MS>(a, grid, s); break;
+    case 5: launch_attn_g<D, 5, NW, FIN, MS>(a, grid, s); break;  // Qwen2.5-14B / 32B
+    case 6: launch_attn_g<D, 6, NW, FIN, MS>(a, grid, s); break;  // Qwen2.5-1.5B
+    case 7: launch_attn_g<D, 7, NW, FIN, MS>(a, grid, s); break;  // Qwen2.5-0.5B / 7B
+    case 8: launch_attn_g<D, 8, NW, FIN, MS>(a, grid, s); break;
   }
 }
 
@@ -3112,6 +3158,9 @@ static void launch_attn_prefill_d(const AttnArgs& a, hipStream_t s) {
     case 1: attn_prefill_kernel<D, 1><<<grid, 64, 0, s>>>(a); break;
     case 2: attn_prefill_kernel<D, 2><<<grid, 128, 0, s>>>(a); break;
     case 4: attn_prefill_kernel<D, 4><<<grid, 256, 0, s>>>(a); break;
+    case 5: attn_prefill_kernel<D, 5><<<grid, 320, 0, s>>>(a); break;
+    case 6: attn_prefill_kernel<D, 6><<<grid, 384, 0, s>>>(a); break;
+    case 7: attn_prefill_kernel<D, 7><<<grid, 448, 0, s>>>(a); break;
     case 8: attn_prefill_kernel<D, 8><<<grid, 512, 0, s>>>(a); break;
   }
 }

@@ -1225,7 +1225,7 @@ __device__ __forceinline__ void mkq_pers_body(const MMArgs& a, const uint8_t* Ws
   // one token's q|k|v: pos / slot once, each tile's RoPE pairs when the tile starts (mm_pers_kernel's
   // prefetch: in the epilogue they were a chain of dependent round trips)
   int qpos = 0, qslot = 0;
-  f32x4 qcs[TPW];
+  f32x4 qcs[TPW], qbs[TPW];
   if constexpr (EPI == EPI_QKV && NB == 1) {
     const int c0 = colr[0] < a.M ? colr[0] : a.M - 1;
     qpos = a.pos[c0], qslot = a.slot[c0];
@@ -1244,7 +1244,7 @@ __device__ __forceinline__ void mkq_pers_body(const MMArgs& a, const uint8_t* Ws
         s += rb[ww][n][lane];
         if constexpr (EPI == EPI_SWIGLU) up += rb[ww][n][lane + 32];
       }
-      if constexpr (EPI == EPI_QKV && NB == 1) qkv_store_pre(a, tile * 16 + (lane >> 4) * 4, colr[0], s, qpos, qslot, qcs[i]);
+      if constexpr (EPI == EPI_QKV && NB == 1) qkv_store_pre(a, tile * 16 + (lane >> 4) * 4, colr[0], s, qpos, qslot, qcs[i], qbs[i]);
       else epi_store<EPI>(a, tile, lane, colr[n], s, up);
     }
   };
@@ -1275,6 +1275,7 @@ __device__ __forceinline__ void mkq_pers_body(const MMArgs& a, const uint8_t* Ws
 #pragma unroll
     for (int n = 0; n < NB; ++n) acc[0][n] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (EPI == EPI_QKV && NB == 1) qcs[i] = qkv_cs(a, min(tile_of(i), ntiles - 1) * 16 + (lane >> 4) * 4, qpos);
+    if constexpr (EPI == EPI_QKV && NB == 1) qbs[i] = qkv_bias4(a, min(tile_of(i), ntiles - 1) * 16 + (lane >> 4) * 4);
 #pragma unroll
     for (int k = 0; k < NKW; ++k) {
       const int f = i * NKW + k;

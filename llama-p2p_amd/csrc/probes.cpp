@@ -90,6 +90,13 @@ struct QkvOperand {
     a.n_q = n_q; a.n_kv = n_kv; a.head_dim = p.head_dim; a.pos = d_pos; a.slot = d_slot; a.rope_cs = d_cs;
     a.kc = d_k; a.vc = d_v; a.n_ctx = p.n_ctx; a.ctx_stride = g.ctx_stride; a.n_head_kv = p.n_head_kv;
     a.slot_stride = g.slot_stride;
+    if (p.bias) {  // the q/k/v bias, [n_q + 2 n_kv] = [N]
+      float* d_bias = nullptr;
+      const size_t nb = ((size_t)n_q + 2 * (size_t)n_kv) * 4;
+      if (!dev.alloc(&d_bias, nb)) return fail(MX_ERR_HIP, who + ": device allocation");
+      HIPC(hipMemcpy(d_bias, p.bias, nb, hipMemcpyHostToDevice));
+      a.qkv_bias = d_bias;
+    }
     return 0;
   }
   template <class P>
@@ -301,7 +308,7 @@ int mx_sample_probe(int device, const float* logits_host, int n, int V, int ldl,
 
 int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
-                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out) {
+                       int nslab, const float* rope_cs, void* kcache, void* vcache, void* out, const float* bias) {
   // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
   if (mode < 0 || mode > 2 || !pos || !slot || !kcache || !vcache || !out)
     return fail(MX_ERR_ARG, "mx_attention_probe: mode 0..2, non-null pos / slot / caches / out");
@@ -309,8 +316,9 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
       n_head > 1024)
     return fail(MX_ERR_ARG, "mx_attention_probe: head_dim 64 or 128, n_head a multiple of n_head_kv");
   const int G = n_head / n_head_kv;
-  if (G != 1 && G != 2 && G != 4 && G != 8)
-    return fail(MX_ERR_ARG, "mx_attention_probe: n_head / n_head_kv must be 1, 2, 4 or 8");
+  if (G != 1 && G != 2 && (G < 4 || G > 8))
+    return fail(MX_ERR_ARG, "mx_attention_probe: n_head / n_head_kv must be 1, 2 or 4..8");
+  if (bias && mode != 1) return fail(MX_ERR_ARG, "mx_attention_probe: a bias goes with mode 1 (the slabs)");
   if (n_ctx < 1 || n_ctx > (1 << 20) || n_slots < 1 || n_slots > 4096)
     return fail(MX_ERR_ARG, "mx_attention_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
   if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_attention_probe: 1 <= M <= PREFILL_ROWS rows");
@@ -357,6 +365,12 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
     HIPC(hipMemcpy(d_cs, rope_cs, cs_bytes, hipMemcpyHostToDevice));
     at.slabs = d_slabs; at.nslab = nslab; at.slab_stride = (size_t)M * N; at.rope_cs = d_cs; at.kc_w = d_k;
     at.vc_w = d_v;
+    if (bias) {
+      float* d_bias = nullptr;
+      if (!dev.alloc(&d_bias, N * 4)) return fail(MX_ERR_HIP, "mx_attention_probe: device allocation");
+      HIPC(hipMemcpy(d_bias, bias, N * 4, hipMemcpyHostToDevice));
+      at.qkv_bias = d_bias;
+    }
   } else {
     HIPC(hipMemcpy(d_q, q, (size_t)M * nq * 4, hipMemcpyHostToDevice));
   }

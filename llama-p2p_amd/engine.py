@@ -164,7 +164,8 @@ class MxMatmulArgs(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("n_head", "n_head_kv", "head_dim", "n_ctx", "n_slots")] + \
                [(n, ctypes.c_void_p) for n in ("pos", "slot", "rope_cs", "kcache", "vcache", "resid", "out", "ssq_out",
                                                "slabs_out")] + \
-               [("slabs_cap", ctypes.c_uint64), ("split_out", ctypes.c_void_p), ("packed_out", ctypes.c_void_p)]
+               [("slabs_cap", ctypes.c_uint64), ("split_out", ctypes.c_void_p), ("packed_out", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p)]
 
 
 class MxQ8MatmulArgs(ctypes.Structure):
@@ -178,7 +179,7 @@ class MxQ8MatmulArgs(ctypes.Structure):
                                                "ssq_out", "slabs_out")] + \
                [("slabs_cap", ctypes.c_uint64)] + \
                [(n, ctypes.c_void_p) for n in ("split_out", "packed_out", "xq_out", "xd_out", "x_out", "nxq_out",
-                                               "nxd_out")] + [("np", ctypes.c_int32)]
+                                               "nxd_out")] + [("np", ctypes.c_int32), ("bias", ctypes.c_void_p)]
 
 
 class MxQ8Plan(ctypes.Structure):
@@ -197,7 +198,7 @@ class MxKqMatmulArgs(ctypes.Structure):
                                                "ssq_out", "slabs_out")] + \
                [("slabs_cap", ctypes.c_uint64)] + \
                [(n, ctypes.c_void_p) for n in ("split_out", "packed_out", "xq_out", "xd_out", "xb_out", "nxq_out",
-                                               "nxd_out", "nxb_out")]
+                                               "nxd_out", "nxb_out", "bias")]
 
 
 class MxKqPlan(ctypes.Structure):
@@ -322,7 +323,7 @@ def lib() -> ctypes.CDLL:
         L.mx_forward_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
         L.mx_attention_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
-                                         vp]
+                                         vp, vp]
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
         L.mx_matmul_plan.argtypes = [i32, i32, i32, i32, P(i32), P(i32), P(i32), P(i32)]
         L.mx_norm_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_float, vp, vp]
@@ -559,12 +560,25 @@ def accept_probe(logits, draft, n_draft, pos0, device: int = 0):
 KV_POS_ALIGN = 64  # kernels.h: KV positions per slot are allocated in multiples of this
 
 
+def _set_qkv_bias(a, g: dict, keep: list):
+    """The optional "bias" of a matmul probe's qkv= dict (the q/k/v bias, added to each finished row sum before
+    RoPE) into the argument struct `a`; the array is kept alive in `keep`."""
+    if g.get("bias") is None:
+        return
+    qb = np.ascontiguousarray(g["bias"], dtype=np.float32)
+    if qb.size != (g["n_head"] + 2 * g["n_head_kv"]) * g["head_dim"]:
+        raise ValueError("bias [(n_head + 2 n_head_kv) * head_dim] expected")
+    a.bias = qb.ctypes.data
+    keep.append(qb)
+
+
 def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot,
-                    kcache, vcache, q=None, slabs=None, rope_cs=None, out_f32: bool = True, device: int = 0):
+                    kcache, vcache, q=None, slabs=None, rope_cs=None, out_f32: bool = True, device: int = 0, bias=None):
     """The production attention launchers on caller-supplied q / K / V (no engine; include/mx_engine.h
     mx_attention_probe).  kcache / vcache: the raw tiled f16 bits (uint16) of n_slots x n_head_kv x ctx_stride x
     head_dim elements each, left untouched.  mode 0 / 2: q [M][n_head * head_dim] f32 (decode / prefill
-    kernel); mode 1: slabs [nslab][M][(n_head + 2 n_head_kv) * head_dim] f32 and rope_cs [n_ctx][head_dim/2][2].
+    kernel); mode 1: slabs [nslab][M][(n_head + 2 n_head_kv) * head_dim] f32 and rope_cs [n_ctx][head_dim/2][2],
+    optionally bias [(n_head + 2 n_head_kv) * head_dim] f32 (the q/k/v bias, added to the summed slabs before RoPE).
     Returns (out [M][n_head * head_dim] as f32 -- a bf16 output widened exactly --, kcache after, vcache after)."""
     pos, slot = _i32(pos), _i32(slot)
     M = len(pos)
@@ -589,12 +603,17 @@ def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx
         qa = np.ascontiguousarray(q, dtype=np.float32)
         if qa.size != M * nq:
             raise ValueError("q [M][n_head * head_dim] expected")
+    ba = None
+    if bias is not None:  # mode 1: the q/k/v bias, added to the summed slabs before RoPE
+        ba = np.ascontiguousarray(bias, dtype=np.float32)
+        if ba.size != N:
+            raise ValueError("bias [(n_head + 2 n_head_kv) * head_dim] expected")
     out = np.empty((M, max(nq, 0)), dtype=np.float32 if out_f32 else np.uint16)
     _check(lib().mx_attention_probe(device, mode, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
                                     slot.ctypes.data, int(bool(out_f32)), qa.ctypes.data if qa is not None else None,
                                     sa.ctypes.data if sa is not None else None, nslab,
                                     ca.ctypes.data if ca is not None else None, kc.ctypes.data, vc.ctypes.data,
-                                    out.ctypes.data))
+                                    out.ctypes.data, ba.ctypes.data if ba is not None else None))
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
     return out, kc, vc
@@ -696,8 +715,9 @@ def matmul_probe(path: int, epi: int, w, x=None, *, xf=None, norm_w=None, eps: f
     """A production bf16 matmul launcher on caller-supplied operands (no engine; include/mx_engine.h
     mx_matmul_probe).  w: bf16 bits (uint16) [N][K] in GGUF order; x: bf16 bits [M][K], or xf f32 [M][K] with
     norm_w f32 [K] (RMS_NORM on load); resid f32 [M][N] (RESID); qkv: dict(n_head, n_head_kv, head_dim, n_ctx,
-    n_slots, pos, slot, rope_cs, kcache, vcache) with the caches as in attention_probe.  out (optional): a
-    caller-owned buffer for the [M + 64][ld] result (tests of refusals)."""
+    n_slots, pos, slot, rope_cs, kcache, vcache) with the caches as in attention_probe, and optionally bias (f32
+    [N], the q/k/v bias added to each finished row sum before RoPE; the same key serves q8_matmul_probe and
+    kq_matmul_probe).  out (optional): a caller-owned buffer for the [M + 64][ld] result (tests of refusals)."""
     wa = np.ascontiguousarray(w, dtype=np.uint16)
     N, K = wa.shape
     xa = fa = na = ra = None
@@ -754,6 +774,7 @@ def matmul_probe(path: int, epi: int, w, x=None, *, xf=None, norm_w=None, eps: f
                 raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
             a.rope_cs = cs.ctypes.data
             keep.append(cs)
+        _set_qkv_bias(a, g, keep)
         stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
         elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
         if g.get("kcache") is not None and g.get("vcache") is not None:
@@ -946,6 +967,7 @@ def q8_matmul_probe(path: int, epi: int, w, xf, *, wq4: bool = False, act: int =
                 raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
             a.rope_cs = cs.ctypes.data
             keep.append(cs)
+        _set_qkv_bias(a, g, keep)
         stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
         elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
         if g.get("kcache") is not None and g.get("vcache") is not None:
@@ -1166,6 +1188,7 @@ def kq_matmul_probe(path: int, epi: int, w, xf, segs, *, act: int = 0, N: Option
                 raise ValueError("rope_cs [n_ctx][head_dim/2][2] expected")
             a.rope_cs = cs.ctypes.data
             keep.append(cs)
+        _set_qkv_bias(a, g, keep)
         stride = (max(g["n_ctx"], 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
         elems = max(g["n_slots"], 0) * max(g["n_head_kv"], 0) * stride * max(g["head_dim"], 0)
         if g.get("kcache") is not None and g.get("vcache") is not None:

@@ -456,7 +456,8 @@ def _mixed_type(wtype: str, name: str) -> int:
 def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = None, wtype: str = "bf16",
                          dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None,
                          pooling_type: int = None, eos_token_id: int = 2, eot_token_id: int = None,
-                         merge_lora=None):
+                         merge_lora=None, arch: str = "llama", qkv_bias: float = None, tie_embeddings: bool = False,
+                         qk_rows: str = "norm"):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
     "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
@@ -471,33 +472,47 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     tokenizer.ggml.eot_token_id when given (the end-of-turn token, which ends a request as EOS does) -- the
     defaults leave the file as it always was.  merge_lora: (adapter_path, lora_scale): the matrices the adapter
     (write_lora_gguf) covers are written already merged (lora_merge_bf16 with scale lora_scale * alpha / r, or
-    lora_scale when alpha is 0), after dequant_from where both are given; only for matrices written as BF16."""
+    lora_scale when alpha is 0), after dequant_from where both are given; only for matrices written as BF16.
+    arch: general.architecture and the prefix of every hyper-parameter key ("llama" or "qwen2").  qkv_bias: the
+    std of blk.N.attn_{q,k,v}.bias tensors (F32; synth.synth_bias_f32, 0.0 writes them as zeros), None: none.
+    tie_embeddings: no output.weight (the loader falls back to token_embd.weight).  qk_rows "neox": the rows of
+    attn_q / attn_k (whatever their type: a row gather on the array of values or blocks) and of their biases are
+    written in the inverse of the loader's qwen2 permutation -- file row j*d/2 + i of a head = row 2i + j of the
+    "norm" file -- so a qwen2 loader rebuilds the "norm" file's rows.  The defaults leave every file as it was."""
     from . import synth
+
+    if qk_rows not in ("norm", "neox"):
+        raise ValueError(f"unknown qk_rows {qk_rows!r}")
+    A = arch + "."
+    half = shape.head_dim // 2
+    # file row r of a head <- "norm" row 2 (r % (d/2)) + r // (d/2)
+    neox_idx = lambda n: (np.arange(n) // shape.head_dim * shape.head_dim
+                          + 2 * (np.arange(n) % shape.head_dim % half) + np.arange(n) % shape.head_dim // half)
 
     if wtype not in ("bf16", "q8_0", "q4_0_synth") and wtype not in MIXED:
         raise ValueError(f"unknown wtype {wtype!r}")
     rng = np.random.default_rng(1000 + seed)
 
     w = GGUFWriter(path)
-    w.add_string("general.architecture", "llama")
+    w.add_string("general.architecture", arch)
     w.add_string("general.name", f"synthetic-{shape.name}-seed{seed}")
     w.add_uint32("general.file_type", {"bf16": 32, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q4_0": 2,
                                         "q4_0_synth": 2, "f16": 1}[wtype])  # llama_ftype
-    w.add_uint32("llama.context_length", n_ctx_train or shape.n_ctx_train)
-    w.add_uint32("llama.embedding_length", shape.n_embd)
-    w.add_uint32("llama.block_count", shape.n_layer)
-    w.add_uint32("llama.feed_forward_length", shape.n_ff)
-    w.add_uint32("llama.rope.dimension_count", shape.head_dim)
-    w.add_uint32("llama.attention.head_count", shape.n_head)
-    w.add_uint32("llama.attention.head_count_kv", shape.n_head_kv)
-    w.add_float32("llama.attention.layer_norm_rms_epsilon", shape.eps)
-    w.add_float32("llama.rope.freq_base", shape.rope_base)
+    w.add_uint32(A + "context_length", n_ctx_train or shape.n_ctx_train)
+    w.add_uint32(A + "embedding_length", shape.n_embd)
+    w.add_uint32(A + "block_count", shape.n_layer)
+    w.add_uint32(A + "feed_forward_length", shape.n_ff)
+    w.add_uint32(A + "rope.dimension_count", shape.head_dim)
+    w.add_uint32(A + "attention.head_count", shape.n_head)
+    w.add_uint32(A + "attention.head_count_kv", shape.n_head_kv)
+    w.add_float32(A + "attention.layer_norm_rms_epsilon", shape.eps)
+    w.add_float32(A + "rope.freq_base", shape.rope_base)
     if rope_scaling is not None:
-        w.add_string("llama.rope.scaling.type", rope_scaling[0])
-        w.add_float32("llama.rope.scaling.factor", rope_scaling[1])
+        w.add_string(A + "rope.scaling.type", rope_scaling[0])
+        w.add_float32(A + "rope.scaling.factor", rope_scaling[1])
     if pooling_type is not None:
-        w.add_uint32("llama.pooling_type", pooling_type)
-    w.add_uint32("llama.vocab_size", shape.n_vocab)
+        w.add_uint32(A + "pooling_type", pooling_type)
+    w.add_uint32(A + "vocab_size", shape.n_vocab)
     toks, scores, types = synthetic_spm_vocab(shape.n_vocab)
     w.add_string("tokenizer.ggml.model", "llama")
     w.add_array("tokenizer.ggml.tokens", T_STRING, toks)
@@ -522,6 +537,8 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     if lora is not None and wtype != "bf16" and src is None:
         raise ValueError("merge_lora needs matrices written as BF16 (wtype 'bf16' or dequant_from)")
     for name, kind, arr in synth.synth_tensors(shape, seed):
+        if name == "output.weight" and tie_embeddings:
+            continue
         if name == "token_embd.weight" and embd_type is not None:
             w.add_tensor_info(name, arr.shape, embd_type)
             arrays.append(synth_q8_0_tensor(arr) if embd_type == GGML_Q8_0
@@ -558,6 +575,19 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
         else:
             w.add_tensor_info(name, arr.shape, GGML_BF16 if kind == "bf16" else GGML_F32)
             arrays.append(merged(name, arr) if kind == "bf16" else arr)
+    if qk_rows == "neox":  # a row gather on the values or blocks, [rows][...] in every type
+        for i, info in enumerate(w.tensors):
+            if info[0].endswith((".attn_q.weight", ".attn_k.weight")):
+                arrays[i] = np.ascontiguousarray(arrays[i][neox_idx(arrays[i].shape[0])])
+    if qkv_bias is not None:
+        for l in range(shape.n_layer):
+            for k, (tid, n) in {"q": (synth.L_QB, shape.n_embd), "k": (synth.L_KB, shape.n_embd_kv),
+                                "v": (synth.L_VB, shape.n_embd_kv)}.items():
+                b = synth.synth_bias_f32(seed, synth.layer_tid(l, tid), n, qkv_bias)
+                if qk_rows == "neox" and k != "v":
+                    b = np.ascontiguousarray(b[neox_idx(n)])
+                w.add_tensor_info(f"blk.{l}.attn_{k}.bias", b.shape, GGML_F32)
+                arrays.append(b)
     if rope_freqs is not None:
         rf = np.ascontiguousarray(rope_freqs, dtype=np.float32)
         assert rf.shape == (shape.head_dim // 2,)
@@ -572,16 +602,16 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
 # ne = {n_in, n_out}: T.lora_a, ne = {n_in, r}, row-major A[r][n_in]; T.lora_b, ne = {r, n_out}, row-major
 # B[n_out][r]; W' = W + scale * B A.
 # ---------------------------------------------------------------------------
-def write_lora_gguf(path: str, tensors, alpha: float, dtype: int = GGML_F32):
+def write_lora_gguf(path: str, tensors, alpha: float, dtype: int = GGML_F32, arch: str = "llama"):
     """tensors: {base tensor name: (A[r][n_in], B[n_out][r])}; dtype: GGML_F32, GGML_F16 or GGML_BF16 (the values
-    rounded to it, bf16 by RNE)."""
+    rounded to it, bf16 by RNE); arch: the adapter's general.architecture (the loader wants the base model's)."""
     from . import synth
 
     if dtype not in (GGML_F32, GGML_F16, GGML_BF16):
         raise ValueError("adapter tensors are F32, F16 or BF16")
     w = GGUFWriter(path)
     w.add_string("general.type", "adapter")
-    w.add_string("general.architecture", "llama")
+    w.add_string("general.architecture", arch)
     w.add_string("adapter.type", "lora")
     w.add_float32("adapter.lora.alpha", alpha)
     arrays = []

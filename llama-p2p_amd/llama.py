@@ -131,9 +131,10 @@ class Llama:
         self._check_pooling_type(pooling_type)
         if pooling_type != LLAMA_POOLING_TYPE_UNSPECIFIED:
             return int(pooling_type)
-        md = int(self.metadata.get("llama.pooling_type", LLAMA_POOLING_TYPE_NONE))
+        key = f"{self.metadata.get('general.architecture', 'llama')}.pooling_type"
+        md = int(self.metadata.get(key, LLAMA_POOLING_TYPE_NONE))
         if md not in _POOLING_TYPES:
-            raise ValueError(f"llama.pooling_type = {md} in {self.model_path} is not supported")
+            raise ValueError(f"{key} = {md} in {self.model_path} is not supported")
         return md
 
     @staticmethod

@@ -35,6 +35,7 @@ TID_OUTPUT = 3
 TID_LAYER_BASE = 16
 TID_LAYER_STRIDE = 16
 L_ATTN_NORM, L_Q, L_K, L_V, L_O, L_FFN_NORM, L_GATE, L_UP, L_DOWN = range(9)
+L_QB, L_KB, L_VB = 9, 10, 11  # the q / k / v biases of a Qwen2 layer (GGUF files only: the engine synthesises none)
 
 
 def layer_tid(layer: int, kind: int) -> int:
@@ -141,6 +142,12 @@ def synth_weight_bf16(seed: int, tid: int, n_out: int, n_in: int) -> np.ndarray:
 
 def synth_norm_f32(seed: int, tid: int, n: int) -> np.ndarray:
     return (np.float32(1.0) + synth_values(seed, tid, 0, n, NORM_STD)).astype(np.float32)
+
+
+def synth_bias_f32(seed: int, tid: int, n: int, std: float = 0.3) -> np.ndarray:
+    """A q / k / v bias vector.  std 0.3 is about the size of q / k / v themselves in the test shapes
+    (0.02 sqrt(n_embd)), so a path that drops the bias is off by the whole logit scale."""
+    return synth_values(seed, tid, 0, n, std).astype(np.float32)
 
 
 def synth_tensors(shape: LlamaShape, seed: int):

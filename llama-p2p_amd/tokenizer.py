@@ -27,6 +27,8 @@ TOKEN_NORMAL, TOKEN_UNKNOWN, TOKEN_CONTROL, TOKEN_USER, TOKEN_UNUSED, TOKEN_BYTE
 
 LLAMA3_PRETOKENIZE = (r"(?:'[sS]|'[tT]|'[rR][eE]|'[vV][eE]|'[mM]|'[lL][lL]|'[dD])|[^\r\n\p{L}\p{N}]?\p{L}+|"
                       r"\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+")
+# tokenizer.ggml.pre == "qwen2" (llama.cpp LLAMA_VOCAB_PRE_TYPE_QWEN2): every digit is a word of its own
+QWEN2_PRETOKENIZE = LLAMA3_PRETOKENIZE.replace(r"\p{N}{1,3}", r"\p{N}")
 
 
 def _bytes_to_unicode() -> Dict[int, str]:
@@ -45,12 +47,13 @@ class Tokenizer:
     def __init__(self, tokens: Sequence[str], scores: Optional[Sequence[float]] = None,
                  types: Optional[Sequence[int]] = None, model: str = "llama", merges: Optional[Sequence[str]] = None,
                  bos_id: int = 1, eos_id: int = 2, unk_id: int = 0, add_bos: bool = True,
-                 add_space_prefix: bool = True, eot_id: Optional[int] = None):
+                 add_space_prefix: bool = True, eot_id: Optional[int] = None, pre: Optional[str] = None):
         self.tokens = list(tokens)
         self.n_vocab = len(self.tokens)
         self.scores = list(scores) if scores is not None else [0.0] * self.n_vocab
         self.types = list(types) if types is not None else [TOKEN_NORMAL] * self.n_vocab
         self.model = model
+        self.pre = pre  # tokenizer.ggml.pre: "qwen2" selects its pre-tokeniser, anything else the Llama-3 one
         self.bos_id, self.eos_id, self.unk_id, self.eot_id = bos_id, eos_id, unk_id, eot_id
         self.add_bos = add_bos
         self.add_space_prefix = add_space_prefix
@@ -90,7 +93,7 @@ class Tokenizer:
                    int(md.get("tokenizer.ggml.eos_token_id", 2)), int(md.get("tokenizer.ggml.unknown_token_id", 0)),
                    bool(md.get("tokenizer.ggml.add_bos_token", True)),
                    bool(md.get("tokenizer.ggml.add_space_prefix", model == "llama")),
-                   md.get("tokenizer.ggml.eot_token_id"))
+                   md.get("tokenizer.ggml.eot_token_id"), md.get("tokenizer.ggml.pre"))
 
     # ------------------------------------------------------------- tokenize
     def tokenize(self, text: bytes, add_bos: bool = True, special: bool = False) -> List[int]:
@@ -195,7 +198,7 @@ class Tokenizer:
         if self._re is None:
             import regex
 
-            self._re = regex.compile(LLAMA3_PRETOKENIZE)
+            self._re = regex.compile(QWEN2_PRETOKENIZE if self.pre == "qwen2" else LLAMA3_PRETOKENIZE)
         out = []
         for word in self._re.findall(text):
             out.extend(self._cached(word, self._bpe_word))
