@@ -376,6 +376,18 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
                        int nslab, const float* rope_cs, void* kcache, void* vcache, void* out, const float* bias);
 
+/* Qwen3's per-head q/k RMS_NORM kernels on caller-supplied split-K slabs, no engine.  Geometry,
+ * caches, pos / slot, slabs and rope_cs as mx_attention_probe's mode 1 (M <= 64, every row its own slot); q_norm /
+ * k_norm: f32 [head_dim], in the engine's order (adjacent RoPE pairs).  mode 0: qkn_finish_kernel (slab sum, head
+ * norm, RoPE, q and K/V stores), then the plain decode attention; mode 1: the decode attention finishing the slabs
+ * itself.  q_out [M][n_head * head_dim] f32 (required in mode 0; filled with 0xFF bytes before the launch, written
+ * by mode 0 alone), attn_out the same shape (the attention's f32 output); the caches are copied back after the
+ * launch.  Anything else is MX_ERR_ARG and nothing is launched. */
+int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                 const int32_t* pos, const int32_t* slot, const float* slabs, int nslab, const float* rope_cs,
+                 const float* q_norm, const float* k_norm, float eps, void* kcache, void* vcache, float* q_out,
+                 float* attn_out);
+
 /* Prefix sharing across KV slots (llama-cpp-python's Llama.set_cache(LlamaRAMCache())), DESIGN.md §12.  Off by
  * default.  On: at admission a request whose prompt shares a longer prefix with the tokens another slot holds
  * K/V for -- free or busy, or a request admitted earlier in the same round -- than with its own slot's gets those

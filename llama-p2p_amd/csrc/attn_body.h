@@ -17,7 +17,10 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 // MS: slabs the FIN path loads (>= a.nslab; the ones past a.nslab re-read the last and add zero)
 // QB (FIN only): the instance launched with a q/k/v bias
-template <int D, int G, int NW, bool FIN, int MS = ATTN_FIN_MAXSLAB, bool QB = false>
+// QN (FIN only, never with QB): the instance launched with Qwen3's per-head q/k norm weights.  The
+// slab pass leaves the raw sums in qs and stores V alone; after a barrier wave w normalises heads w, w + NW, ...
+// of the G q heads and the K head in place (qk_norm_rope_head: RMS_NORM, MUL, RoPE) and stores K from there.
+template <int D, int G, int NW, bool FIN, int MS = ATTN_FIN_MAXSLAB, bool QB = false, bool QN = false>
 __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int c) {
   constexpr int CH = ATTN_CHUNK;
   constexpr int QK = D / 32;  // k-steps of QK^T
@@ -60,6 +63,16 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int
   // holding it is patched from LDS in compute(), so a stale read of that position is harmless.
   KV A;
   if (w * CH < ctx) load(A, w);
+  // QN: this lane's RoPE pair and norm weights, issued with the slab loads below (pair l of a head, lanes < D/2)
+  f32x2 ncs = f32x2{1.f, 0.f}, nqw = f32x2{0.f, 0.f}, nkw = f32x2{0.f, 0.f};
+  if constexpr (QN) {
+    static_assert(FIN && !QB, "the head norm runs in the FIN path, and no model has it beside a bias");
+    if (lane < D / 2) {
+      ncs = *reinterpret_cast<const f32x2*>(a.rope_cs + ((size_t)max(0, min(pos, a.n_ctx - 1)) * (D / 2) + lane) * 2);
+      nqw = *reinterpret_cast<const f32x2*>(a.q_norm + 2 * lane);
+      nkw = *reinterpret_cast<const f32x2*>(a.k_norm + 2 * lane);
+    }
+  }
 
   // wide path: q/k/v of this (kv head, token) are still split-K partial slabs -- sum them in slab
   // order (bit-identical to qkv_finish_kernel), RoPE q and k, write this position's K and V into
@@ -89,7 +102,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int
 #pragma unroll
       for (int k = 1; k < MS; ++k) v += sv[k] * (k < a.nslab ? 1.0f : 0.0f);
       if constexpr (QB) v += bv;  // on the finished sum, before RoPE: what qs, the K and the V stores below all take
-      {  // RoPE (mode NORM: adjacent pairs) on q and k, as selects (a branch would pull csv's load into it)
+      if constexpr (!QN) {  // RoPE (mode NORM: adjacent pairs) on q and k, as selects (a branch would pull csv's load into it)
         const bool rope = i < G * D + D && pos < a.n_ctx;
         const f32x4 s = v;
         const f32x4 rv = rope4(s, csv);
@@ -100,8 +113,10 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int
       if (i >= G * D && pos < a.n_ctx) {
         const size_t sb = (size_t)slot * a.slot_stride;
         if (i < G * D + D) {
+          if constexpr (!QN) {
           _Float16* kp = a.kc_w + sb + (size_t)kvh * a.ctx_stride * D + kv_k_off(pos, dd, D);
           *reinterpret_cast<f16x4*>(kp) = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+          }
         } else {
           _Float16* vh = a.vc_w + sb + (size_t)kvh * a.ctx_stride * D;
 #pragma unroll
@@ -110,6 +125,20 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, int kvh, int
       }
     }
     __syncthreads();
+    if constexpr (QN) {
+      for (int hd = w; hd < G + 1; hd += NW) {  // wave-uniform: heads 0..G-1 are q, head G is this position's K
+        float* hp = qs + hd * D + 2 * lane;
+        const f32x2 raw = lane < D / 2 ? *reinterpret_cast<const f32x2*>(hp) : f32x2{0.f, 0.f};
+        const f32x2 o = qk_norm_rope_head<D>(raw, hd < G ? nqw : nkw, ncs, a.qk_eps);
+        if (lane < D / 2) {
+          *reinterpret_cast<f32x2*>(hp) = o;
+          if (hd == G && pos < a.n_ctx)
+            *reinterpret_cast<f16x2*>(a.kc_w + (size_t)slot * a.slot_stride + (size_t)kvh * a.ctx_stride * D +
+                                      kv_k_off(pos, 2 * lane, D)) = f16x2{(_Float16)o[0], (_Float16)o[1]};
+        }
+      }
+      __syncthreads();
+    }
   }
 
   // A operand of QK^T: rows = heads of the group (rows >= G are zero)

@@ -168,6 +168,31 @@ __device__ __forceinline__ f32x4 rope4(f32x4 s, f32x4 c) {
   return o;
 }
 
+// Qwen3's per-head RMS_NORM + MUL + RoPE: one wave owns one head of one token.  Lane l < D/2 holds
+// the adjacent pair v = (x[2l], x[2l+1]) -- one RoPE pair after the load-time permutation --, its norm weights w
+// and its (cos, sin) cs; lanes >= D/2 (D = 64) must pass v = 0 and their result means nothing.  Sum of squares as
+// ssq4 forms it (each square rounded to f32, accumulated in double), pair first, then ssq_wave's fixed xor
+// butterfly over the 64 lanes (the idle half adds exact zeros): the order depends on D alone.  Then ggml's
+// RMS_NORM (x * scale) and MUL (* w) in f32 and rope4's scalar-fma RoPE behind the same opq fences.  Every caller
+// (the decode attention's FIN path, qkn_finish_kernel) goes through here, so their q and K bits are equal.
+template <int D>
+__device__ __forceinline__ f32x2 qk_norm_rope_head(f32x2 v, f32x2 w, f32x2 cs, float eps) {
+  static_assert(D == 64 || D == 128, "one wave holds a head as adjacent pairs");
+  double q;
+  {
+#pragma clang fp contract(off)
+    q = (double)(v[0] * v[0]);
+    q += (double)(v[1] * v[1]);
+  }
+  const float scale = rms_scale(ssq_wave(q), D, eps);
+  const float n0 = opq((v[0] * scale) * w[0]), n1 = opq((v[1] * scale) * w[1]);
+  const float c0 = opq(cs[0]), c1 = opq(cs[1]);
+  f32x2 o;
+  o[0] = opq(__builtin_fmaf(n0, c0, -(n1 * c1)));
+  o[1] = opq(__builtin_fmaf(n0, c1, n1 * c0));
+  return o;
+}
+
 // q/k/v rows [row, row+4) of token column `col`: the bias `b` (qkv_bias4) on the finished sum `s`, RoPE (mode
 // NORM, adjacent pairs) on q and k, q -> f32 buffer, k / v -> the f16 K / V caches (layout above).
 // QB = false: the instance of a kernel that is launched only without a bias (the decode kernels of a model without
@@ -206,7 +231,7 @@ __device__ __forceinline__ void qkv_store(const MMArgs& a, int row, int col, f32
 // column `col`.  SWIGLU tiles hold 8 gate rows (lanes 0-31) and the matching up rows (lanes l+32).
 template <int EPI>
 __device__ __forceinline__ void epi_store(const MMArgs& a, int tile, int l, int col, f32x4 s, f32x4 up) {
-  if constexpr (EPI == EPI_F32 || EPI == EPI_SLAB) {
+  if constexpr (EPI == EPI_F32 || EPI == EPI_SLAB || EPI == EPI_QKV_RAW) {
     const int row = tile * 16 + (l >> 4) * 4;
     *reinterpret_cast<f32x4*>(a.out + (size_t)col * a.ldo + row) = s;
   } else if constexpr (EPI == EPI_RESID) {

@@ -186,6 +186,7 @@ struct Layer {
   uint16_t *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;
   float *attn_norm = nullptr, *ffn_norm = nullptr;
   float* qkv_bias = nullptr;  // f32 [n_embd + 2 n_embd_kv] in the packed QKV row order, or nullptr
+  float *q_norm = nullptr, *k_norm = nullptr;  // Qwen3: f32 [head_dim] each, permuted like a head's rows, or nullptr (§19)
   KqMat kq_qkv, kq_o, kq_gu, kq_down;  // K-quant model: segments of the four packed matrices
 };
 
@@ -643,6 +644,7 @@ struct mx_engine {
   // what every walk's q|k|v GEMV and attention launch of layer li share; the walk adds its operand and outputs
   MMArgs qkv_args(const Layer& L, int li, const Forward& f) const;
   AttnArgs attn_args(int li, const Forward& f) const;
+  void finish_raw_qkv(const MMArgs& a, AttnArgs& at, const float* raw, int nslab, size_t stride, hipStream_t s) const;
   int enqueue_forward_gemm(const Forward& f, hipStream_t s);
   bool gemm_shapes() const {  // the bf16 prefill GEMM takes every matrix of a layer
     return gemm_supported(n_embd + 2 * n_embd_kv, n_embd) && gemm_supported(n_embd, n_embd) &&
@@ -1028,11 +1030,12 @@ int mx_engine::load_gguf(const std::string& path) {
   std::string err = f.open(path);
   if (!err.empty()) return fail(MX_ERR_MODEL, err);
   const GGUFValue* arch = f.get("general.architecture");
-  if (!arch || (arch->str != "llama" && arch->str != "qwen2"))
-    return fail(MX_ERR_MODEL, "general.architecture must be 'llama' or 'qwen2', got '" + (arch ? arch->str : "") + "'");
+  if (!arch || (arch->str != "llama" && arch->str != "qwen2" && arch->str != "qwen3"))
+    return fail(MX_ERR_MODEL, "general.architecture must be 'llama' or 'qwen2' or 'qwen3', got '" + (arch ? arch->str : "") + "'");
   const std::string A = arch->str + ".";  // every hyper-parameter is keyed by the architecture
   // qwen2: NeoX RoPE, run as the kernels' adjacent-pair RoPE on attn_q / attn_k rows permuted at load
-  const bool neox = arch->str == "qwen2";
+  const bool neox = arch->str == "qwen2" || arch->str == "qwen3";
+  const bool qwen3 = arch->str == "qwen3";  // + per-head q/k RMS_NORM before RoPE, no q/k/v bias
   n_embd = (int)f.get_num(A + "embedding_length", 0);
   n_layer = (int)f.get_num(A + "block_count", 0);
   n_head = (int)f.get_num(A + "attention.head_count", 0);
@@ -1048,6 +1051,12 @@ int mx_engine::load_gguf(const std::string& path) {
   if (!te || te->ne.size() != 2) return fail(MX_ERR_MODEL, "missing token_embd.weight");
   n_vocab = (int)te->ne[1];
   if (!n_embd || !n_layer || !n_head || !n_ff) return fail(MX_ERR_MODEL, "missing " + A + "* hyper-parameters");
+  for (const char* key : {"attention.key_length", "attention.value_length"}) {
+    const int len = (int)f.get_num(A + key, n_embd / n_head);
+    if (len != n_embd / n_head)
+      return fail(MX_ERR_MODEL, A + key + " " + std::to_string(len) + " differs from n_embd / n_head = " +
+                                    std::to_string(n_embd / n_head) + ": not supported (Qwen3-0.6B, 4B and 32B)");
+  }
   if ((int)f.get_num(A + "rope.dimension_count", n_embd / n_head) != n_embd / n_head)
     return fail(MX_ERR_MODEL, "partial RoPE (rope.dimension_count != head_dim) is not supported");
   {  // RoPE scaling: llama.cpp's "linear" (freq_scale = 1/factor) and Llama-3.1 frequency factors
@@ -1135,7 +1144,7 @@ int mx_engine::load_gguf(const std::string& path) {
     }
   }
   // q/k/v biases (qwen2; llama.cpp reads them for llama too): all three of a layer, F32 [h], [kv], [kv], or none
-  std::vector<char> has_bias;
+  std::vector<char> has_bias, has_qk_norm;
   {
     const int b0 = lb < 0 ? 0 : lb, e0 = (le < 0 || le > n_layer) ? n_layer : le;
     const int hd = n_head ? n_embd / n_head : 0;
@@ -1155,6 +1164,23 @@ int mx_engine::load_gguf(const std::string& path) {
       if (n != 0 && n != 3)
         return fail(MX_ERR_MODEL, "blk." + std::to_string(l) + ": attn_q.bias, attn_k.bias and attn_v.bias come together or not at all");
       has_bias.push_back(n == 3);
+      // per-head q/k norm weights: both, F32 [head_dim]; a qwen3 file must have them, and never beside a bias
+      int nn = 0;
+      for (const char* nmw : {"attn_q_norm.weight", "attn_k_norm.weight"}) {
+        const std::string name = "blk." + std::to_string(l) + "." + nmw;
+        const GGUFTensor* t = f.tensor(name);
+        if (!t) continue;
+        nn++;
+        if (t->type != 0 || t->ne.size() != 1 || t->ne[0] != (uint64_t)hd)
+          return fail(MX_ERR_MODEL, "tensor " + name + " must be F32 [head_dim]");
+      }
+      if (nn == 1 || (qwen3 && nn != 2))
+        return fail(MX_ERR_MODEL, "blk." + std::to_string(l) + ": attn_q_norm.weight and attn_k_norm.weight " +
+                                      (qwen3 ? "are required by qwen3" : "come together or not at all"));
+      if (nn && n)
+        return fail(MX_ERR_MODEL, "blk." + std::to_string(l) + ": q/k norm weights beside a q/k/v bias are not supported");
+      if (nn && hd != 64 && hd != 128) return fail(MX_ERR_MODEL, "q/k norm weights need head_dim 64 or 128");
+      has_qk_norm.push_back(nn == 2);
     }
   }
   if (int rc = init_common()) return rc;
@@ -1309,6 +1335,22 @@ int mx_engine::load_gguf(const std::string& path) {
     weight_bytes += b.size() * 4;
     return 0;
   };
+  // the layer's q / k head-norm weights, permuted inside the head like the rows of attn_q / attn_k (neox)
+  auto upload_qk_norm = [&](int l, Layer& L) -> int {
+    if (!has_qk_norm[l - lb]) return 0;
+    const int d = head_dim;
+    std::vector<float> w(d);
+    float** dst[2] = {&L.q_norm, &L.k_norm};
+    static const char* nm[2] = {"attn_q_norm.weight", "attn_k_norm.weight"};
+    for (int k = 0; k < 2; k++) {
+      const float* src = reinterpret_cast<const float*>(f.data(*f.tensor("blk." + std::to_string(l) + "." + nm[k])));
+      for (int r = 0; r < d; r++) memcpy(&w[r], src + (neox ? (r & 1) * (d / 2) + (r >> 1) : r), 4);
+      if (int rc = alloc((void**)dst[k], (size_t)d * 4)) return rc;
+      HIPC(hipMemcpy(*dst[k], w.data(), (size_t)d * 4, hipMemcpyHostToDevice));
+      weight_bytes += (size_t)d * 4;
+    }
+    return 0;
+  };
   auto kq_layer_types = [&](int l, int t[9]) {
     const std::string p = "blk." + std::to_string(l) + ".";
     static const char* nm[9] = {nullptr, "attn_q", "attn_k", "attn_v", "attn_output", nullptr, "ffn_gate", "ffn_up", "ffn_down"};
@@ -1367,6 +1409,7 @@ int mx_engine::load_gguf(const std::string& path) {
       if ((rc = upload_norm(p + "attn_norm.weight", L.attn_norm))) goto out;
       if ((rc = upload_norm(p + "ffn_norm.weight", L.ffn_norm))) goto out;
       if ((rc = upload_bias(l, L))) goto out;
+      if ((rc = upload_qk_norm(l, L))) goto out;
       if ((rc = upload_kq(p + "attn_q.weight", h, h, L.kq_qkv, L.qkv, PACK_ROWS, 0))) goto out;
       if ((rc = upload_kq(p + "attn_k.weight", kv, h, L.kq_qkv, L.qkv, PACK_ROWS, h))) goto out;
       if ((rc = upload_kq(p + "attn_v.weight", kv, h, L.kq_qkv, L.qkv, PACK_ROWS, h + kv))) goto out;
@@ -1442,6 +1485,7 @@ int mx_engine::load_gguf(const std::string& path) {
     if ((rc = upload_norm(p + "attn_norm.weight", L.attn_norm))) goto out;
     if ((rc = upload_norm(p + "ffn_norm.weight", L.ffn_norm))) goto out;
     if ((rc = upload_bias(l, L))) goto out;
+    if ((rc = upload_qk_norm(l, L))) goto out;
     if ((rc = upload_packed(p + "attn_q.weight", h, h, L.qkv, PACK_ROWS, 0))) goto out;
     if ((rc = upload_packed(p + "attn_k.weight", kv, h, L.qkv, PACK_ROWS, h))) goto out;
     if ((rc = upload_packed(p + "attn_v.weight", kv, h, L.qkv, PACK_ROWS, h + kv))) goto out;
@@ -1467,6 +1511,7 @@ MMArgs mx_engine::qkv_args(const Layer& L, int li, const Forward& f) const {
   a.rope_cs = rope_cs; a.kc = kcache + layer_kv_stride * li; a.vc = vcache + layer_kv_stride * li; a.n_ctx = n_ctx;
   a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv; a.slot_stride = slot_stride;
   a.qkv_bias = L.qkv_bias;
+  a.q_norm = L.q_norm; a.k_norm = L.k_norm; a.qk_eps = eps;
   return a;
 }
 
@@ -1477,7 +1522,20 @@ AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
   at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
   at.scale = 1.0f / sqrtf((float)head_dim);
   at.qkv_bias = layers[li].qkv_bias;  // read by the FIN path alone (at.slabs)
+  at.q_norm = layers[li].q_norm; at.k_norm = layers[li].k_norm; at.qk_eps = eps;
   return at;
+}
+
+// q|k|v of a layer with q/k norm weights, still raw in `raw` ([nslab][M][N]): rows that are each their own slot
+// (<= MAX_ROWS of them) leave it to the attention's FIN path -- no launch here --, rows that attend to each
+// other's new K/V take qkn_finish_kernel first.  a: qkv_args (q buffer, caches).
+void mx_engine::finish_raw_qkv(const MMArgs& a, AttnArgs& at, const float* raw, int nslab, size_t stride,
+                               hipStream_t s) const {
+  if (rows_distinct && a.M <= MAX_ROWS) {
+    at.slabs = raw; at.nslab = nslab; at.slab_stride = stride; at.rope_cs = rope_cs; at.kc_w = a.kc; at.vc_w = a.vc;
+  } else {
+    launch_qkv_finish(a, raw, nslab, stride, s);
+  }
 }
 
 // One forward of M <= MAX_ROWS rows through this stage's layers.
@@ -1542,9 +1600,15 @@ int mx_engine::enqueue_forward(const Forward& f, hipStream_t s) {
     norm_operand(a, L.attn_norm, true);
     AttnArgs at = attn_args(li, f);
     at.out = attn_out;
-    const bool pers_qkv = use_pers && a.X == nullptr && mm_pers_supported(EPI_QKV, M, a.N, h);
-    if ((pers_qkv ? launch_mm_pers(EPI_QKV, a, s) : -1) != 0 && launch_mm(EPI_QKV, a, s))
+    const bool pers_qkv = use_pers && a.X == nullptr && !L.q_norm && mm_pers_supported(EPI_QKV, M, a.N, h);
+    if (L.q_norm) {  // raw sums as one slab (EPI_QKV's K grouping; the persistent form has no raw epilogue)
+      MMArgs r = a;
+      r.out = slabs; r.ldo = a.N;
+      if (launch_mm(EPI_QKV_RAW, r, s)) return fail(MX_ERR_ARG, "qkv launch shape");
+      finish_raw_qkv(a, at, slabs, 1, slab_stride, s);
+    } else if ((pers_qkv ? launch_mm_pers(EPI_QKV, a, s) : -1) != 0 && launch_mm(EPI_QKV, a, s)) {
       return fail(MX_ERR_ARG, "qkv launch shape");
+    }
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.X = attn_out; b.ldx = h; b.M = M; b.out = x; b.ldo = h;
     if (use_pers && nol && mm_pers_supported(EPI_SWIGLU, M, 2 * ff, h)) {  // partials for gate/up's norm on load
@@ -1766,7 +1830,17 @@ int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
     AttnArgs at = attn_args(li, f);
     at.outf = attn_f;
     const int qs = qkv_slab(a);
-    if (qs > 0 && rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
+    if (L.q_norm) {  // no EPI_QKV epilogue can apply the head norm: split-K slabs, or the GEMV's sums raw as one slab
+      float* raw = M <= MAX_ROWS ? slabs : gslabs;
+      if (qs <= 0) {
+        if (!raw || (M > MAX_ROWS && (size_t)M * a.N > GSLAB_FLOATS))
+          return fail(MX_ERR_ARG, fmt + " qkv of " + std::to_string(M) + " rows with q/k norm weights: no slab space");
+        MMArgs r = a;
+        r.out = raw; r.ldo = a.N;
+        if (mm(EPI_F32, r)) return fail(MX_ERR_ARG, fmt + " qkv launch shape");
+      }
+      finish_raw_qkv(a, at, qs > 0 ? slabs : raw, qs > 0 ? qs : 1, slab_stride, s);
+    } else if (qs > 0 && rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
       at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
       at.vc_w = a.vc;
     } else if (qs > 0) {

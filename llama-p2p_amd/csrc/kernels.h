@@ -34,6 +34,8 @@ enum Epilogue : int {
   EPI_SWIGLU = 3,  // act = bf16(silu(gate) * up); tile = 8 gate + 8 up rows (ffn_gate/ffn_up)
   EPI_SLAB = 4,    // split-K partial: out = slab[ksplit][col][row] (reduced by resid_norm / qkv_finish)
   EPI_QKV_BIAS = 5,  // template tag only (mm_pers_kernel): EPI_QKV's instance for a launch with a q/k/v bias
+  EPI_QKV_RAW = 6,   // launch_mm: q|k|v sums left raw, out[col][row] = acc in EPI_QKV's canonical K grouping -- one
+                     // slab for the attention's FIN path or launch_qkv_finish (a layer with q/k norm weights, §19)
 };
 
 struct AttnArgs {
@@ -61,6 +63,11 @@ struct AttnArgs {
   // q/k/v bias (Qwen2): f32 [n_q + 2*n_kv] in the packed QKV row order, added by the FIN path to
   // the summed slabs before RoPE; nullptr = none
   const float* qkv_bias;
+  // Qwen3's per-head RMS_NORM weights: f32 [head_dim] each, in the engine's (permuted) order, applied
+  // by the FIN path to every q head and the K head between the slab sum and RoPE; nullptr = none
+  const float* q_norm;
+  const float* k_norm;
+  float qk_eps;
 };
 
 struct MMArgs {
@@ -116,6 +123,11 @@ struct MMArgs {
   // EPI_QKV: q/k/v bias, f32 [N] in the packed row order, added to the finished sum before RoPE (ggml_add then
   // rope); nullptr = none
   const float* qkv_bias;
+  // EPI_QKV: Qwen3's per-head RMS_NORM weights, f32 [head_dim] each.  No GEMV epilogue can apply them
+  // (a head is spread over several tiles): launch_qkv_finish reads them, the epilogues are not run with them
+  const float* q_norm;
+  const float* k_norm;
+  float qk_eps;
 };
 
 

@@ -581,6 +581,9 @@ __device__ __forceinline__ f32x4 kfold(const F& get, int kgrp) {
 // gate/up and the lm_head never split K in their 17..64-row launches: one canonical group
 template <int EPI>
 constexpr int epi_kg() { return (EPI == EPI_SWIGLU || EPI == EPI_F32) ? 1 : 0; }
+// the shape's canonical K grouping is a function of the operation: raw q|k|v sums fold as EPI_QKV's do
+template <int EPI>
+constexpr int epi_canon() { return EPI == EPI_QKV_RAW ? (int)EPI_QKV : EPI; }
 
 template <int KS, int RT, int NB, int EPI, int U, bool XS>
 __device__ __forceinline__ void mm_body(const MMArgs& a, int tile0) {
@@ -723,7 +726,7 @@ __global__ __launch_bounds__(64 * KS) void mm_kernel(MMArgs a) {
 template <int KS, int RT, int EPI, int U>
 static int launch_mm_cfg(const MMArgs& a0, hipStream_t s) {
   MMArgs a = a0;
-  a.kgrp = canon_kgroups(EPI, a.N, a.K);
+  a.kgrp = canon_kgroups(epi_canon<EPI>(), a.N, a.K);
   const int nb = (a.M + 15) / 16;
   if ((a.N / TILE_N) % RT) return -1;
   const int grid = a.N / (16 * RT);
@@ -1008,6 +1011,7 @@ int launch_mm(int epi, const MMArgs& a, hipStream_t s) {
       case EPI_QKV:  // 16 waves = the 16 canonical K slices (round 1's 8-wave norm-on-load groups,
                      // profiles/round1_xs_probe.txt, folded two slices per wave: not batch-invariant)
         return launch_mm_cfg<16, 1, EPI_QKV, 4>(a, s);
+      case EPI_QKV_RAW: return launch_mm_cfg<16, 1, EPI_QKV_RAW, 4>(a, s);  // EPI_QKV's geometry at every row count
       case EPI_SWIGLU: return launch_mm_cfg<16, 1, EPI_SWIGLU, 4>(a, s);
     }
     return -1;
@@ -1019,6 +1023,8 @@ int launch_mm(int epi, const MMArgs& a, hipStream_t s) {
       case EPI_RESID: return launch_mm_cfg<4, 1, EPI_RESID, 8>(a, s);
       case EPI_QKV:
         return ntiles % 2 == 0 ? launch_mm_cfg<8, 2, EPI_QKV, 8>(a, s) : launch_mm_cfg<8, 1, EPI_QKV, 8>(a, s);
+      case EPI_QKV_RAW:
+        return ntiles % 2 == 0 ? launch_mm_cfg<8, 2, EPI_QKV_RAW, 8>(a, s) : launch_mm_cfg<8, 1, EPI_QKV_RAW, 8>(a, s);
       case EPI_SWIGLU:
         return ntiles % 4 == 0 ? launch_mm_cfg<4, 4, EPI_SWIGLU, 4>(a, s) : launch_mm_cfg<4, 1, EPI_SWIGLU, 8>(a, s);
     }
@@ -1030,6 +1036,8 @@ int launch_mm(int epi, const MMArgs& a, hipStream_t s) {
     case EPI_RESID: return launch_mm_cfg<4, 1, EPI_RESID, 8>(a, s);
     case EPI_QKV:
       return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_QKV, 4>(a, s) : launch_mm_cfg<4, 1, EPI_QKV, 4>(a, s);
+    case EPI_QKV_RAW:
+      return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_QKV_RAW, 4>(a, s) : launch_mm_cfg<4, 1, EPI_QKV_RAW, 4>(a, s);
     case EPI_SWIGLU:
       return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_SWIGLU, 4>(a, s) : launch_mm_cfg<4, 1, EPI_SWIGLU, 4>(a, s);
   }
@@ -1255,7 +1263,62 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(MMArgs a, const float* 
   }
 }
 
+// The same finish for a layer with Qwen3's per-head q/k norm weights: a head's RMS_NORM needs its
+// D values together, so the unit of work is a head, not a quad.  A work-group is one head of the packed q|k|v
+// rows (q heads, then K heads, then V heads) x 8 consecutive token columns; each of its 4 waves owns one head of
+// one token at a time (columns w and w + 4), lane l its adjacent pair (2l, 2l+1): slabs summed in slab order, then
+// qk_norm_rope_head for q and K heads (the decode attention's FIN path calls the same function: equal bits), q to
+// the f32 buffer, K as one f16 pair, V heads the plain sum.  As above, a 128-byte line of the K / V caches (8
+// positions x 8 dims) is written by this one work-group for the consecutive positions of a prompt chunk.
+template <int D>
+__global__ __launch_bounds__(256) void qkn_finish_kernel(MMArgs a, const float* slabs, int nslab, size_t stride) {
+  const int N = a.n_q + 2 * a.n_kv;
+  const int hd = blockIdx.x;  // head of the packed rows: N / D of them
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const bool live = lane < D / 2;
+  const int row = hd * D + (live ? 2 * lane : 0);
+  const bool is_q = row < a.n_q, is_k = !is_q && row < a.n_q + a.n_kv;
+  const int kvh = is_q ? 0 : (row - a.n_q - (is_k ? 0 : a.n_kv)) / D;
+  f32x2 nw = f32x2{0.f, 0.f};
+  if (live && (is_q || is_k)) nw = *reinterpret_cast<const f32x2*>((is_q ? a.q_norm : a.k_norm) + 2 * lane);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int col = blockIdx.y * 8 + 4 * t + w;  // wave-uniform
+    if (col >= a.M) continue;
+    const int pos = a.pos[col], slot = a.slot[col];
+    if (pos < 0 || pos >= a.n_ctx) continue;  // never write outside the slot's KV rows
+    f32x2 v = f32x2{0.f, 0.f}, cs = f32x2{1.f, 0.f};
+    if (live) {
+      const float* sp = slabs + (size_t)col * N + row;
+      v = *reinterpret_cast<const f32x2*>(sp);
+      for (int k = 1; k < nslab; ++k) v += *reinterpret_cast<const f32x2*>(sp + k * stride);
+      cs = *reinterpret_cast<const f32x2*>(a.rope_cs + ((size_t)pos * (D / 2) + lane) * 2);
+    }
+    if (is_q || is_k) {  // block-uniform
+      const f32x2 o = qk_norm_rope_head<D>(v, nw, cs, a.qk_eps);
+      if (!live) continue;
+      if (is_q) {
+        *reinterpret_cast<f32x2*>(a.out + (size_t)col * a.ldo + row) = o;
+      } else {
+        _Float16* kp = a.kc + (size_t)slot * a.slot_stride + (size_t)kvh * a.ctx_stride * D + kv_k_off(pos, 2 * lane, D);
+        *reinterpret_cast<f16x2*>(kp) = f16x2{(_Float16)o[0], (_Float16)o[1]};
+      }
+    } else if (live) {
+      _Float16* vh = a.vc + (size_t)slot * a.slot_stride + (size_t)kvh * a.ctx_stride * D;
+      vh[kv_v_off(pos, 2 * lane, D)] = (_Float16)v[0];
+      vh[kv_v_off(pos, 2 * lane + 1, D)] = (_Float16)v[1];
+    }
+  }
+}
+
+static void launch_qkn_finish(const MMArgs& a, const float* slabs, int nslab, size_t stride, hipStream_t s) {
+  dim3 grid((a.n_q + 2 * a.n_kv) / a.head_dim, (a.M + 7) / 8);
+  if (a.head_dim == 64) qkn_finish_kernel<64><<<grid, 256, 0, s>>>(a, slabs, nslab, stride);
+  else qkn_finish_kernel<128><<<grid, 256, 0, s>>>(a, slabs, nslab, stride);
+}
+
 void launch_qkv_finish(const MMArgs& a, const float* slabs, int nslab, size_t stride, hipStream_t s) {
+  if (a.q_norm) return launch_qkn_finish(a, slabs, nslab, stride, s);
   const int quads = (a.n_q + 2 * a.n_kv) / 4;
   const int grid = (a.M + 63) / 64 * ((quads + 31) / 32);
   qkv_finish_kernel<<<grid, 256, 0, s>>>(a, slabs, nslab, stride);
@@ -1414,14 +1477,15 @@ bool mm_can_norm_on_load(int M, int K) {
 #include "attn_body.h"
 namespace mx {
 
-template <int D, int G, int NW, bool FIN, int MS, bool QB>
+template <int D, int G, int NW, bool FIN, int MS, bool QB, bool QN = false>
 __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs a) {
-  attn_decode_body<D, G, NW, FIN, MS, QB>(a, blockIdx.x, blockIdx.y);
+  attn_decode_body<D, G, NW, FIN, MS, QB, QN>(a, blockIdx.x, blockIdx.y);
 }
 // QB: the FIN instance that adds the q/k/v bias; a launch without one runs the instance without
 template <int D, int G, int NW, bool FIN, int MS>
 static void launch_attn_g(const AttnArgs& a, dim3 grid, hipStream_t s) {
-  if (FIN && a.qkv_bias) attn_decode_kernel<D, G, NW, FIN, MS, FIN><<<grid, 64 * NW, 0, s>>>(a);
+  if (FIN && a.q_norm) attn_decode_kernel<D, G, NW, FIN, MS, false, FIN><<<grid, 64 * NW, 0, s>>>(a);  // QN (never with a bias)
+  else if (FIN && a.qkv_bias) attn_decode_kernel<D, G, NW, FIN, MS, FIN><<<grid, 64 * NW, 0, s>>>(a);
   else attn_decode_kernel<D, G, NW, FIN, MS, false><<<grid, 64 * NW, 0, s>>>(a);
 }
 
@@ -1439,6 +1503,21 @@ static void launch_attn_dfw(const AttnArgs& a, hipStream_t s) {
   }
 }
 
+// FIN with q/k norm weights and a single slab: the only launch that takes MS = 1
+template <int D, int NW>
+static void launch_attn_qn1(const AttnArgs& a, hipStream_t s) {
+  dim3 grid(a.n_head_kv, a.M);
+  switch (a.n_head / a.n_head_kv) {
+    case 1: attn_decode_kernel<D, 1, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 2: attn_decode_kernel<D, 2, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 4: attn_decode_kernel<D, 4, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 5: attn_decode_kernel<D, 5, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 6: attn_decode_kernel<D, 6, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 7: attn_decode_kernel<D, 7, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+    case 8: attn_decode_kernel<D, 8, NW, true, 1, false, true><<<grid, 64 * NW, 0, s>>>(a); break;
+  }
+}
+
 // Waves per work-group: 8 for decode-sized grids (<= 64 rows: n_head_kv x M work-groups do not fill
 // the chip, so each work-group splits its positions over more waves); 4 once the grid alone fills
 // it (>= 128 rows, e.g. a prefill chunk whose rows are not 16-position blocks).  Measured in round 2
@@ -1453,7 +1532,11 @@ template <int D>
 static void launch_attn_d(const AttnArgs& a, hipStream_t s) {
   static const bool nw4 = getenv("MX_ATTN_NW4") != nullptr;  // A/B: 4 waves for every model (read once)
   const bool mha = a.n_head == a.n_head_kv || nw4;
-  if (a.slabs && mha && a.nslab <= 4) launch_attn_dfw<D, true, 4, 4>(a, s);
+  // QN, one slab (the <= 16-row GEMV's raw q|k|v): MS = 1, no clamped re-reads of it in the one-token step
+  if (a.slabs && a.q_norm && a.nslab == 1) {
+    if (mha) launch_attn_qn1<D, 4>(a, s);
+    else launch_attn_qn1<D, 8>(a, s);
+  } else if (a.slabs && mha && a.nslab <= 4) launch_attn_dfw<D, true, 4, 4>(a, s);
   else if (a.slabs && mha) launch_attn_dfw<D, true, 4>(a, s);  // MS = 4 would drop slabs 4..7
   else if (a.slabs && a.nslab <= 4) launch_attn_dfw<D, true, 8, 4>(a, s);  // Llama-3-8B's q|k|v splits K 4 ways
   else if (a.slabs) launch_attn_dfw<D, true, 8>(a, s);
@@ -2973,7 +3056,10 @@ static int gemm_split(const MMArgs& a, size_t slab_floats, int target) {
 int launch_gemm_split(int epi, const MMArgs& a, float* slabs, size_t slab_floats, int target, hipStream_t s) {
   if (a.M < 1 || !a.X || !gemm_supported(a.N, a.K)) return -1;
   const int S = (slabs && epi != EPI_F32 && target > 0) ? gemm_split(a, slab_floats, target) : 1;
-  if (S == 1) return launch_gemm(epi, a, s) ? -1 : 0;
+  // q/k norm weights: no epilogue can finish q|k|v, so the unsplit GEMM leaves its sums raw too, as one slab
+  const bool qkn = epi == EPI_QKV && a.q_norm;
+  if (qkn && (!slabs || (size_t)a.M * a.N > slab_floats)) return -1;
+  if (S == 1 && !qkn) return launch_gemm(epi, a, s) ? -1 : 0;
   MMArgs p = a;
   p.out = slabs;
   p.ldo = a.N;
@@ -2982,7 +3068,8 @@ int launch_gemm_split(int epi, const MMArgs& a, float* slabs, size_t slab_floats
   launch_gemm_v<EPI_SLAB>(p, grid, s);
   const int total = epi == EPI_SWIGLU ? a.M * a.N / 8 : a.M * a.N / 4;
   const int blocks = std::min((total + 255) / 256, 2048);
-  if (epi == EPI_QKV) qkv_finish_kernel<<<blocks, 256, 0, s>>>(a, slabs, S, p.slab_stride);
+  if (qkn) launch_qkn_finish(a, slabs, S, p.slab_stride, s);
+  else if (epi == EPI_QKV) qkv_finish_kernel<<<blocks, 256, 0, s>>>(a, slabs, S, p.slab_stride);
   else if (epi == EPI_SWIGLU) swiglu_finish_kernel<<<blocks, 256, 0, s>>>(a, slabs, S, p.slab_stride);
   return epi == EPI_RESID ? S : 0;
 }

@@ -391,6 +391,82 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
   return 0;
 }
 
+int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                 const int32_t* pos, const int32_t* slot, const float* slabs, int nslab, const float* rope_cs,
+                 const float* q_norm, const float* k_norm, float eps, void* kcache, void* vcache, float* q_out,
+                 float* attn_out) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (mode < 0 || mode > 1 || !pos || !slot || !slabs || !rope_cs || !q_norm || !k_norm || !kcache || !vcache ||
+      !attn_out || (mode == 0 && !q_out))
+    return fail(MX_ERR_ARG, "mx_qkn_probe: mode 0 / 1, non-null pos / slot / slabs / rope_cs / norms / caches / outputs");
+  if ((head_dim != 64 && head_dim != 128) || n_head_kv < 1 || n_head < n_head_kv || n_head % n_head_kv != 0 ||
+      n_head > 1024)
+    return fail(MX_ERR_ARG, "mx_qkn_probe: head_dim 64 or 128, n_head a multiple of n_head_kv");
+  const int G = n_head / n_head_kv;
+  if (G != 1 && G != 2 && (G < 4 || G > 8)) return fail(MX_ERR_ARG, "mx_qkn_probe: n_head / n_head_kv must be 1, 2 or 4..8");
+  if (n_ctx < 1 || n_ctx > (1 << 20) || n_slots < 1 || n_slots > 4096)
+    return fail(MX_ERR_ARG, "mx_qkn_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+  if (M < 1 || M > MAX_ROWS || nslab < 1 || nslab > ATTN_FIN_MAXSLAB)
+    return fail(MX_ERR_ARG, "mx_qkn_probe: 1 <= M <= 64 rows, 1 <= nslab <= 8");
+  KvGeom g;
+  if (int rc = g.set("mx_qkn_probe", n_head_kv, head_dim, n_ctx, n_slots)) return rc;
+  for (int i = 0; i < M; i++) {
+    if (slot[i] < 0 || slot[i] >= n_slots) return fail(MX_ERR_ARG, "mx_qkn_probe: slot out of range");
+    if (pos[i] < 0 || pos[i] > n_ctx) return fail(MX_ERR_ARG, "mx_qkn_probe: position outside [0, n_ctx]");
+  }
+  {
+    std::vector<int32_t> sorted(slot, slot + M);  // the engine's rows_distinct condition (both modes: one input set)
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      return fail(MX_ERR_ARG, "mx_qkn_probe: every row in its own slot");
+  }
+  const size_t nq = (size_t)n_head * head_dim, N = nq + 2 * (size_t)n_head_kv * head_dim;
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  float *d_q = nullptr, *d_slabs = nullptr, *d_cs = nullptr, *d_qn = nullptr, *d_kn = nullptr, *d_out = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr;
+  const size_t cs_bytes = (size_t)n_ctx * head_dim * 4, slab_bytes = (size_t)nslab * M * N * 4;
+  if (!dev.alloc(&d_k, g.cache_elems * 2) || !dev.alloc(&d_v, g.cache_elems * 2) || !dev.alloc(&d_pos, (size_t)M * 4) ||
+      !dev.alloc(&d_slot, (size_t)M * 4) || !dev.alloc_ff(&d_out, (size_t)M * nq * 4) ||
+      !dev.alloc_ff(&d_q, (size_t)M * nq * 4) || !dev.alloc(&d_slabs, slab_bytes) || !dev.alloc(&d_cs, cs_bytes) ||
+      !dev.alloc(&d_qn, (size_t)head_dim * 4) || !dev.alloc(&d_kn, (size_t)head_dim * 4))
+    return fail(MX_ERR_HIP, "mx_qkn_probe: device allocation");
+  HIPC(hipMemcpy(d_k, kcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_v, vcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_pos, pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_slot, slot, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_slabs, slabs, slab_bytes, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_cs, rope_cs, cs_bytes, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_qn, q_norm, (size_t)head_dim * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_kn, k_norm, (size_t)head_dim * 4, hipMemcpyHostToDevice));
+  AttnArgs at{};
+  at.q = d_q; at.kc = d_k; at.vc = d_v; at.pos = d_pos; at.slot = d_slot; at.outf = d_out;
+  at.ldo = (int)nq; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
+  at.n_ctx = n_ctx; at.ctx_stride = g.ctx_stride; at.slot_stride = g.slot_stride;
+  at.scale = 1.0f / sqrtf((float)head_dim);
+  HIPC(hipDeviceSynchronize());
+  if (mode == 0) {  // qkn_finish_kernel, then the plain attention on what it stored
+    MMArgs a{};
+    a.M = M; a.N = (int)N; a.out = d_q; a.ldo = (int)nq; a.n_q = (int)nq; a.n_kv = n_head_kv * head_dim;
+    a.head_dim = head_dim; a.pos = d_pos; a.slot = d_slot; a.rope_cs = d_cs; a.kc = d_k; a.vc = d_v; a.n_ctx = n_ctx;
+    a.ctx_stride = g.ctx_stride; a.n_head_kv = n_head_kv; a.slot_stride = g.slot_stride;
+    a.q_norm = d_qn; a.k_norm = d_kn; a.qk_eps = eps;
+    launch_qkv_finish(a, d_slabs, nslab, (size_t)M * N, nullptr);
+  } else {  // the decode attention's FIN path with the norm weights
+    at.slabs = d_slabs; at.nslab = nslab; at.slab_stride = (size_t)M * N; at.rope_cs = d_cs; at.kc_w = d_k; at.vc_w = d_v;
+    at.q_norm = d_qn; at.k_norm = d_kn; at.qk_eps = eps;
+  }
+  launch_attention(at, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(attn_out, d_out, (size_t)M * nq * 4, hipMemcpyDeviceToHost));
+  if (q_out) HIPC(hipMemcpy(q_out, d_q, (size_t)M * nq * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(kcache, d_k, g.cache_elems * 2, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(vcache, d_v, g.cache_elems * 2, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int mx_matmul_plan(int epi, int M, int N, int K, int32_t* kgroups, int32_t* pers_ok, int32_t* norm_on_load_ok,
                    int32_t* gemm_ok) {
   if (epi < EPI_F32 || epi > EPI_SWIGLU || M < 1 || N < TILE_N || N % TILE_N || K < TILE_K || K % TILE_K)

@@ -32,7 +32,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
-    "mx_attention_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
+    "mx_attention_probe", "mx_qkn_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
@@ -324,6 +324,8 @@ def lib() -> ctypes.CDLL:
         L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
         L.mx_attention_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
                                          vp, vp]
+        L.mx_qkn_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.c_float,
+                                   vp, vp, vp, vp]
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
         L.mx_matmul_plan.argtypes = [i32, i32, i32, i32, P(i32), P(i32), P(i32), P(i32)]
         L.mx_norm_probe.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, ctypes.c_float, vp, vp]
@@ -617,6 +619,39 @@ def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
     return out, kc, vc
+
+
+def qkn_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot, kcache,
+              vcache, slabs, rope_cs, q_norm, k_norm, eps: float, device: int = 0):
+    """Qwen3's per-head q/k norm kernels on caller-supplied split-K slabs (no engine; include/mx_engine.h
+    mx_qkn_probe).  mode 0: qkn_finish_kernel, then the plain decode attention; mode 1: the decode attention's FIN
+    path with the norm weights.  Arguments as attention_probe's mode 1, plus q_norm / k_norm [head_dim] f32 (the
+    engine's order: adjacent RoPE pairs).  Returns (q [M][n_head * head_dim] f32 -- 0xFF bytes where nothing was
+    written, and in mode 1 --, attention out f32, kcache after, vcache after)."""
+    pos, slot = _i32(pos), _i32(slot)
+    M = len(pos)
+    if len(slot) != M:
+        raise ValueError("one slot per row")
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    elems = max(n_slots, 0) * max(n_head_kv, 0) * ctx_stride * max(head_dim, 0)
+    kc = np.array(kcache, dtype=np.uint16, copy=True).reshape(-1)
+    vc = np.array(vcache, dtype=np.uint16, copy=True).reshape(-1)
+    if kc.size != elems or vc.size != elems:
+        raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+    nq, N = n_head * head_dim, (n_head + 2 * n_head_kv) * head_dim
+    sa = np.ascontiguousarray(slabs, dtype=np.float32)
+    ca = np.ascontiguousarray(rope_cs, dtype=np.float32)
+    qn, kn = (np.ascontiguousarray(w, dtype=np.float32) for w in (q_norm, k_norm))
+    nslab = sa.shape[0]
+    if sa.shape != (nslab, M, N) or ca.size != max(n_ctx, 0) * head_dim or qn.size != head_dim or kn.size != head_dim:
+        raise ValueError("slabs [nslab][M][n_q + 2 n_kv], rope_cs [n_ctx][head_dim/2][2], norms [head_dim] expected")
+    q = np.full((M, max(nq, 0)), np.nan, dtype=np.float32)
+    q.view(np.uint8)[...] = 0xFF
+    out = np.empty((M, max(nq, 0)), dtype=np.float32)
+    _check(lib().mx_qkn_probe(device, mode, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
+                              slot.ctypes.data, sa.ctypes.data, nslab, ca.ctypes.data, qn.ctypes.data, kn.ctypes.data,
+                              float(eps), kc.ctypes.data, vc.ctypes.data, q.ctypes.data, out.ctypes.data))
+    return q, out, kc, vc
 
 
 def kv_copy_probe(n_layer: int, n_slots: int, n_head_kv: int, head_dim: int, n_ctx: int, copies, kcache, vcache,

@@ -457,7 +457,7 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
                          dequant_from: str = None, rope_freqs=None, rope_scaling=None, embd_type: int = None,
                          pooling_type: int = None, eos_token_id: int = 2, eot_token_id: int = None,
                          merge_lora=None, arch: str = "llama", qkv_bias: float = None, tie_embeddings: bool = False,
-                         qk_rows: str = "norm"):
+                         qk_rows: str = "norm", qk_norm=None, key_length: int = None):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
     "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
@@ -478,7 +478,10 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     tie_embeddings: no output.weight (the loader falls back to token_embd.weight).  qk_rows "neox": the rows of
     attn_q / attn_k (whatever their type: a row gather on the array of values or blocks) and of their biases are
     written in the inverse of the loader's qwen2 permutation -- file row j*d/2 + i of a head = row 2i + j of the
-    "norm" file -- so a qwen2 loader rebuilds the "norm" file's rows.  The defaults leave every file as it was."""
+    "norm" file -- so a qwen2 loader rebuilds the "norm" file's rows.  qk_norm: Qwen3's per-head norm weights,
+    {(layer, "q" | "k"): f32 [head_dim]} written as blk.N.attn_{q,k}_norm.weight as given (file order; arch "qwen3"
+    needs them).  key_length: written as <arch>.attention.key_length and .value_length.  The defaults leave every
+    file as it was."""
     from . import synth
 
     if qk_rows not in ("norm", "neox"):
@@ -507,6 +510,9 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     w.add_uint32(A + "attention.head_count_kv", shape.n_head_kv)
     w.add_float32(A + "attention.layer_norm_rms_epsilon", shape.eps)
     w.add_float32(A + "rope.freq_base", shape.rope_base)
+    if key_length is not None:
+        w.add_uint32(A + "attention.key_length", key_length)
+        w.add_uint32(A + "attention.value_length", key_length)
     if rope_scaling is not None:
         w.add_string(A + "rope.scaling.type", rope_scaling[0])
         w.add_float32(A + "rope.scaling.factor", rope_scaling[1])
@@ -588,6 +594,11 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
                     b = np.ascontiguousarray(b[neox_idx(n)])
                 w.add_tensor_info(f"blk.{l}.attn_{k}.bias", b.shape, GGML_F32)
                 arrays.append(b)
+    for (l, k), nw in (qk_norm or {}).items():
+        nw = np.ascontiguousarray(nw, dtype=np.float32)
+        assert nw.shape == (shape.head_dim,)
+        w.add_tensor_info(f"blk.{l}.attn_{k}_norm.weight", nw.shape, GGML_F32)
+        arrays.append(nw)
     if rope_freqs is not None:
         rf = np.ascontiguousarray(rope_freqs, dtype=np.float32)
         assert rf.shape == (shape.head_dim // 2,)
