@@ -377,10 +377,11 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
                        int nslab, const float* rope_cs, void* kcache, void* vcache, void* out, const float* bias);
 
 /* Qwen3's per-head q/k RMS_NORM kernels on caller-supplied split-K slabs, no engine.  Geometry,
- * caches, pos / slot, slabs and rope_cs as mx_attention_probe's mode 1 (M <= 64, every row its own slot); q_norm /
- * k_norm: f32 [head_dim], in the engine's order (adjacent RoPE pairs).  mode 0: qkn_finish_kernel (slab sum, head
- * norm, RoPE, q and K/V stores), then the plain decode attention; mode 1: the decode attention finishing the slabs
- * itself.  q_out [M][n_head * head_dim] f32 (required in mode 0; filled with 0xFF bytes before the launch, written
+ * caches, pos / slot, slabs and rope_cs as mx_attention_probe's mode 1 (M <= 64); q_norm / k_norm: f32 [head_dim],
+ * in the engine's order (adjacent RoPE pairs).  mode 0: qkn_finish_kernel (slab sum, head norm, RoPE, q and K/V
+ * stores), then the plain decode attention -- rows may share a slot (a prompt chunk: consecutive positions of one
+ * slot), but the (slot, position) pairs of the rows below n_ctx must be distinct; mode 1: the decode attention
+ * finishing the slabs itself -- every row its own slot.  q_out [M][n_head * head_dim] f32 (required in mode 0; filled with 0xFF bytes before the launch, written
  * by mode 0 alone), attn_out the same shape (the attention's f32 output); the caches are copied back after the
  * launch.  Anything else is MX_ERR_ARG and nothing is launched. */
 int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
@@ -459,7 +460,9 @@ int mx_kv_pack_probe(int device, int dir, int n_layer, int n_slots, int n_head_k
  * path 0 launch_mm (M 1..64), 1 launch_mm_pers (M 1..16, shapes of mx_matmul_plan's pers_ok), 2 launch_mm_wide
  * (M 1..64), 3 launch_mm_wide with full_chain, 4 launch_gemm_split (M 65..4096 as in the engine, `target`
  * 0..256 work-groups, slab space `slab_floats` <= 2^26; act_f32 only with target 0: the split finish writes
- * bf16).  epi: 0 F32, 1 RESID, 2 QKV, 3 SWIGLU.  w: bf16 [N][K] row-major in GGUF order (N % 16,
+ * bf16).  epi: 0 F32, 1 RESID, 2 QKV, 3 SWIGLU; 6 QKV_RAW on path 0 alone (launch_mm's raw q|k|v sums in EPI_QKV's
+ * K grouping, out f32 [M][N] with ld N, no QKV operands; every other path refuses it).  w: bf16 [N][K] row-major
+ * in GGUF order (N % 16,
  * K % 32; SWIGLU: rows [0, N/2) ffn_gate, [N/2, N) ffn_up), packed on the device with launch_pack as at model
  * load (packed_out, optional, receives the N*K packed bf16).  Activations: x bf16 [M][K] -- the device buffer
  * has 16 / 32 / 64 rows for M <= 16 / 32 / 64 (else M rounded up to 16), rows >= M hold bf16 NaN -- or, paths

@@ -173,7 +173,8 @@ __device__ __forceinline__ f32x4 rope4(f32x4 s, f32x4 c) {
 // and its (cos, sin) cs; lanes >= D/2 (D = 64) must pass v = 0 and their result means nothing.  Sum of squares as
 // ssq4 forms it (each square rounded to f32, accumulated in double), pair first, then ssq_wave's fixed xor
 // butterfly over the 64 lanes (the idle half adds exact zeros): the order depends on D alone.  Then ggml's
-// RMS_NORM (x * scale) and MUL (* w) in f32 and rope4's scalar-fma RoPE behind the same opq fences.  Every caller
+// RMS_NORM (x * scale) and MUL (* w), formed in double and rounded to f32 once, and rope4's scalar-fma RoPE behind the
+// same opq fences.  Every caller
 // (the decode attention's FIN path, qkn_finish_kernel) goes through here, so their q and K bits are equal.
 template <int D>
 __device__ __forceinline__ f32x2 qk_norm_rope_head(f32x2 v, f32x2 w, f32x2 cs, float eps) {
@@ -184,8 +185,12 @@ __device__ __forceinline__ f32x2 qk_norm_rope_head(f32x2 v, f32x2 w, f32x2 cs, f
     q = (double)(v[0] * v[0]);
     q += (double)(v[1] * v[1]);
   }
-  const float scale = rms_scale(ssq_wave(q), D, eps);
-  const float n0 = opq((v[0] * scale) * w[0]), n1 = opq((v[1] * scale) * w[1]);
+  // the scale, x * scale and * w in double, rounded to f32 once: formed in f32 (scale, product, product: three more
+  // roundings) a q element near 8.6 came out 1.9 f32 ulp from float64 where plain f32 NumPy is within 0.63
+  // (tests/test_qkn_kernel_gpu.py test_fin_plans[D64-G1-real]).  Once per head per token: not on any hot loop.
+  const double scale = 1.0 / sqrt(ssq_wave(q) / D + (double)eps);
+  const float n0 = opq((float)(((double)v[0] * scale) * (double)w[0]));
+  const float n1 = opq((float)(((double)v[1] * scale) * (double)w[1]));
   const float c0 = opq(cs[0]), c1 = opq(cs[1]);
   f32x2 o;
   o[0] = opq(__builtin_fmaf(n0, c0, -(n1 * c1)));

@@ -653,8 +653,16 @@ struct mx_engine {
   // launch_mm_wide walks K in chunks of 4 K tiles: a model whose n_embd or n_ff is no multiple of 128 (n_embd 448)
   // runs its 17..64-row forwards through launch_mm, as it runs its <= 16-row ones
   bool wide_shapes() const { return n_embd % (4 * TILE_K) == 0 && n_ff % (4 * TILE_K) == 0; }
+  // A quantised layer with q/k norm weights (§19) leaves the raw q|k|v sums of a chunk above 64 rows in gslabs
+  // (enqueue_forward_quant): there is none without the GEMM's shapes, and it holds GSLAB_FLOATS.  Such a model takes
+  // its prompts in chunks of MAX_ROWS rows (the slabs' room) instead of meeting "no slab space" on a long prompt.
+  bool qkn_raw_fits() const {
+    if (layers.empty() || !layers[0].q_norm) return true;
+    const bool gemm_route = kqd_qkv && (wkq ? !kq_ggml_prefill : q8_gemm_prefill && !wq4);  // enqueue_forward_gemm
+    return gemm_route || (gslabs && (size_t)PREFILL_ROWS * (n_embd + 2 * n_embd_kv) <= GSLAB_FLOATS);
+  }
   bool gemm_ok() const {  // chunks of PREFILL_ROWS rows can run (the Q8_0 / K-quant paths take any row count)
-    return wq8 || wkq || gemm_shapes();
+    return (wq8 || wkq) ? qkn_raw_fits() : gemm_shapes();
   }
   int enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_chain = false);
   int forward_rows_chunk(int n, const int32_t* slots, const int32_t* pos, const int32_t* ids, const void* x_in,

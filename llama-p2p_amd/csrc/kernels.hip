@@ -1021,10 +1021,11 @@ int launch_mm(int epi, const MMArgs& a, hipStream_t s) {
       case EPI_F32:
         return ntiles % 4 == 0 ? launch_mm_cfg<8, 4, EPI_F32, 4>(a, s) : launch_mm_cfg<8, 1, EPI_F32, 8>(a, s);
       case EPI_RESID: return launch_mm_cfg<4, 1, EPI_RESID, 8>(a, s);
-      case EPI_QKV:
-        return ntiles % 2 == 0 ? launch_mm_cfg<8, 2, EPI_QKV, 8>(a, s) : launch_mm_cfg<8, 1, EPI_QKV, 8>(a, s);
-      case EPI_QKV_RAW:
-        return ntiles % 2 == 0 ? launch_mm_cfg<8, 2, EPI_QKV_RAW, 8>(a, s) : launch_mm_cfg<8, 1, EPI_QKV_RAW, 8>(a, s);
+      // q|k|v: one wave per canonical K slice at every row count.  8 or 4 waves chain two or four slices in one
+      // MFMA accumulator, which rounds differently from the 16-wave fold of <= 16 rows: a row's q|k|v then
+      // depended on the row count (tests/test_qkv_raw_kernel_gpu.py test_canonical_grouping)
+      case EPI_QKV: return launch_mm_cfg<16, 1, EPI_QKV, 4>(a, s);
+      case EPI_QKV_RAW: return launch_mm_cfg<16, 1, EPI_QKV_RAW, 4>(a, s);
       case EPI_SWIGLU:
         return ntiles % 4 == 0 ? launch_mm_cfg<4, 4, EPI_SWIGLU, 4>(a, s) : launch_mm_cfg<4, 1, EPI_SWIGLU, 8>(a, s);
     }
@@ -1034,10 +1035,8 @@ int launch_mm(int epi, const MMArgs& a, hipStream_t s) {
     case EPI_F32:
       return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_F32, 4>(a, s) : launch_mm_cfg<4, 1, EPI_F32, 4>(a, s);
     case EPI_RESID: return launch_mm_cfg<4, 1, EPI_RESID, 8>(a, s);
-    case EPI_QKV:
-      return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_QKV, 4>(a, s) : launch_mm_cfg<4, 1, EPI_QKV, 4>(a, s);
-    case EPI_QKV_RAW:
-      return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_QKV_RAW, 4>(a, s) : launch_mm_cfg<4, 1, EPI_QKV_RAW, 4>(a, s);
+    case EPI_QKV: return launch_mm_cfg<16, 1, EPI_QKV, 4>(a, s);  // as above
+    case EPI_QKV_RAW: return launch_mm_cfg<16, 1, EPI_QKV_RAW, 4>(a, s);
     case EPI_SWIGLU:
       return ntiles % 2 == 0 ? launch_mm_cfg<4, 2, EPI_SWIGLU, 4>(a, s) : launch_mm_cfg<4, 1, EPI_SWIGLU, 4>(a, s);
   }

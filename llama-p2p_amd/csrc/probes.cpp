@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine_shared.h"
@@ -415,10 +416,15 @@ int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, 
     if (pos[i] < 0 || pos[i] > n_ctx) return fail(MX_ERR_ARG, "mx_qkn_probe: position outside [0, n_ctx]");
   }
   {
-    std::vector<int32_t> sorted(slot, slot + M);  // the engine's rows_distinct condition (both modes: one input set)
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-      return fail(MX_ERR_ARG, "mx_qkn_probe: every row in its own slot");
+    // mode 1: the engine's rows_distinct condition.  mode 0 (a prompt chunk: rows of one slot at consecutive
+    // positions) only needs no two storing rows on one cache entry
+    std::vector<std::pair<int32_t, int32_t>> key;
+    for (int i = 0; i < M; i++)
+      if (mode == 1 || pos[i] < n_ctx) key.emplace_back(slot[i], mode == 1 ? 0 : pos[i]);
+    std::sort(key.begin(), key.end());
+    if (std::adjacent_find(key.begin(), key.end()) != key.end())
+      return fail(MX_ERR_ARG, mode == 1 ? "mx_qkn_probe: mode 1 needs every row in its own slot"
+                                        : "mx_qkn_probe: mode 0 needs distinct (slot, position) pairs among the rows below n_ctx");
   }
   const size_t nq = (size_t)n_head * head_dim, N = nq + 2 * (size_t)n_head_kv * head_dim;
   if (device >= 0) HIPC(hipSetDevice(device));
@@ -483,8 +489,9 @@ int mx_matmul_probe(int device, const mx_matmul_args* pa) {
   if (!pa) return fail(MX_ERR_ARG, "mx_matmul_probe: null arguments");
   const mx_matmul_args& p = *pa;
   const int path = p.path, epi = p.epi, M = p.M, N = p.N, K = p.K;
-  if (path < 0 || path > 4 || epi < EPI_F32 || epi > EPI_SWIGLU)
-    return fail(MX_ERR_ARG, "mx_matmul_probe: path 0..4, epi 0..3");
+  const bool raw = epi == EPI_QKV_RAW;  // launch_mm alone has the raw q|k|v epilogue
+  if (path < 0 || path > 4 || ((epi < EPI_F32 || epi > EPI_SWIGLU) && !(raw && path == 0)))
+    return fail(MX_ERR_ARG, "mx_matmul_probe: path 0..4, epi 0..3 (6, the raw q|k|v sums: path 0 only)");
   if (N < TILE_N || N % TILE_N || K < TILE_K || K % TILE_K || N > (1 << 18) || K > 32768 ||
       (size_t)N * K > ((size_t)1 << 30))
     return fail(MX_ERR_ARG, "mx_matmul_probe: N a multiple of 16 (<= 2^18), K a multiple of 32 (<= 32768), N*K <= 2^30");

@@ -724,6 +724,7 @@ def kv_pack_probe(direction: int, n_layer: int, n_slots: int, n_head_kv: int, he
 
 
 EPI_F32, EPI_RESID, EPI_QKV, EPI_SWIGLU = 0, 1, 2, 3  # kernels.h Epilogue
+EPI_QKV_RAW = 6  # matmul_probe path 0 only: the raw q|k|v sums, out [M][N]
 PROBE_GUARD_ROWS = 64  # rows of 0xFF bytes the probes return after every output
 
 

@@ -24,6 +24,22 @@ SHAPES = {
     "q3-g5": (LlamaShape("q3-g5", 640, 2, 5, 1, 512, 512, 1e6, 1e-6), False),              # d 128, G 5 (14B)
     "q3-mha": (LlamaShape("q3-mha", 256, 2, 4, 4, 512, 512, 1e6, 1e-6), False),            # d 64, G 1: 4-wave attention
 }
+# Shapes without a transformers golden: the reference for them is forward(..., "ggml") (checked against transformers
+# on the four shapes above), the ids come from seeded_ids.  q3-g7: Qwen2's qwen-g7 geometry, a width that is no multiple
+# of 128 (no launch_mm_wide, no prefill GEMM: 17..64-row forwards take launch_mm's raw q|k|v epilogue).
+EXTRA_SHAPES = {
+    "q3-g7": (LlamaShape("q3-g7", 448, 2, 7, 1, 512, 512, 1e6, 1e-6), False),              # d 64, G 7
+}
+
+
+def shape_of(name):
+    return SHAPES[name] if name in SHAPES else EXTRA_SHAPES[name]
+
+
+def seeded_ids(name, T=40):
+    shape, _ = shape_of(name)
+    rng = np.random.default_rng([SEED, len(name), T])
+    return np.concatenate([[1], rng.integers(3, shape.n_vocab, T - 1)]).astype(np.int32)
 
 
 def golden(name):
@@ -33,7 +49,7 @@ def golden(name):
 
 def qk_norm(name, seed=SEED, ones=False):
     """{(layer, "q" | "k"): f32 [head_dim]} in file order: log-normal around 1 (0.3 .. 3), or all ones."""
-    shape, _ = SHAPES[name]
+    shape, _ = shape_of(name)
     out = {}
     for l in range(shape.n_layer):
         for j, k in enumerate("qk"):
@@ -45,7 +61,7 @@ def qk_norm(name, seed=SEED, ones=False):
 def write_gguf(path, name, wtype="bf16", ones=False, **kw):
     from llama_p2p_amd import gguf
 
-    shape, tied = SHAPES[name]
+    shape, tied = shape_of(name)
     kw.setdefault("arch", "qwen3")
     kw.setdefault("tie_embeddings", tied)
     kw.setdefault("qk_norm", qk_norm(name, ones=ones))
@@ -55,7 +71,7 @@ def write_gguf(path, name, wtype="bf16", ones=False, **kw):
 def weights(name, seed=SEED, permute=True, ones=False):
     """{gguf name: float64 array}: the synthetic bf16 weights and the head-norm weights; attn_q / attn_k rows and the
     norm weights in the engine's order when `permute`."""
-    shape, tied = SHAPES[name]
+    shape, tied = shape_of(name)
     t = {}
     for nm, kind, arr in synth.synth_tensors(shape, seed):
         t[nm] = (synth.bf16_bits_to_f32(arr) if kind == "bf16" else arr).astype(np.float64)
@@ -79,7 +95,7 @@ def head_norm(x, w, eps):
 def forward(name, ids, mode="exact", t=None):
     """Logits [T][n_vocab] (float64) of `ids` at positions 0..T-1, every position attending to its prefix."""
     assert mode in ("exact", "ggml")
-    shape, _ = SHAPES[name]
+    shape, _ = shape_of(name)
     t = t or weights(name)
     act = rbf16 if mode == "ggml" else (lambda v: v)
     half = rf16 if mode == "ggml" else (lambda v: v)

@@ -17,9 +17,9 @@ refusals, cross-path equality with random (order-sensitive) operands.
 Branches and the case that reaches each (kernels.hip):
   launch_mm nb=1 <16,1,*,4>: M 1/15/16, every epilogue; K 32 (15 of 16 waves empty), 96 (uneven), 512 (one tile
     per wave, tail only), 2080 (ring + tail), 4096 (full ring).  nb=2: F32 <8,4> tiles 4 / <8,1> tiles 1,2,3,6;
-    RESID <4,1>; QKV <8,2> (tiles always even: head_dim 64 / 128 make q|k|v a multiple of 4 tiles, so <8,1,QKV>
-    and <4,1,QKV> are unreachable with a valid geometry); SWIGLU <4,4> tiles 4 / <4,1> tiles 1,2,3,6.  nb=3,4:
-    <4,2> even / <4,1> odd tiles for F32 and SWIGLU, <4,2,QKV>, <4,1,RESID>.  Norm on load: K 512 / 2048 / 8192.
+    RESID <4,1>; QKV <16,1,QKV,4> as at nb=1 (one wave per canonical K slice at every row count:
+    tests/test_qkv_raw_kernel_gpu.py); SWIGLU <4,4> tiles 4 / <4,1> tiles 1,2,3,6.  nb=3,4:
+    <4,2> even / <4,1> odd tiles for F32 and SWIGLU, <16,1,QKV,4>, <4,1,RESID>.  Norm on load: K 512 / 2048 / 8192.
   launch_mm_pers: SWIGLU tiles 1026 / 1376 / 1537 (5, 6, 7 per group, phantom tiles), 1792, 704 (K 2048), 3584
     (K 8192); RESID (4096,4096) (4096,14336) (2048,2048) (2048,5632); QKV 384 / 768 / 160 / 640 tiles.
   launch_mm_wide F32 tiles 6 <3,2>, 4 <4,1>, 2 <2,1>, 2048 <4,2>, 4096 <8,2>; SWIGLU 3, 5, 770 (<3,1> / <4,1>

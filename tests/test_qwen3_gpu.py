@@ -10,7 +10,7 @@ import pytest
 from conftest import assert_logits_close, assert_tokens_match
 
 import qwen3_ref as Q
-from test_qwen2_gpu import N_CTX, REGIMES, mx, open_engine, run_regime, tmp  # noqa: F401  (fixtures)
+from test_qwen2_gpu import N_CTX, REGIMES, StopOnHipError, mx, open_engine, run_regime, tmp  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,31 +44,89 @@ def test_bf16_logits_every_regime(mx, tmp, name):
         eng.close()
 
 
-def quant_vs_own_bf16(mx, tmp, tag, wtype, **kw):
-    """test_qwen2_gpu.quant_vs_own_bf16 on q3-g4-d128 in regimes one and slots24."""
-    ids, _ = Q.golden("q3-g4-d128")
-    pq = Q.write_gguf(str(tmp / f"{tag}_{wtype}.gguf"), "q3-g4-d128", wtype=wtype, **kw)
-    pb = Q.write_gguf(str(tmp / f"{tag}_{wtype}_bf16.gguf"), "q3-g4-d128", dequant_from=pq, **kw)
+def quant_vs_own_bf16(mx, tmp, tag, wtype, name="q3-g4-d128", **kw):
+    """test_qwen2_gpu.quant_vs_own_bf16 on `name` in every regime -> {regime: worst |d| / max|ref|}."""
+    ids = Q.golden(name)[0] if name in Q.SHAPES else Q.seeded_ids(name)
+    pq = Q.write_gguf(str(tmp / f"{tag}_{name}_{wtype}.gguf"), name, wtype=wtype, **kw)
+    pb = Q.write_gguf(str(tmp / f"{tag}_{name}_{wtype}_bf16.gguf"), name, dequant_from=pq, **kw)
     res = []
     for path in (pq, pb):
         eng = open_engine(mx, path)
         try:
-            res.append([run_regime(eng, ids[:12] if r == "one" else ids, r)[1] for r in ("one", "slots24")])
+            res.append({r: run_regime(eng, ids[:12] if r == "one" else ids, r)[1] for r in REGIMES})
         finally:
             eng.close()
-    assert all(not np.isnan(a).any() for a in res[0])
-    return max(float(np.abs(a - b).max() / np.abs(b).max()) for a, b in zip(*res))
+    assert all(not np.isnan(a).any() for a in res[0].values())
+    return {r: float(np.abs(res[0][r] - res[1][r]).max() / np.abs(res[1][r]).max()) for r in REGIMES}
+
+
+def quantised_within_twice_the_twin(mx, tmp, wtype, name):
+    twin = quant_vs_own_bf16(mx, tmp, "twin", wtype, name, arch="llama", qk_norm=None)
+    q3 = quant_vs_own_bf16(mx, tmp, "q3", wtype, name)
+    for r in REGIMES:
+        print(f"{name} {wtype} {r}: quantised vs its own BF16, worst |d| / max|ref|: llama twin {twin[r]:.4g}, qwen3 "
+              f"{q3[r]:.4g} (ratio {q3[r] / twin[r] if twin[r] else float('inf'):.3f})")
+    t, q = max(twin.values()), max(q3.values())
+    assert t > 0
+    assert q <= 2 * t, f"{wtype}: qwen3 {q:.4g} > 2 x llama twin {t:.4g}"
 
 
 @pytest.mark.parametrize("wtype", ["q8_0", "q4_k_m"])
 def test_quantised_model(mx, tmp, wtype):
-    """Q8_0, and Q4_K with attn_v Q6_K, against this engine on the same file rewritten as BF16; the bar of the Qwen2
-    quantised test: twice what the llama twin of the shape (no norm weights: code from before them) shows."""
-    twin = quant_vs_own_bf16(mx, tmp, "twin", wtype, arch="llama", qk_norm=None)
-    q3 = quant_vs_own_bf16(mx, tmp, "q3", wtype)
-    print(f"q3-g4-d128 {wtype}: quantised vs its own BF16, worst |d| / max|ref|: llama twin {twin:.4g}, qwen3 {q3:.4g}")
-    assert twin > 0
-    assert q3 <= 2 * twin, f"{wtype}: qwen3 {q3:.4g} > 2 x llama twin {twin:.4g}"
+    """Q8_0, and Q4_K with attn_v Q6_K, against this engine on the same file rewritten as BF16, in every regime; the bar
+    of the Qwen2 quantised test: twice what the llama twin of the shape (no norm weights: code from before them) shows,
+    worst regime against worst regime as before.  "chunk5" / "chunk16" reach qkn_finish_kernel behind the quantised
+    GEMVs (shared-slot rows, an EPI_F32 GEMV's sums as one slab), "prefill144" Q8_0's route of more than 64 rows into
+    the GEMM's slab space and the K-quant model's dequantised GEMM, whose split finish leaves q|k|v raw."""
+    quantised_within_twice_the_twin(mx, tmp, wtype, "q3-g4-d128")
+
+
+def test_bf16_width_448_every_regime(mx, tmp):
+    """q3-g7 (n_embd 448 = 7 heads x 64, one kv head, n_ff 512): no multiple of 128, so no launch_mm_wide and no
+    prefill GEMM.  "slots24" runs the FIN path with the norm behind launch_mm's 17..64-row raw q|k|v epilogue,
+    "prefill144" the GEMV route with qkn_finish_kernel.  The reference is qwen3_ref.forward(..., "ggml"), validated
+    against transformers on the four golden shapes; the ids come from a seeded generator, so no new transformers
+    golden is needed."""
+    ids = Q.seeded_ids("q3-g7")
+    ref = Q.forward("q3-g7", ids, "ggml").astype(np.float32)
+    eng = open_engine(mx, Q.write_gguf(str(tmp / "q3-g7.gguf"), "q3-g7"))
+    try:
+        assert (eng.info.n_head, eng.info.n_head_kv, eng.info.head_dim) == (7, 1, 64)
+        check(eng, ids, ref, REGIMES, "q3-g7")
+    finally:
+        eng.close()
+
+
+def test_q8_0_without_gemm_slab_space(mx, tmp):
+    """A Q8_0 model with q/k norm weights whose shapes the prefill GEMM does not take (q3-g7) has no slab space for the
+    raw q|k|v sums of more than 64 rows: its prompts are taken in 64-row chunks (engine.cpp qkn_raw_fits).  Before
+    that, a prompt chunk above 64 rows was refused ("no slab space") and Llama.create_completion failed on any
+    prompt above 64 tokens.  Every regime ("prefill144": 144 rows in one call) against the llama twin's bar, and a
+    100-token prompt through the Llama front against the engine's own 16-row chunks."""
+    from llama_p2p_amd.llama import Llama
+
+    quantised_within_twice_the_twin(mx, tmp, "q8_0", "q3-g7")
+    path = Q.write_gguf(str(tmp / "front_q3-g7_q8_0.gguf"), "q3-g7", wtype="q8_0")
+    ids = [int(t) for t in Q.seeded_ids("q3-g7", 100)]
+    llm = Llama(path, n_ctx=128, n_seq_max=2, device=0, verbose=False)
+    try:
+        text = llm.create_completion(ids, max_tokens=1, temperature=0.0)["choices"][0]["text"]
+    finally:
+        llm.close()
+    try:
+        eng = StopOnHipError(mx.Engine(path, n_ctx=128, n_seq_max=2, device=0), mx)
+    except mx.MxError as e:
+        if e.code == mx.MX_ERR_HIP:
+            pytest.exit(f"{path}: {e}", returncode=3)
+        raise
+    try:
+        eos = eng.info.eos_id
+        for i in range(0, 100, 16):
+            lg = eng.forward_rows([0] * len(ids[i:i + 16]), list(range(i, min(i + 16, 100))), ids[i:i + 16])[-1]
+    finally:
+        eng.close()
+    tok = int(lg.argmax())
+    assert text == ("" if tok == eos else llm.tokenizer_.detokenize([tok], prev_tokens=ids).decode("utf-8", errors="ignore"))
 
 
 def test_norm_weights_are_applied(mx, tmp):
