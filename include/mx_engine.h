@@ -376,6 +376,18 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
                        const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const float* slabs,
                        int nslab, const float* rope_cs, void* kcache, void* vcache, void* out, const float* bias);
 
+/* Long-context decode attention: the segment rule, without a GPU.  A row of context ctx =
+ * min(pos + 1, n_ctx) (1 <= ctx <= 2^20) runs as *nseg segments of *seg_len positions (the last one shorter);
+ * *nseg is 1 up to *threshold and at most *nseg_max.  Both depend on ctx alone. */
+int mx_attention_split_plan(int ctx, int32_t* threshold, int32_t* nseg_max, int32_t* nseg, int32_t* seg_len);
+/* launch_attention_split (attn_split_kernel + attn_merge_kernel) on caller-supplied final q and raw tiled caches, no
+ * engine: the arguments of mx_attention_probe's mode 0 with 1 <= M <= 64; the caches are only read.  out: 64 rows
+ * [n_head * head_dim], f32 (out_f32 != 0) or bf16, filled with 0xFF bytes before the launch -- rows M..63 are a
+ * guard that must come back as 0xFF.  Anything else is MX_ERR_ARG and nothing is launched. */
+int mx_attention_long_probe(int device, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                            const int32_t* pos, const int32_t* slot, int out_f32, const float* q, void* kcache,
+                            void* vcache, void* out);
+
 /* Qwen3's per-head q/k RMS_NORM kernels on caller-supplied split-K slabs, no engine.  Geometry,
  * caches, pos / slot, slabs and rope_cs as mx_attention_probe's mode 1 (M <= 64); q_norm / k_norm: f32 [head_dim],
  * in the engine's order (adjacent RoPE pairs).  mode 0: qkn_finish_kernel (slab sum, head norm, RoPE, q and K/V

@@ -251,8 +251,10 @@ struct GraphKey {
   void* xout;
   hipStream_t stream;
   int ktop;  // 0: greedy argmax tail; k: the device sampling chain with top-k k
+  bool long_ctx;  // captured with mx_engine::long_fwd: the split attention
   bool operator<(const GraphKey& o) const {
     if (M != o.M) return M < o.M;
+    if (long_ctx != o.long_ctx) return long_ctx < o.long_ctx;
     if (xin != o.xin) return xin < o.xin;
     if (xout != o.xout) return xout < o.xout;
     if (ktop != o.ktop) return ktop < o.ktop;
@@ -332,6 +334,22 @@ struct mx_engine {
   bool use_wide = getenv("MX_NO_WIDE") == nullptr;  // 17..64-row forward through mm_wide (LDS-shared activations)
   float* slabs = nullptr;                           // split-K partials [8][MAX_ROWS][n_embd + 2 n_embd_kv]
   size_t slab_stride = 0;
+  // long-context decode attention: the segment partials of launch_attention_split, allocated only
+  // when n_ctx > ATTN_SPLIT_T (MX_NO_ATTN_SPLIT=1 for A/B: never), and the flag of the next forward: some row may
+  // have ctx > ATTN_SPLIT_T, so every <= 64-row attention takes the split form (the same bits for its short rows)
+  // and the FIN sites finish q|k|v with launch_qkv_finish first.  Part of every graph key.
+  float* attn_ws = nullptr;
+  bool long_fwd = false;
+  // ctx_max: the largest min(pos + 1, n_ctx) a row of the forward -- or of any step of its replays -- may reach
+  bool is_long(int ctx_max) const { return attn_ws && ctx_max > ATTN_SPLIT_T; }
+  bool is_long(const int32_t* pos, int n) const { return n > 0 && is_long(*std::max_element(pos, pos + n) + 1); }
+  // launch_attention, or its split form in a long forward (final q: at.slabs is never set there)
+  // -> 0, or -1 with nothing launched (a geometry the split form does not take; init_common admits none)
+  int attend(const AttnArgs& at, hipStream_t s) const {
+    if (long_fwd && at.M <= MAX_ROWS && !at.slabs) return launch_attention_split(at, attn_ws, s);
+    launch_attention(at, s);
+    return 0;
+  }
   float* gslabs = nullptr;  // split-K partials of small-M prefill GEMMs, [S][M][N] (launch_gemm_split)
   // K-quant model prefill: one layer's four matrices dequantised to packed bf16 for the GEMM path
   uint16_t *kqd_qkv = nullptr, *kqd_o = nullptr, *kqd_gu = nullptr, *kqd_down = nullptr;
@@ -393,7 +411,7 @@ struct mx_engine {
   // graphs for the scheduler's decode steps, by (M, top-k of the device sampling chain or 0 = argmax)
   // ... and the top-k of the round's log-probabilities (-1: none; such rounds enqueue what they always did)
   // ... and whether the round runs the extended chain (0: none; 1: bias / tail-free / typical; 2: Mirostat too;
-  // + 4: some row takes the wide kernel)
+  // + 4: some row takes the wide kernel; + 8: grammar masks; + 16: a long round, mx_engine::long_fwd)
   std::map<std::tuple<int, int, int, int>, hipGraphExec_t> sched_graphs;
   // pipeline stage hand-off dtype: x_in / x_out are bf16 [M][n_embd] instead of f32 (mx_opts.handoff_bf16)
   bool handoff_bf16 = false;
@@ -684,7 +702,7 @@ struct mx_engine {
   // of the round's requests -- their token sequences [SPEC_MAX_REQ][n_ctx] and lengths, {num_pred_tokens,
   // max_ngram_size}, draft lengths, the variable-length token history [SPEC_MAX_REQ][SCHED_KMAX * SPEC_ROWS]
   // with its counts, the counters [.][3] and the per-step log [.][SCHED_KMAX][2] = {n_draft, accepted}
-  std::map<std::pair<int, int>, hipGraphExec_t> spec_graphs;
+  std::map<std::tuple<int, int, bool>, hipGraphExec_t> spec_graphs;  // (R, D, long_fwd)
   int *spec_ctx = nullptr, *spec_len = nullptr, *spec_par = nullptr, *spec_ndraft = nullptr, *spec_hist = nullptr;
   int *spec_hist_count = nullptr, *spec_cnt = nullptr, *spec_log = nullptr;
   uint64_t stat_spec_steps = 0, stat_spec_drafted = 0, stat_spec_accepted = 0;
@@ -787,6 +805,8 @@ int mx_engine::init_common() {
   }
   slab_stride = (size_t)MAX_ROWS * (n_embd + 2 * n_embd_kv);
   if (int rc = alloc((void**)&slabs, slab_stride * 8 * 4)) return rc;
+  if (n_ctx > ATTN_SPLIT_T && getenv("MX_NO_ATTN_SPLIT") == nullptr)
+    if (int rc = alloc((void**)&attn_ws, attn_split_ws_floats(MAX_ROWS, n_head, head_dim) * 4)) return rc;
   if (gemm_shapes())
     if (int rc = alloc((void**)&gslabs, GSLAB_FLOATS * 4)) return rc;
   if ((wkq || (wq8 && !wq4 && q8_gemm_prefill)) && gemm_shapes()) {  // per-layer bf16 copies for the prefill GEMM
@@ -1539,7 +1559,7 @@ AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
 // other's new K/V take qkn_finish_kernel first.  a: qkv_args (q buffer, caches).
 void mx_engine::finish_raw_qkv(const MMArgs& a, AttnArgs& at, const float* raw, int nslab, size_t stride,
                                hipStream_t s) const {
-  if (rows_distinct && a.M <= MAX_ROWS) {
+  if (rows_distinct && a.M <= MAX_ROWS && !long_fwd) {  // a long forward attends in the split form: final q
     at.slabs = raw; at.nslab = nslab; at.slab_stride = stride; at.rope_cs = rope_cs; at.kc_w = a.kc; at.vc_w = a.vc;
   } else {
     launch_qkv_finish(a, raw, nslab, stride, s);
@@ -1622,7 +1642,7 @@ int mx_engine::enqueue_forward(const Forward& f, hipStream_t s) {
     if (use_pers && nol && mm_pers_supported(EPI_SWIGLU, M, 2 * ff, h)) {  // partials for gate/up's norm on load
       b.ssq = ssq; b.np = h / 16;
     }
-    launch_attention(at, s);
+    if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
     if ((mm_pers_supported(EPI_RESID, M, h, h) ? launch_mm_pers(EPI_RESID, b, s) : -1) != 0 &&
         launch_mm(EPI_RESID, b, s))
       return fail(MX_ERR_ARG, "attn_output launch shape");
@@ -1684,18 +1704,21 @@ int mx_engine::enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_c
     const int qsplit = launch_mm_wide(EPI_QKV, a, slabs, slab_stride, s, false, full_chain);
     if (qsplit < 0) return fail(MX_ERR_ARG, "wide qkv launch shape");
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
-    if (!rows_distinct) {  // rows of one sequence attend to each other's new K/V: finish them first
+    // rows of one sequence attend to each other's new K/V, and a long forward attends in the split form (§20):
+    // finish q|k|v first
+    const bool fin = rows_distinct && !long_fwd;
+    if (!fin) {
       launch_qkv_finish(a, slabs, qsplit, slab_stride, s);
       if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
     }
     AttnArgs at = attn_args(li, f);
     at.out = attn_out;
-    if (rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
+    if (fin) {  // the attention kernel finishes q/k/v from the split-K slabs
       at.slabs = slabs; at.nslab = qsplit; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
       at.vc_w = a.vc;
     }
     if (full_chain && rows_blocked) launch_attention_prefill(at, s);
-    else launch_attention(at, s);
+    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.X = attn_out; b.ldx = h; b.M = M;
@@ -1848,7 +1871,7 @@ int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
         if (mm(EPI_F32, r)) return fail(MX_ERR_ARG, fmt + " qkv launch shape");
       }
       finish_raw_qkv(a, at, qs > 0 ? slabs : raw, qs > 0 ? qs : 1, slab_stride, s);
-    } else if (qs > 0 && rows_distinct) {  // the attention kernel finishes q/k/v from the split-K slabs
+    } else if (qs > 0 && rows_distinct && !long_fwd) {  // the attention kernel finishes q/k/v from the split-K slabs
       at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
       at.vc_w = a.vc;
     } else if (qs > 0) {
@@ -1857,7 +1880,7 @@ int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
       return fail(MX_ERR_ARG, fmt + " qkv launch shape");
     }
     if (M > MAX_ROWS && rows_blocked) launch_attention_prefill(at, s);
-    else launch_attention(at, s);
+    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.M = M; b.out = x; b.ldo = h;
     if (operand(b, L.kq_o, attn_f, h, nullptr)) return fail(MX_ERR_ARG, fmt + " quantise shape");
@@ -1927,7 +1950,7 @@ int mx_engine::enqueue_forward_gemm(const Forward& f, hipStream_t s) {
     AttnArgs at = attn_args(li, f);
     at.out = attn_out;
     if (rows_blocked) launch_attention_prefill(at, s);
-    else launch_attention(at, s);
+    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
     MMArgs b{};
     b.W = Wo; b.N = h; b.K = h; b.X = attn_out; b.ldx = h; b.M = M; b.out = x; b.ldo = h;
     if ((nslab = launch_gemm_split(EPI_RESID, b, gslabs, GSLAB_FLOATS, gemm_split_target, s)) < 0)
@@ -2008,6 +2031,7 @@ int mx_engine::forward_rows_chunk(int n, const int32_t* slots, const int32_t* po
   std::sort(sorted.begin(), sorted.end());
   rows_distinct = std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
   rows_blocked = blocked_rows(slots, pos, x_in ? nullptr : ids, n);
+  long_fwd = is_long(pos, n);
   if (head && last_row_only) {
     const int32_t last = n - 1;
     if (int rc = h2d(d_rowmap, &last, 1, 3)) return rc;
@@ -2017,6 +2041,7 @@ int mx_engine::forward_rows_chunk(int n, const int32_t* slots, const int32_t* po
                                   s);
   rows_distinct = false;
   rows_blocked = false;
+  long_fwd = false;
   if (frc) {  // the index copies enqueued above still read h_idx: drain them before it is reused
     hipStreamSynchronize(s);
     return frc;
@@ -2548,11 +2573,13 @@ int mx_engine::prefill_batch(std::vector<Request*>& admitted) {
     if (n_out) HIPC(hipMemcpyAsync(d_rowmap, rowmap.data(), n_out * 4, hipMemcpyHostToDevice, st));
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data() + i, pos.data() + i, ids.data() + i, m);
+    long_fwd = is_long(pos.data() + i, m);
     prefill_gemm = true;
     const int frc = enqueue_forward({.M = m, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = n_out > 0,
                                      .rowmap = n_out ? d_rowmap : nullptr, .n_out = n_out},
                                     st);
     rows_blocked = false;
+    long_fwd = false;
     prefill_gemm = false;
     if (frc) return frc;
     int ktop = 0, lpk = -1;  // lpk: log-probabilities of the first tokens, from these raw last-row logits
@@ -2669,10 +2696,12 @@ int mx_engine::prefill_prompt_logprobs(Request* r) {
     HIPC(hipMemcpyAsync(lp_tgt, tgt.data(), m * 4, hipMemcpyHostToDevice, st));
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data(), pos.data(), ids.data(), mp);
+    long_fwd = is_long(pos.data(), mp);
     prefill_gemm = true;
     const int frc = enqueue_forward(
         {.M = mp, .ids = d_ids, .pos = d_pos, .slot = d_slot, .head = true, .rowmap = d_rowmap, .n_out = m}, st);
     rows_blocked = false;
+    long_fwd = false;
     prefill_gemm = false;
     if (frc) {
       hipStreamSynchronize(st);
@@ -2739,9 +2768,11 @@ int mx_engine::prefill_embed(std::vector<Request*>& reqs) {
     HIPC(hipMemcpyAsync(d_slot, slots.data() + i, m * 4, hipMemcpyHostToDevice, st));
     rows_distinct = false;
     rows_blocked = blocked_rows(slots.data() + i, pos.data() + i, ids.data() + i, m);
+    long_fwd = is_long(pos.data() + i, m);
     prefill_gemm = true;
     const int frc = enqueue_forward({.M = m, .ids = d_ids, .pos = d_pos, .slot = d_slot}, st);
     rows_blocked = false;
+    long_fwd = false;
     prefill_gemm = false;
     if (frc) {
       hipStreamSynchronize(st);
@@ -2850,6 +2881,14 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
     while (K >= 1 && r->pos + K * (1 + D) + D > n_ctx - 1) K--;
   if (K < 1) return 0;  // close to n_ctx: the plain round reaches the last positions
   const int M = R * (1 + D), HS = SCHED_KMAX * SPEC_ROWS;
+  // the round's last step attends up to position pos + (K - 1)(1 + D) + D: long when that context passes the threshold
+  int ctx_max = 0;
+  for (const Request* r : rows) ctx_max = std::max(ctx_max, r->pos + K * (1 + D));
+  long_fwd = is_long(ctx_max);
+  struct ResetLong {
+    mx_engine* e;
+    ~ResetLong() { e->long_fwd = false; }
+  } reset_long{this};
   std::vector<int32_t> ids(M), pos(M), slots(M), par(2 * R), len(R);
   std::vector<std::vector<int32_t>> ctx(R);
   hipStream_t s = stream;
@@ -2888,7 +2927,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   bool captured = false;
-  auto it = spec_graphs.find({R, D});
+  auto it = spec_graphs.find({R, D, long_fwd});
   if (use_graphs && it == spec_graphs.end()) {
     captured = true;
     hipGraph_t g;
@@ -2900,7 +2939,7 @@ int mx_engine::sched_step_spec(std::vector<Request*>& rows) {
     hipGraphExec_t ex;
     HIPC(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
     hipGraphDestroy(g);
-    it = spec_graphs.emplace(std::make_pair(R, D), ex).first;
+    it = spec_graphs.emplace(std::make_tuple(R, D, long_fwd), ex).first;
   }
   for (int k = 0; k < K; k++) {
     if (use_graphs) HIPC(hipGraphLaunch(it->second, s));
@@ -3007,7 +3046,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   struct Reset {
     mx_engine* e;
     ~Reset() {
-      e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1;
+      e->rows_distinct = false; e->long_fwd = false; e->pick_samp = nullptr; e->pick_k = 0; e->pick_lp = -1;
       e->pick_ext = nullptr; e->pick_miro = false; e->pick_wide = false; e->pick_gram = false;
     }
   } reset_flags{this};
@@ -3018,6 +3057,8 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   const int gl = any_gram ? upload_gram(rows.data(), M, s) : 0;
   if (gl < 0) return fail(MX_ERR_HIP, "grammar mask copy");
   rows_distinct = true;  // one row per active request, each its own slot
+  // the round's last step attends [0, pos + K - 1]: long when that context passes the threshold (the host mirror)
+  long_fwd = is_long(*std::max_element(pos.begin(), pos.end()) + K);
   pick_samp = dev_chain ? d_samp : nullptr;
   pick_k = dev_chain ? ktop : 0;
   pick_lp = lpk;
@@ -3031,7 +3072,7 @@ int mx_engine::sched_step(std::vector<Request*>& rows) {
   static const bool trace = getenv("MX_SCHED_TRACE") != nullptr;  // per-round timing on stderr
   const auto t0 = std::chrono::steady_clock::now();
   bool captured = false;
-  const std::tuple<int, int, int, int> gkey(M, pick_k, pick_lp, xl | (gl ? 8 : 0));
+  const std::tuple<int, int, int, int> gkey(M, pick_k, pick_lp, xl | (gl ? 8 : 0) | (long_fwd ? 16 : 0));
   auto it = sched_graphs.find(gkey);
   if (use_graphs && it == sched_graphs.end()) {
     captured = true;
@@ -4117,15 +4158,17 @@ int mx_batch_step(mx_engine* e, mx_batch* b, const void* x_in, void* x_out, void
   const bool head = x_out == nullptr;
   if (b->max_pos >= e->n_ctx) return fail(MX_ERR_CTX, "decode batch reached n_ctx");
   b->max_pos++;
+  const bool long_ctx = e->is_long(b->max_pos);  // max_pos is now this step's largest context
   if (head && !e->has_head) return fail(MX_ERR_STATE, "x_out is required on a non-final pipeline stage");
   if (!x_in && !e->has_embed) return fail(MX_ERR_STATE, "x_in is required on a non-first pipeline stage");
   auto body = [&]() -> int {
     e->rows_distinct = b->distinct;
+    e->long_fwd = long_ctx;
     e->pick_samp = head && b->ktop > 0 ? b->d_samp : nullptr;
     e->pick_k = head ? b->ktop : 0;
     struct Reset {
       mx_engine* e;
-      ~Reset() { e->rows_distinct = false; e->pick_samp = nullptr; e->pick_k = 0; }
+      ~Reset() { e->rows_distinct = false; e->long_fwd = false; e->pick_samp = nullptr; e->pick_k = 0; }
     } reset_flags{e};
     if (int rc = e->enqueue_forward(
             {.M = b->M, .ids = b->d_ids, .pos = b->d_pos, .slot = b->d_slot, .x_in = x_in, .x_out = x_out, .head = head,
@@ -4138,7 +4181,7 @@ int mx_batch_step(mx_engine* e, mx_batch* b, const void* x_in, void* x_out, void
     return 0;
   };
   if (!e->use_graphs) return body();
-  GraphKey key{b->M, x_in, x_out, s, head ? b->ktop : 0};
+  GraphKey key{b->M, x_in, x_out, s, head ? b->ktop : 0, long_ctx};
   auto it = b->graphs.find(key);
   if (it == b->graphs.end()) {
     hipGraph_t g;
@@ -4290,6 +4333,7 @@ int mx_stage_rows_pick(mx_engine* e, int n, const int32_t* slots, const int32_t*
     }
     e->rows_distinct = false;
     e->rows_blocked = blocked_rows(slots + i, pos + i, x_in ? nullptr : ids + i, m);
+    e->long_fwd = e->is_long(pos + i, m);
     e->prefill_gemm = true;
     e->pick_samp = ktop > 0 ? e->d_samp : nullptr;
     e->pick_k = ktop;
@@ -4300,6 +4344,7 @@ int mx_stage_rows_pick(mx_engine* e, int n, const int32_t* slots, const int32_t*
                                         .head = no > 0, .rowmap = no ? e->d_rowmap : nullptr, .n_out = no},
                                        s);
     e->rows_blocked = false;
+    e->long_fwd = false;
     e->prefill_gemm = false;
     if (!frc && no) e->pick(no, PickOut{}, s);  // logits rows [no][V]
     e->pick_samp = nullptr;
@@ -4546,6 +4591,8 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
           at.kc_w = e->kcache + e->layer_kv_stride * li; at.vc_w = e->vcache + e->layer_kv_stride * li;
         }
         per = (size_t)M * (prof_pos + 1) * kv * 2 * 2;
+        // as a forward at these positions runs it: the split form (two launches) past the threshold
+        if (!prof_fin && M <= MAX_ROWS && e->is_long(prof_pos + 1)) return launch_attention_split(at, e->attn_ws, s);
         launch_attention(at, s);
         return 0;
       }
@@ -4574,6 +4621,10 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
   HIPC(hipEventElapsedTime(&ms, t0, t1));
   hipEventDestroy(t0);
   hipEventDestroy(t1);
+  if (kind == 7 && getenv("MX_ATTN_TRACE") && !prof_fin && M <= MAX_ROWS && e->is_long(prof_pos + 1)) {
+    fprintf(stderr, "MX_ATTN_TRACE: the timed form here is launch_attention_split (two launches); the phase trace "
+                    "below is of the unsplit attn_decode_kernel at the same positions\n");
+  }
   if (kind == 7 && getenv("MX_ATTN_TRACE")) {  // diagnosis: phase stamps of one launch (layer 0)
     const size_t n = (size_t)M * e->n_head_kv * 8 * 8;
     unsigned long long* tr = nullptr;

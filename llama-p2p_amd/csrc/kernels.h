@@ -180,6 +180,33 @@ int launch_mm_wide(int epi, const MMArgs& a, float* slabs, size_t slab_stride, h
 void launch_resid_norm(uint16_t* y, int ldy, float* x, const float* slabs, int nslab, size_t slab_stride,
                        const float* w, int M, int n, float eps, hipStream_t s);  // X == nullptr path (RMS_NORM fused into the GEMV) is legal
 void launch_attention(const AttnArgs& a, hipStream_t s);
+// ---- long-context decode attention (attn_split.hip): a row whose context ctx = min(pos + 1, n_ctx)
+// exceeds ATTN_SPLIT_T is cut into attn_nseg(ctx) segments of attn_seg_len(ctx) positions, one work-group per (kv
+// head, row, segment), merged by a second kernel in segment order.  Both are functions of ctx alone -- never of the
+// row count, n_ctx or the launch's other rows -- so a row's summation order is its own (batch invariance).
+#ifndef MX_ATTN_SPLIT_T  // -DMX_ATTN_SPLIT_T= / _NSEG_MAX= / _SEG_MIN=: sweep builds only (profiles/long_context_attention.txt)
+#define MX_ATTN_SPLIT_T 2048
+#define MX_ATTN_NSEG_MAX 16
+#define MX_ATTN_SEG_MIN 1024
+#endif
+constexpr int ATTN_SPLIT_T = MX_ATTN_SPLIT_T;    // rows up to here: one segment, launch_attention's bits
+constexpr int ATTN_NSEG_MAX = MX_ATTN_NSEG_MAX;  // grid.z of the split launch
+constexpr int ATTN_SEG_MIN = MX_ATTN_SEG_MIN;    // a multiple of 8 waves x ATTN_CHUNK = 256: every wave of a full segment has a chunk
+static_assert(ATTN_SPLIT_T >= 2048 && ATTN_SEG_MIN % 256 == 0 && ATTN_NSEG_MAX >= 2, "segment rule (DESIGN.md §20)");
+__host__ __device__ inline int attn_seg_len(int ctx) {
+  const int per = (ctx + ATTN_NSEG_MAX - 1) / ATTN_NSEG_MAX;
+  const int len = (per + ATTN_SEG_MIN - 1) / ATTN_SEG_MIN * ATTN_SEG_MIN;
+  return len < ATTN_SEG_MIN ? ATTN_SEG_MIN : len;
+}
+__host__ __device__ inline int attn_nseg(int ctx) {
+  return ctx <= ATTN_SPLIT_T ? 1 : (ctx + attn_seg_len(ctx) - 1) / attn_seg_len(ctx);
+}
+// floats of the workspace for launches of up to M rows: [row][q head][ATTN_NSEG_MAX][head_dim + 4] (m, l, -, -, acc)
+size_t attn_split_ws_floats(int M, int n_head, int head_dim);
+// launch_attention's non-FIN decode form (final q in a.q, a.M <= MAX_ROWS) with long rows split; a row of one
+// segment gets launch_attention's bits.  Two launches (segments, merge).  -1 and nothing launched for a.slabs,
+// a.M > MAX_ROWS, a head_dim other than 64 / 128 or a GQA group outside {1, 2, 4, 5, 6, 7, 8}.
+int launch_attention_split(const AttnArgs& a, float* ws, hipStream_t s);
 // rows in blocks of 16 consecutive positions of one sequence each (prefill chunks): one
 // work-group per (kv head, block), the 16 queries share every K/V chunk
 void launch_attention_prefill(const AttnArgs& a, hipStream_t s);

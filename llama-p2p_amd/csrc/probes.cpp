@@ -392,6 +392,68 @@ int mx_attention_probe(int device, int mode, int n_head, int n_head_kv, int head
   return 0;
 }
 
+int mx_attention_split_plan(int ctx, int32_t* threshold, int32_t* nseg_max, int32_t* nseg, int32_t* seg_len) {
+  if (ctx < 1 || ctx > (1 << 20) || !threshold || !nseg_max || !nseg || !seg_len)
+    return fail(MX_ERR_ARG, "mx_attention_split_plan: 1 <= ctx <= 2^20, non-null outputs");
+  *threshold = ATTN_SPLIT_T; *nseg_max = ATTN_NSEG_MAX; *nseg = attn_nseg(ctx); *seg_len = attn_seg_len(ctx);
+  return 0;
+}
+
+int mx_attention_long_probe(int device, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                            const int32_t* pos, const int32_t* slot, int out_f32, const float* q, void* kcache,
+                            void* vcache, void* out) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  if (!pos || !slot || !q || !kcache || !vcache || !out)
+    return fail(MX_ERR_ARG, "mx_attention_long_probe: non-null pos / slot / q / caches / out");
+  if ((head_dim != 64 && head_dim != 128) || n_head_kv < 1 || n_head < n_head_kv || n_head % n_head_kv != 0 ||
+      n_head > 1024)
+    return fail(MX_ERR_ARG, "mx_attention_long_probe: head_dim 64 or 128, n_head a multiple of n_head_kv");
+  const int G = n_head / n_head_kv;
+  if (G != 1 && G != 2 && (G < 4 || G > 8))
+    return fail(MX_ERR_ARG, "mx_attention_long_probe: n_head / n_head_kv must be 1, 2 or 4..8");
+  if (n_ctx < 1 || n_ctx > (1 << 20) || n_slots < 1 || n_slots > 4096)
+    return fail(MX_ERR_ARG, "mx_attention_long_probe: 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+  if (M < 1 || M > MAX_ROWS) return fail(MX_ERR_ARG, "mx_attention_long_probe: 1 <= M <= 64 rows");
+  KvGeom g;
+  if (int rc = g.set("mx_attention_long_probe", n_head_kv, head_dim, n_ctx, n_slots)) return rc;
+  for (int i = 0; i < M; i++) {
+    if (slot[i] < 0 || slot[i] >= n_slots) return fail(MX_ERR_ARG, "mx_attention_long_probe: slot out of range");
+    if (pos[i] < 0 || pos[i] > n_ctx) return fail(MX_ERR_ARG, "mx_attention_long_probe: position outside [0, n_ctx]");
+  }
+  const size_t nq = (size_t)n_head * head_dim;
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  float *d_q = nullptr, *d_ws = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr;
+  void* d_out = nullptr;
+  // out: M rows and a guard of MAX_ROWS - M more, all 0xFF; the workspace 0xFF too (a record read before it is
+  // written shows as NaN)
+  const size_t out_bytes = (size_t)MAX_ROWS * nq * (out_f32 ? 4 : 2);
+  if (!dev.alloc(&d_k, g.cache_elems * 2) || !dev.alloc(&d_v, g.cache_elems * 2) || !dev.alloc(&d_pos, (size_t)M * 4) ||
+      !dev.alloc(&d_slot, (size_t)M * 4) || !dev.alloc_ff(&d_out, out_bytes) || !dev.alloc(&d_q, (size_t)M * nq * 4) ||
+      !dev.alloc_ff(&d_ws, attn_split_ws_floats(M, n_head, head_dim) * 4))
+    return fail(MX_ERR_HIP, "mx_attention_long_probe: device allocation");
+  HIPC(hipMemcpy(d_k, kcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_v, vcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_pos, pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_slot, slot, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_q, q, (size_t)M * nq * 4, hipMemcpyHostToDevice));
+  AttnArgs at{};
+  at.q = d_q; at.kc = d_k; at.vc = d_v; at.pos = d_pos; at.slot = d_slot;
+  if (out_f32) at.outf = (float*)d_out;
+  else at.out = (uint16_t*)d_out;
+  at.ldo = (int)nq; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
+  at.n_ctx = n_ctx; at.ctx_stride = g.ctx_stride; at.slot_stride = g.slot_stride;
+  at.scale = 1.0f / sqrtf((float)head_dim);
+  HIPC(hipDeviceSynchronize());
+  if (launch_attention_split(at, d_ws, nullptr)) return fail(MX_ERR_ARG, "mx_attention_long_probe: launch shape");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
                  const int32_t* pos, const int32_t* slot, const float* slabs, int nslab, const float* rope_cs,
                  const float* q_norm, const float* k_norm, float eps, void* kcache, void* vcache, float* q_out,

@@ -32,7 +32,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
-    "mx_attention_probe", "mx_qkn_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
+    "mx_attention_probe", "mx_attention_split_plan", "mx_attention_long_probe", "mx_qkn_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
@@ -324,6 +324,8 @@ def lib() -> ctypes.CDLL:
         L.mx_logprob_probe.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
         L.mx_attention_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
                                          vp, vp]
+        L.mx_attention_split_plan.argtypes = [i32, P(i32), P(i32), P(i32), P(i32)]
+        L.mx_attention_long_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
         L.mx_qkn_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.c_float,
                                    vp, vp, vp, vp]
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
@@ -619,6 +621,45 @@ def attention_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
     return out, kc, vc
+
+
+def attention_split_plan(ctx: int) -> dict:
+    """The long-context attention's segment rule for a row of context ctx (mx_attention_split_plan; no GPU):
+    threshold (rows up to it run as one segment), nseg_max, nseg and seg_len of this ctx."""
+    v = [ctypes.c_int32() for _ in range(4)]
+    _check(lib().mx_attention_split_plan(ctx, *[ctypes.byref(c) for c in v]))
+    return dict(zip(("threshold", "nseg_max", "nseg", "seg_len"), (c.value for c in v)))
+
+
+def attention_long_probe(n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot, kcache,
+                         vcache, q, out_f32: bool = True, device: int = 0):
+    """launch_attention_split on caller-supplied final q / K / V (no engine; include/mx_engine.h
+    mx_attention_long_probe): attention_probe's mode 0 with long rows split over work-groups, M <= 64.  Returns
+    (out [M][n_head * head_dim] as f32 -- a bf16 output widened exactly --, guard: the raw bytes of the output rows
+    past M, which must all be 0xFF)."""
+    pos, slot = _i32(pos), _i32(slot)
+    M = len(pos)
+    if len(slot) != M:
+        raise ValueError("one slot per row")
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    elems = max(n_slots, 0) * max(n_head_kv, 0) * ctx_stride * max(head_dim, 0)
+    kc = np.ascontiguousarray(kcache, dtype=np.uint16).reshape(-1)
+    vc = np.ascontiguousarray(vcache, dtype=np.uint16).reshape(-1)
+    if kc.size != elems or vc.size != elems:
+        raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+    nq = max(n_head * head_dim, 0)
+    qa = np.ascontiguousarray(q, dtype=np.float32)
+    if qa.size != M * nq:
+        raise ValueError("q [M][n_head * head_dim] expected")
+    out = np.empty((64, nq), dtype=np.float32 if out_f32 else np.uint16)
+    _check(lib().mx_attention_long_probe(device, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
+                                         slot.ctypes.data, int(bool(out_f32)), qa.ctypes.data, kc.ctypes.data,
+                                         vc.ctypes.data, out.ctypes.data))
+    guard = out[min(M, 64):].view(np.uint8).copy()
+    out = out[:M]
+    if not out_f32:
+        out = (out.astype(np.uint32) << 16).view(np.float32)
+    return out, guard
 
 
 def qkn_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot, kcache,
