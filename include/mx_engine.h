@@ -83,7 +83,7 @@ typedef struct {
   int32_t n_ctx, n_seq_max;
   int32_t layer_begin, layer_end, has_embed, has_head;
   uint64_t weight_bytes; /* device bytes of the weights this stage streams per decode step */
-  int32_t weight_type;       /* ggml type of the layer matrices: 30 BF16, 8 Q8_0, 2 Q4_0, 12 Q4_K (Q4_K_M), 13 Q5_K (Q5_K_M) */
+  int32_t weight_type;       /* ggml type of the layer matrices: 30 BF16, 8 Q8_0, 2 Q4_0, 12 Q4_K (Q4_K_M), 13 Q5_K (Q5_K_M), 23 IQ4_XS */
   int32_t eot_id;            /* tokenizer.ggml.eot_token_id: ends a request like eos_id; -1 when the file has none */
 } mx_model_info;
 
@@ -117,9 +117,9 @@ void mx_opts_default(mx_opts* o);
 void mx_sampling_default(mx_sampling* s);
 const char* mx_last_error(void);
 
-/* model_path: a GGUF file (LLaMA; all-BF16, all-Q8_0, all-Q4_0 and Q4_K_M / Q5_K_M files natively -- the
+/* model_path: a GGUF file (LLaMA; all-BF16, all-Q8_0, all-Q4_0 and Q4_K_M / Q5_K_M / IQ4_XS files natively -- the
  * quantised ones on the int8 MFMA with ggml's arithmetic; any other mix of F32 / F16 / BF16 / Q4_0 / Q8_0
- * / K-quant matrices dequantised to bf16 at load) or "synthetic:<shape>[:seed=N][:q8_0|:q4_0|:q4_k_m|:q5_k_m]" */
+ * / K-quant / IQ4_XS matrices dequantised to bf16 at load) or "synthetic:<shape>[:seed=N][:q8_0|:q4_0|:q4_k_m|:q5_k_m|:iq4_xs]" */
 int mx_engine_create(const char* model_path, const mx_opts* opts, mx_engine** out);
 void mx_engine_destroy(mx_engine* e);
 /* Parse a GGUF container without touching a GPU (header, metadata, tensor table, bounds of every
@@ -595,7 +595,7 @@ int mx_q8_matmul_plan(int epi, int M, int N, int K, int wq4, int on_load, int no
  * and, optionally, ssq_out [M + 64][K/16].  Outputs start as 0xFF bytes. */
 int mx_q8_side_probe(int device, int mode, int N, int K, const void* blocks, const int32_t* ids, int M, void* out,
                      float* ssq_out);
-/* The production K-quant (Q4_K 12, Q5_K 13, Q6_K 14) launchers on caller-supplied operands, no engine.
+/* The production K-quant (Q4_K 12, Q5_K 13, Q6_K 14, IQ4_XS 23) launchers on caller-supplied operands, no engine.
  * path 0 launch_mkq (whatever it dispatches, M 1..4096); path 1 launch_mkq_slab (17..32 rows, RESID) finished as
  * the engine finishes it: the slabs folded by the next launch_rmsnorm_q8k (weights fold_w [N]; out receives the
  * folded x, nxq_out / nxd_out / nxb_out that norm's Q8_K rows [M + 64][N], [N/256], [N/32]; N > 4096, where that

@@ -273,6 +273,15 @@ __device__ __forceinline__ void scale_min_k4(int j, const uint8_t* q, int& sc, i
     m = (q[j + 4] >> 4) | ((q[j] >> 6) << 4);
   }
 }
+// IQ4_XS (ggml-common.h block_iq4_xs {d, scales_h, scales_l[4], qs[128]}): the codebook kvalues_iq4nl,
+// and the 6-bit scale of sub-block j before the -32
+__device__ __forceinline__ int iq4_kv(int i) {
+  constexpr int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+  return kv[i];
+}
+__device__ __forceinline__ int iq4_ls(const uint8_t* b, int j) {
+  return ((b[4 + (j >> 1)] >> (4 * (j & 1))) & 15) | ((((b[2] | (b[3] << 8)) >> (2 * j)) & 3) << 4);
+}
 
 // Reductions over the 16 lanes of a DPP row (the 16 positions of one C-layout row): rotations
 // within the row, so every lane ends with the result.  One VOP2-DPP instruction per step (the

@@ -174,9 +174,11 @@ struct KqMat {
 // ggml type of a tensor in llama.cpp's Q4_K_M / Q5_K_M recipes (llama_tensor_get_type, Oct 2024;
 // synth.py kq_tensor_type is the same rule): output Q6_K; attn_v and ffn_down Q6_K on the
 // use_more_bits layers; attn_v of an 80-layer (70B) Q4_K_M model otherwise Q5_K; the rest `base`.
+// IQ4_XS (base 23): output Q6_K, attn_v Q5_K, ffn_down Q5_K in the first n_layer / 8 layers.
 bool use_more_bits(int i, int n) { return i < n / 8 || i >= 7 * n / 8 || (i - n / 8) % 3 == 2; }
 int kq_recipe_type(int base, int kind, int layer, int n_layer) {  // kind: L_* or -1 output, -2 token_embd
   if (kind == -1) return 14;
+  if (base == 23) return kind == 3 || (kind == 8 && layer < n_layer / 8) ? 13 : 23;
   if ((kind == 3 || kind == 8) && use_more_bits(layer, n_layer)) return 14;  // L_V, L_DOWN
   if (kind == 3 && n_layer == 80 && base == 12) return 13;
   return base;
@@ -1109,7 +1111,7 @@ int mx_engine::load_gguf(const std::string& path) {
   }
   if (le < 0 || le > n_layer) le = n_layer;
   // Matrix types.  All BF16 -> the bf16 path; all Q8_0 -> the Q8_0 path (int8 MFMA on the blocks);
-  // all Q4_K / Q5_K / Q6_K with ffn_gate and ffn_up of one type (llama.cpp's Q4_K_M, Q5_K_M files) ->
+  // all Q4_K / Q5_K / Q6_K / IQ4_XS with ffn_gate and ffn_up of one type (llama.cpp's Q4_K_M, Q5_K_M files) ->
   // the K-quant path (kquant.hip: int8 MFMA on the blocks with Q8_K activations); any other mix of
   // F32 / F16 / BF16 / Q4_0 / Q8_0 / K-quants -> every matrix is dequantised to bf16 at load
   // (ggml's dequantize_row_*) and runs on the bf16 path.
@@ -1128,11 +1130,11 @@ int mx_engine::load_gguf(const std::string& path) {
       if (!t) return fail(MX_ERR_MODEL, "missing tensor " + nm);
       if (t->type != 30 && !ggml_block_elems(t->type))
         return fail(MX_ERR_MODEL, "tensor " + nm + ": ggml type " + std::to_string(t->type) +
-                                      " is not supported (F32, F16, BF16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K are)");
+                                      " is not supported (F32, F16, BF16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, IQ4_XS are)");
       n8 += t->type == 8;
       n4 += t->type == 2 && nm != mats.back();  // layer matrices only (the head is checked below)
       n30 += t->type == 30;
-      nkq += t->type == 12 || t->type == 13 || t->type == 14;
+      nkq += kq_tile_bytes(t->type) != 0;  // Q4_K, Q5_K, Q6_K, IQ4_XS
       raw_max = std::max(raw_max, (size_t)t->nbytes);
     }
     wq8 = out_q8 = n8 == (int)mats.size();
@@ -1156,7 +1158,7 @@ int mx_engine::load_gguf(const std::string& path) {
     deq = !wq8 && !wkq && n30 != (int)mats.size();
     if (wq8 && !out_q8) deq = false;
     embd_q8 = te->type == 8;
-    if (wkq && (te->type == 12 || te->type == 13 || te->type == 14)) embd_kq_type = te->type;
+    if (wkq && kq_tile_bytes(te->type)) embd_kq_type = te->type;
     if (lora) {
       // an adapter is merged into bf16 matrices: the native Q8_0 / Q4_0 / K-quant paths are off and every
       // matrix, token_embd included, is dequantised to bf16 at load -- the model a BF16 file of the merged
@@ -3543,6 +3545,7 @@ static int engine_create(const char* model_path, const mx_opts* opts, std::uniqu
         else if (part == "q4_0") q4 = true;
         else if (part == "q4_k_m") kq = 12;
         else if (part == "q5_k_m") kq = 13;
+        else if (part == "iq4_xs") kq = 23;
         else if (part != "bf16") return fail(MX_ERR_MODEL, "unknown synthetic option '" + part + "'");
         tail = e2 == std::string::npos ? "" : tail.substr(e2 + 1);
       }

@@ -70,6 +70,7 @@ uint64_t type_bytes(int type, uint64_t n) {
     case 12: blk = 256, bb = 144; break;     // Q4_K
     case 13: blk = 256, bb = 176; break;     // Q5_K
     case 14: blk = 256, bb = 210; break;     // Q6_K
+    case 23: blk = 256, bb = 136; break;     // IQ4_XS
     default: return 0;
   }
   if (n % blk) return 0;

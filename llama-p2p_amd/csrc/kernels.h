@@ -243,7 +243,7 @@ int launch_dequant_q8_tiles(uint16_t* dst, const uint8_t* W, int N, int K, hipSt
 void launch_synth_q8_packed(uint8_t* dst, int N, int K, uint64_t seed, uint64_t tid, float scale, int mode,
                             int row_offset, hipStream_t s);
 void launch_synth_q8_rowmajor(uint8_t* dst, int N, int K, uint64_t seed, uint64_t tid, float scale, hipStream_t s);
-// any GGUF matrix type (F32 0, F16 1, Q4_0 2, Q8_0 8, Q4_K 12, Q5_K 13, Q6_K 14) -> bf16 row-major,
+// any GGUF matrix type (F32 0, F16 1, Q4_0 2, Q8_0 8, Q4_K 12, Q5_K 13, Q6_K 14, IQ4_XS 23) -> bf16 row-major,
 // n elements (ggml dequantize_row_*, then RNE to bf16); -1 for an unsupported type or ragged n
 int ggml_block_elems(int type);
 int launch_dequant_bf16(uint16_t* dst, const uint8_t* src, int type, size_t n, hipStream_t s);
@@ -291,18 +291,18 @@ Mq8Plan mq8_plan(int epi, int M, int N, int K, bool wq4, bool on_load, bool norm
 // split of launch_mq8_slab for a shape, -1 = it refuses (the conditions on the shape alone)
 int mq8_slab_ks(int M, int N, int K);
 
-// ---- K-quant weights (GGUF Q4_K 12, Q5_K 13, Q6_K 14), kquant.hip.  Packed tile =
+// ---- K-quant weights (GGUF Q4_K 12, Q5_K 13, Q6_K 14, IQ4_XS 23), kquant.hip.  Packed tile =
 // 16 rows x 256 k (one super-block per row) in MFMA operand lane order: kq_tile_bytes(type) bytes
-// (2368 / 2880 / 3360), tiles nt-major like the bf16 tiles.
+// (2368 / 2880 / 3360 / 2208), tiles nt-major like the bf16 tiles.
 int kq_tile_bytes(int type);  // 0 for a type without a K-quant tile
-int kq_block_bytes(int type);  // GGUF block bytes per 256 weights (144 / 176 / 210)
+int kq_block_bytes(int type);  // GGUF block bytes per 256 weights (144 / 176 / 210 / 136)
 inline size_t kq_matrix_bytes(int type, int N, int K) { return (size_t)N / 16 * (K / 256) * kq_tile_bytes(type); }
 // GGUF blocks [N][K/256] -> packed tiles (packed_row modes as launch_pack); -1 for a bad type/shape
 int launch_pack_kq(uint8_t* dst, const uint8_t* src_blocks, int type, int N, int K, int mode, int row_offset,
                    hipStream_t s);
 // the synthetic model's GGUF blocks (synth.py kq_blocks), row-major
 int launch_synth_kq_blocks(uint8_t* dst, int type, size_t nblocks, uint64_t seed, uint64_t tid, hipStream_t s);
-// GET_ROWS of a K-quant token_embd (dequantize_row_q{4,5,6}_K, f32)
+// GET_ROWS of a K-quant token_embd (dequantize_row_q{4,5,6}_K / dequantize_row_iq4_xs, f32)
 // ssq (optional): per-16-element-tile sums of squares of each embedded row (quantise-on-load consumers)
 int launch_embed_kq(float* x, const uint8_t* tok_blocks, int type, const int* ids, int M, int n, float* ssq,
                     hipStream_t s);

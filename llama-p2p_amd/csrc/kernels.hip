@@ -3566,13 +3566,24 @@ __global__ void dequant_bf16_kernel(uint16_t* dst, const uint8_t* src, int type,
           for (int i = 0; i < 4; ++i)
             y[128 * h + 32 * i + l] = (uint16_t)f2bf_nan((d * (float)sc[8 * h + l / 16 + 2 * i]) * (float)qv[i]);
         }
+    } else if (type == 23) {  // IQ4_XS (dequantize_row_iq4_xs)
+      const uint8_t* x = src + b * 136;
+      const float d = f16b(x);
+      uint16_t* y = dst + b * 256;
+      for (int j = 0; j < 8; ++j) {
+        const float dl = d * (float)(iq4_ls(x, j) - 32);
+        for (int l = 0; l < 16; ++l) {
+          y[32 * j + l] = (uint16_t)f2bf_nan(dl * (float)iq4_kv(x[8 + 16 * j + l] & 15));
+          y[32 * j + 16 + l] = (uint16_t)f2bf_nan(dl * (float)iq4_kv(x[8 + 16 * j + l] >> 4));
+        }
+      }
     }
   }
 }
 int ggml_block_elems(int type) {
   switch (type) {
     case 0: case 1: case 2: case 8: return 32;
-    case 12: case 13: case 14: return 256;
+    case 12: case 13: case 14: case 23: return 256;
   }
   return 0;
 }

@@ -1,4 +1,5 @@
-// kquant.hip -- K-quant weights (GGUF Q4_K, Q5_K, Q6_K) on the int8 MFMA path  (SURVEY §8a a16).
+// kquant.hip -- K-quant weights (GGUF Q4_K, Q5_K, Q6_K, and IQ4_XS's codebook form) on the int8 MFMA path
+// (IQ4_XS: DESIGN.md §21).
 //
 // llama.cpp runs a K-quant MUL_MAT as ggml_vec_dot_q{4,5,6}_K_q8_K: the f32 activation row is
 // quantised to Q8_K (per 256 values: iscale = -127/max, q = nearest_int(iscale*x), d = 1/iscale,
@@ -6,6 +7,8 @@
 //   Q4_K / Q5_K:  S = sum_j sc_j * (q_w . q_x over 32-value sub-block j),  Mn = sum_j m_j * bsum32_j
 //   Q6_K:         S = sum_g sc_g * (q_w . q_x over 16-value group g)        (q_w = 6-bit value - 32)
 // scaled in f32:  acc += (f16(d) * d_x) * S  -  (f16(dmin) * d_x) * Mn.
+// IQ4_XS (ggml_vec_dot_iq4_xs_q8_K) has Q4_K's shape with q_w = kvalues_iq4nl[4-bit index], signed scales
+// ls_j - 32 and no mins: S = sum_j (ls_j - 32) * (q_w . q_x over sub-block j), acc += (f16(d) * d_x) * S.
 // Here the q_w . q_x products run on v_mfma_i32_16x16x32_i8 (16 rows x 16 tokens x one 32-k
 // sub-block; Q6_K two per sub-block, each with the lanes of the other 16-k group zeroed), the
 // mins term on v_mfma_f32_16x16x4_f32 (exact: every operand and sum is an integer < 2^24) and the
@@ -37,6 +40,10 @@ namespace mx {
 //   Q4_K / Q5_K at SC = 2048 / 2560:  column c < 8: 6-bit scale of sub-block c, c >= 8: 6-bit min
 //               of sub-block c - 8;  SC + 256 + 16q + 2i: f16 d of row r, SC + 264 + 16q + 2i: f16 dmin
 //   Q6_K at SC = 3072:  column c: int8 scale of 16-value group c;  SC + 256 + 2r: f16 d of row r
+//   IQ4_XS (type 23; the QS plane holds codebook indices) at SC = 2048, 8 columns only, 32 B per row
+//               group: byte SC + 32q + 4c + i = int8 (ls - 32) of row 4q + i, sub-block c (signed at
+//               pack time);  DD = SC + 128: f16 d of row r at DD + 2r.  2208 B per tile: +1.5 % over
+//               the GGUF's 16 x 136
 // ---------------------------------------------------------------------------
 template <int T>
 struct KqTile;
@@ -53,17 +60,54 @@ struct KqTile<14> {
   static constexpr int BYTES = 3360, SC = 3072, BLOCK = 210;
 };
 
+template <>
+struct KqTile<23> {
+  static constexpr int BYTES = 2208, SC = 2048, DD = 2176, BLOCK = 136;
+};
+
 int kq_tile_bytes(int type) {
-  return type == 12 ? KqTile<12>::BYTES : type == 13 ? KqTile<13>::BYTES : type == 14 ? KqTile<14>::BYTES : 0;
+  return type == 12 ? KqTile<12>::BYTES : type == 13 ? KqTile<13>::BYTES : type == 14 ? KqTile<14>::BYTES
+       : type == 23 ? KqTile<23>::BYTES : 0;
 }
 int kq_block_bytes(int type) {
-  return type == 12 ? KqTile<12>::BLOCK : type == 13 ? KqTile<13>::BLOCK : type == 14 ? KqTile<14>::BLOCK : 0;
+  return type == 12 ? KqTile<12>::BLOCK : type == 13 ? KqTile<13>::BLOCK : type == 14 ? KqTile<14>::BLOCK
+       : type == 23 ? KqTile<23>::BLOCK : 0;
+}
+
+// IQ4_XS codebook (ggml kvalues_iq4nl) as four dwords of int8, entry i in byte i&3 of dword i>>2:
+// wave-uniform literals, so they live in SGPRs and never enter the load ring.
+constexpr uint32_t IQ4_KV0 = 0xBFAD9881u, IQ4_KV1 = 0xF6EADDCFu, IQ4_KV2 = 0x26190D01u, IQ4_KV3 = 0x71594535u;
+// Four indices (the low 4 bits of each byte of n; the high 4 bits are ignored) -> their four int8
+// codebook values.  v_perm_b32 picks 4 bytes out of 8 by selector bytes 0..7, so entries 0-7 and
+// 8-15 are one perm each under the selector idx & 7, and a third perm over those two results takes
+// byte i of the upper one where bit 3 of index i is set (selector i + 4 * bit3).  6 VALU per dword
+// (and, 2 perm, shift, and_or, perm); a byte mask with v_bfi would need 7.
+__device__ __forceinline__ uint32_t iq4_kv4(uint32_t n) {
+  const uint32_t s = n & 0x07070707u;
+  const uint32_t lo = __builtin_amdgcn_perm(IQ4_KV1, IQ4_KV0, s), hi = __builtin_amdgcn_perm(IQ4_KV3, IQ4_KV2, s);
+  return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
+}
+// the A-operand dwords of one sub-block from its QS dword: Q4_K / Q5_K / Q6_K's low 4 bits, or
+// IQ4_XS's codebook values (13 VALU per sub-block against Q4_K's 3)
+template <int T>
+__device__ __forceinline__ void kq_nibbles(uint32_t D, uint32_t& lo, uint32_t& hi) {
+  if constexpr (T == 23) {
+    lo = iq4_kv4(D);
+    hi = iq4_kv4(D >> 4);
+  } else {
+    lo = D & 0x0F0F0F0Fu;
+    hi = (D >> 4) & 0x0F0F0F0Fu;
+  }
 }
 
 // The 256 values of one GGUF super-block in k order (Q4_K 0..15, Q5_K 0..31, Q6_K 0..63 before
-// the -32) -- ggml-common.h block_q4_K {d, dmin, scales[12], qs[128]}, block_q5_K {d, dmin,
+// the -32, IQ4_XS codebook indices 0..15) -- ggml-common.h block_q4_K {d, dmin, scales[12], qs[128]}, block_q5_K {d, dmin,
 // scales[12], qh[32], qs[128]}, block_q6_K {ql[128], qh[64], scales[16], d}.
 __device__ __forceinline__ int kq_value(int type, const uint8_t* b, int k) {
+  if (type == 23) {  // the codebook index
+    const int q = b[8 + 16 * (k >> 5) + (k & 15)];
+    return k & 16 ? q >> 4 : q & 15;
+  }
   if (type == 14) {
     const int h = k >> 7, i = (k >> 5) & 3, l = k & 31;
     const int L = b[64 * h + 32 * (i & 1) + l];
@@ -106,8 +150,13 @@ __global__ void pack_kq_kernel(uint8_t* dst, const uint8_t* src, int N, int K, i
         for (int c = 0; c < 4; ++c) *reinterpret_cast<uint32_t*>(tile + 2048 + 16 * lane + 4 * c) = H[c];
     }
     constexpr int SC = KqTile<T>::SC;
-    uint8_t* scr = tile + SC + 64 * (r >> 2) + (r & 3);  // column c at scr[4c]
-    if (T == 14) {
+    // column c at scr[4c]; a row group's columns take 64 B (IQ4_XS: 8 columns, 32 B)
+    uint8_t* scr = tile + SC + (T == 23 ? 32 : 64) * (r >> 2) + (r & 3);
+    if constexpr (T == 23) {
+      for (int j = 0; j < 8; ++j) scr[4 * j] = (uint8_t)(int8_t)(iq4_ls(b, j) - 32);
+      tile[KqTile<23>::DD + 2 * r] = b[0];
+      tile[KqTile<23>::DD + 2 * r + 1] = b[1];
+    } else if (T == 14) {
       for (int g = 0; g < 16; ++g) scr[4 * g] = b[192 + g];
       tile[SC + 256 + 2 * r] = b[208];
       tile[SC + 256 + 2 * r + 1] = b[209];
@@ -141,13 +190,14 @@ int launch_pack_kq(uint8_t* dst, const uint8_t* src, int type, int N, int K, int
     case 12: pack_kq_kernel<12><<<g, 256, 0, s>>>(dst, src, N, K, mode, offset); return 0;
     case 13: pack_kq_kernel<13><<<g, 256, 0, s>>>(dst, src, N, K, mode, offset); return 0;
     case 14: pack_kq_kernel<14><<<g, 256, 0, s>>>(dst, src, N, K, mode, offset); return 0;
+    case 23: pack_kq_kernel<23><<<g, 256, 0, s>>>(dst, src, N, K, mode, offset); return 0;
   }
   return -1;
 }
 
 // Synthetic K-quant blocks (synth.py kq_blocks is the spec): byte i of the tensor's block stream
 // is byte i%8 of the synthetic hash of i/8; the f16 scale fields are then fixed-exponent bit
-// patterns with a random mantissa byte, Q6_K's int8 scales folded into [-24, 23].
+// patterns with a random mantissa byte, Q6_K's int8 scales folded into [-24, 23], IQ4_XS's d = 0x0100 + byte.
 __device__ __forceinline__ uint64_t synth_hash(uint64_t seed, uint64_t tid, uint64_t idx) {
   uint64_t z = seed * 0x9E3779B97F4A7C15ull + tid * 0xD1B54A32D192ED03ull + idx;
   z += 0x9E3779B97F4A7C15ull;
@@ -163,7 +213,11 @@ __global__ void synth_kq_kernel(uint8_t* dst, int type, int bb, size_t nblocks, 
       const uint64_t gi = (uint64_t)b * bb + i;
       p[i] = (uint8_t)(synth_hash(seed, tid, gi >> 3) >> (8 * (gi & 7)));
     }
-    if (type == 14) {
+    if (type == 23) {  // d only (an f16 subnormal, 1.5e-5 .. 3.0e-5): scales and indices straight from the hash
+      const uint32_t d = 0x0100u + p[0];
+      p[0] = (uint8_t)d;
+      p[1] = (uint8_t)(d >> 8);
+    } else if (type == 14) {
       for (int j = 0; j < 16; ++j) p[192 + j] = (uint8_t)(int8_t)((int)(p[192 + j] % 48) - 24);
       const uint32_t d = 0x0500u + p[208];
       p[208] = (uint8_t)d;
@@ -201,7 +255,10 @@ __global__ __launch_bounds__(256) void embed_kq_kernel(float* x, const uint8_t* 
       const int kk = k % 256;
       const int v = kq_value(type, b, kk);
       float y;
-      if (type == 14) {
+      if (type == 23) {  // dequantize_row_iq4_xs: (d * (ls - 32)) * kvalues_iq4nl[index]
+        const float d = (float)__builtin_bit_cast(_Float16, (uint16_t)(b[0] | (b[1] << 8)));
+        y = (d * (float)(iq4_ls(b, kk / 32) - 32)) * (float)iq4_kv(v);
+      } else if (type == 14) {
         const float d = (float)__builtin_bit_cast(_Float16, (uint16_t)(b[208] | (b[209] << 8)));
         y = (d * (float)(int8_t)b[192 + kk / 16]) * (float)(v - 32);
       } else {
@@ -408,7 +465,8 @@ __global__ __launch_bounds__(256) void dequant_kq_kernel(uint16_t* dst, const ui
   uint16_t* out = dst + ((size_t)(tile_begin + tile) * KT + 8 * sb) * 512 + 8 * lane;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    uint32_t lo = D[j] & 0x0F0F0F0Fu, hi = (D[j] >> 4) & 0x0F0F0F0Fu;
+    uint32_t lo, hi;
+    kq_nibbles<T>(D[j], lo, hi);
     if constexpr (T == 13) {
       lo |= ((H[j >> 2] >> ((2 * j) & 7)) & 0x01010101u) << 4;
       hi |= ((H[j >> 2] >> ((2 * j + 1) & 7)) & 0x01010101u) << 4;
@@ -418,7 +476,12 @@ __global__ __launch_bounds__(256) void dequant_kq_kernel(uint16_t* dst, const ui
       hi |= ((H[j >> 1] >> (4 * (j & 1) + 2)) & 0x03030303u) << 4;
     }
     float y[8];
-    if constexpr (T == 14) {
+    if constexpr (T == 23) {  // dequantize_row_iq4_xs: (d * (ls - 32)) * kv
+      const float d = f16b(t + KqTile<23>::DD + 2 * r);
+      const float dl = d * (float)(int8_t)t[SC + 32 * (r >> 2) + 4 * j + (r & 3)];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) y[e] = dl * (float)(int8_t)((e < 4 ? lo : hi) >> (8 * (e & 3)));
+    } else if constexpr (T == 14) {
       const float d = f16b(t + SC + 256 + 2 * r);
       const int sc = (int)(int8_t)t[SC + 64 * (r >> 2) + 4 * (2 * j + (g >> 1)) + (r & 3)];
       const float ds = d * (float)sc;
@@ -451,6 +514,7 @@ int launch_dequant_kq(uint16_t* dst, const void* W, int K, int kq_n, const int* 
       case 12: dequant_kq_kernel<12><<<blocks, 256, 0, s>>>(dst, src, t0, nt, SB); break;
       case 13: dequant_kq_kernel<13><<<blocks, 256, 0, s>>>(dst, src, t0, nt, SB); break;
       case 14: dequant_kq_kernel<14><<<blocks, 256, 0, s>>>(dst, src, t0, nt, SB); break;
+      case 23: dequant_kq_kernel<23><<<blocks, 256, 0, s>>>(dst, src, t0, nt, SB); break;
       default: return -1;
     }
   }
@@ -467,9 +531,9 @@ template <int RT, int NB>
 struct KqFrag {
   u32x4 qs[RT][2];
   u32x4 h[RT];      // Q5_K: dwords 0-1; Q6_K: 0-3
-  u32x4 sc[RT][4];  // Q4_K / Q5_K: [0..1]; Q6_K: [0..3]
-  u32x4 dm[RT];     // Q4_K / Q5_K: f16 d x 4 rows, then f16 dmin x 4 rows; Q6_K: dwords 0-1 = f16 d x 4 rows
-  u32x2 mw[RT];     // Q4_K / Q5_K: mins dwords of sub-blocks g, g+4 (byte lane&3 = this lane's A row), raw
+  u32x4 sc[RT][4];  // Q4_K / Q5_K / IQ4_XS: [0..1]; Q6_K: [0..3]
+  u32x4 dm[RT];     // Q4_K / Q5_K: f16 d x 4 rows, then f16 dmin x 4 rows; Q6_K / IQ4_XS: dwords 0-1 = f16 d x 4 rows
+  u32x2 mw[RT];     // Q4_K / Q5_K (IQ4_XS: no mins, mw and xb stay unloaded): mins dwords of sub-blocks g, g+4 (byte lane&3 = this lane's A row), raw
   u32x4 x[NB][4];
   float dx[NB];
   f32x2 xb[NB];
@@ -489,7 +553,12 @@ __device__ __forceinline__ void kq_load_w(KqFrag<RT, NB>& f, const uint8_t* cons
       f.h[r] = u32x4{hv[0], hv[1], 0u, 0u};
     }
     if constexpr (T == 14) f.h[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(t + 2048) + lane);
-    if constexpr (T == 14) {
+    if constexpr (T == 23) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) f.sc[r][c] = *reinterpret_cast<const u32x4*>(t + SC + 32 * g + 16 * c);
+      const u32x2 dv = *reinterpret_cast<const u32x2*>(t + KqTile<23>::DD + 8 * g);
+      f.dm[r] = u32x4{dv[0], dv[1], 0u, 0u};
+    } else if constexpr (T == 14) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) f.sc[r][c] = *reinterpret_cast<const u32x4*>(t + SC + 64 * g + 16 * c);
       const u32x2 dv = *reinterpret_cast<const u32x2*>(t + SC + 256 + 8 * g);
@@ -516,7 +585,7 @@ __device__ __forceinline__ void kq_load_x(KqFrag<RT, NB>& f, const int8_t* const
 #pragma unroll
     for (int c = 0; c < 4; ++c) f.x[n][c] = *reinterpret_cast<const u32x4*>(Xq[n] + (size_t)sb * 256 + 16 * c);
     f.dx[n] = Xd[n][sb];
-    if constexpr (T != 14) f.xb[n] = *reinterpret_cast<const f32x2*>(Xb[n] + 8 * sb);
+    if constexpr (T != 14 && T != 23) f.xb[n] = *reinterpret_cast<const f32x2*>(Xb[n] + 8 * sb);
   }
 }
 
@@ -618,7 +687,8 @@ __device__ __forceinline__ void kq_compute(f32x4 (&acc)[RT][NB], const KqFrag<RT
       i32x4 Pc[NB], Pc1[NB];
       int sc[4], sc1[4];
       if (j < 8) {
-        uint32_t lo = D[j] & 0x0F0F0F0Fu, hi = (D[j] >> 4) & 0x0F0F0F0Fu;
+        uint32_t lo, hi;
+        kq_nibbles<T>(D[j], lo, hi);
         if constexpr (T == 13) {
           const uint32_t H = f.h[r][j >> 2];
           lo |= ((H >> ((2 * j) & 7)) & 0x01010101u) << 4;
@@ -648,9 +718,9 @@ __device__ __forceinline__ void kq_compute(f32x4 (&acc)[RT][NB], const KqFrag<RT
             Pc1[n] = __builtin_amdgcn_mfma_i32_16x16x32_i8(A1, B, i32x4{0, 0, 0, 0}, 0, 0, 0);
           }
         } else {
-          // 6-bit scales of row 4g+i, sub-block j: byte i of dword j of the row group's 32
+          // 6-bit scales of row 4g+i, sub-block j: byte i of dword j of the row group's 32 (IQ4_XS: int8)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) sc[i] = (int)((scw[j] >> (8 * i)) & 0xFFu);
+          for (int i = 0; i < 4; ++i) sc[i] = T == 23 ? (int)(int8_t)(scw[j] >> (8 * i)) : (int)((scw[j] >> (8 * i)) & 0xFFu);
 #pragma unroll
           for (int n = 0; n < NB; ++n) {
             const u32x4& xc = f.x[n][j >> 1];
@@ -684,7 +754,7 @@ __device__ __forceinline__ void kq_compute(f32x4 (&acc)[RT][NB], const KqFrag<RT
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
       const float dx = f.dx[n];
-      if constexpr (T == 14) {
+      if constexpr (T == 14 || T == 23) {  // no mins term
         const f16x4 d4 = __builtin_bit_cast(f16x4, u32x2{f.dm[r][0], f.dm[r][1]});
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[r][n][i] += ((float)d4[i] * dx) * (float)S[n][i];
@@ -719,12 +789,17 @@ __device__ __forceinline__ void kq_compute(f32x4 (&acc)[RT][NB], const KqFrag<RT
 //                Mn = sum_j m_j * bsum32_j (lane 15; the lane's bsum32 from the Q8_K image),
 //   Q6_K:        S = sum_g sc_g * (P_g - 32 * bsum16_g) over all 16 columns (the -32 of every
 //                6-bit value taken out of the A operand: an exact integer identity),
+//   IQ4_XS:      columns 0-7 give S = sum_j (ls_j - 32) * P_j (lane 7); columns 8-15 carry zeros
+//                (no mins: bs is not read and the mins select and the -d_x sign are compiled out.  The
+//                8-lane sum, the f32 scaling and kq_bd_finish are knowingly kept as Q4_K's: they are
+//                whole-wave instructions that lanes 0-7 need anyway, so lanes 8-15 riding along on
+//                zeros cost no issue slot; a lane-7-only finish would save 4 DPP adds per tile),
 // which are ggml's super-block integers exactly; the f32 scaling is kq_compute's.  The result of a
 // tile ends in lane 0 of each row group (kq_bd_finish), i.e. column 0 of the C layout: the token.
 // ---------------------------------------------------------------------------
 struct KqBdX {
   u32x2 X;    // this lane's 8 q of its column's sub-block (group) slice, zero where it carries none
-  int bs;     // Q4_K / Q5_K lanes c >= 8: bsum32 of sub-block c - 8; Q6_K: bsum16 of group c
+  int bs;     // Q4_K / Q5_K lanes c >= 8: bsum32 of sub-block c - 8; Q6_K: bsum16 of group c; IQ4_XS: unused
   float dx;   // the super-block's d
 };
 
@@ -746,7 +821,8 @@ __device__ __forceinline__ KqBdX kq_bd_x(const int8_t* xq, const float* xd, cons
     const int j = c & 7;
     const u32x2 v = *reinterpret_cast<const u32x2*>(xq + (size_t)sb * 256 + 64 * q + 8 * j);
     r.X = c < 8 ? v : u32x2{0u, 0u};
-    r.bs = (int)xb[(size_t)sb * 8 + 2 * (j & 3) + (j >> 2)];  // exact: an integer sum
+    if constexpr (T == 23) r.bs = 0;  // no mins: columns 8-15 carry nothing
+    else r.bs = (int)xb[(size_t)sb * 8 + 2 * (j & 3) + (j >> 2)];  // exact: an integer sum
   }
   r.dx = xd[sb];
   return r;
@@ -774,7 +850,8 @@ __device__ __forceinline__ KqBdX kq_bd_x_lane(const int8_t* xq, const float* xd,
     const int j = c & 7;
     const u32x2 v = *reinterpret_cast<const u32x2*>(xq + (size_t)sb * 256 + 64 * q + 8 * j);
     r.X = c < 8 ? v : u32x2{0u, 0u};
-    r.bs = (int)xb[(size_t)sb * 8 + 2 * (j & 3) + (j >> 2)];
+    if constexpr (T == 23) r.bs = 0;
+    else r.bs = (int)xb[(size_t)sb * 8 + 2 * (j & 3) + (j >> 2)];
   }
   r.dx = xd[sb];
   return r;
@@ -793,6 +870,12 @@ __device__ __forceinline__ void kq_load_w_bd(KqFrag<1, 1>& f, const uint8_t* t, 
     f.h[0] = u32x4{hv[0], hv[1], 0u, 0u};
   }
   if constexpr (T == 14) f.h[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(t + 2048) + lane);
+  if constexpr (T == 23) {  // 8 scale columns: lanes c >= 8 re-read column c - 8 (their products are zero)
+    f.sc[0][0][0] = *reinterpret_cast<const uint32_t*>(t + SC + 32 * g + 4 * (lane & 7));
+    const u32x2 dv = *reinterpret_cast<const u32x2*>(t + KqTile<23>::DD + 8 * g);
+    f.dm[0] = u32x4{dv[0], dv[1], 0u, 0u};
+    return;
+  }
   f.sc[0][0][0] = *reinterpret_cast<const uint32_t*>(t + SC + 4 * lane);
   const u32x2 dv = *reinterpret_cast<const u32x2*>(t + SC + 256 + (T == 14 ? 8 * g : 16 * g + (lane & 8)));
   f.dm[0] = u32x4{dv[0], dv[1], 0u, 0u};
@@ -827,7 +910,8 @@ __device__ __forceinline__ void kq_compute_bd(f32x4& acc, const KqFrag<1, 1>& f,
   i32x4 C0 = i32x4{0, 0, 0, 0}, C1 = i32x4{0, 0, 0, 0};  // two chains: no MFMA waits on the previous
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    uint32_t lo = D[j] & 0x0F0F0F0Fu, hi = (D[j] >> 4) & 0x0F0F0F0Fu;
+    uint32_t lo, hi;
+    kq_nibbles<T>(D[j], lo, hi);
     if constexpr (T == 13) {
       const uint32_t H = f.h[0][j >> 2];
       lo |= ((H >> ((2 * j) & 7)) & 0x01010101u) << 4;
@@ -850,6 +934,7 @@ __device__ __forceinline__ void kq_compute_bd(f32x4& acc, const KqFrag<1, 1>& f,
   for (int i = 0; i < 4; ++i) {
     const int P = C0[i] + C1[i];
     if constexpr (T == 14) t[i] = __mul24((int)(int8_t)(s >> (8 * i)), P - 32 * x.bs);  // |P - 32 bs| < 2^18
+    else if constexpr (T == 23) t[i] = __mul24((int)(int8_t)(s >> (8 * i)), P);  // |P| < 2^19; columns 8-15: P = 0
     else t[i] = __mul24((int)((s >> (8 * i)) & 0xFFu), c < 8 ? P : x.bs);                // < 2^17
   }
   if constexpr (T == 14) row16_isum4(t);
@@ -857,7 +942,7 @@ __device__ __forceinline__ void kq_compute_bd(f32x4& acc, const KqFrag<1, 1>& f,
   // ggml: (f16(d) * d_x) * S, and for the mins (f16(dmin) * d_x) * Mn subtracted: lanes 8-15 carry
   // dmin and -d_x, so lane 15 accumulates -(dmin * d_x) * Mn exactly
   const f16x4 dd = __builtin_bit_cast(f16x4, u32x2{f.dm[0][0], f.dm[0][1]});
-  const float dxs = (T != 14 && c >= 8) ? -x.dx : x.dx;
+  const float dxs = (T != 14 && T != 23 && c >= 8) ? -x.dx : x.dx;
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] += ((float)dd[i] * dxs) * (float)t[i];
 }
@@ -876,7 +961,8 @@ __device__ __forceinline__ void kq_compute_bd_lds(f32x4& acc, const KqFrag<1, 1>
   i32x4 C0 = i32x4{0, 0, 0, 0}, C1 = i32x4{0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    uint32_t lo = D[j] & 0x0F0F0F0Fu, hi = (D[j] >> 4) & 0x0F0F0F0Fu;
+    uint32_t lo, hi;
+    kq_nibbles<T>(D[j], lo, hi);
     if constexpr (T == 13) {
       const uint32_t H = f.h[0][j >> 2];
       lo |= ((H >> ((2 * j) & 7)) & 0x01010101u) << 4;
@@ -899,12 +985,13 @@ __device__ __forceinline__ void kq_compute_bd_lds(f32x4& acc, const KqFrag<1, 1>
   for (int i = 0; i < 4; ++i) {
     const int P = C0[i] + C1[i];
     if constexpr (T == 14) t[i] = __mul24((int)(int8_t)(s >> (8 * i)), P - 32 * bs);
+    else if constexpr (T == 23) t[i] = __mul24((int)(int8_t)(s >> (8 * i)), P);
     else t[i] = __mul24((int)((s >> (8 * i)) & 0xFFu), c < 8 ? P : bs);
   }
   if constexpr (T == 14) row16_isum4(t);
   else row8_isum4(t);
   const f16x4 dd = __builtin_bit_cast(f16x4, u32x2{f.dm[0][0], f.dm[0][1]});
-  const float dxs = (T != 14 && c >= 8) ? -dx : dx;
+  const float dxs = (T != 14 && T != 23 && c >= 8) ? -dx : dx;
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] += ((float)dd[i] * dxs) * (float)t[i];
 }
@@ -1144,6 +1231,7 @@ __global__ __launch_bounds__(64 * KS) void mkq_kernel(MMArgs a) {
     case 12: mkq_body<12, KS, RT, NB, EPI, U, QL, BD>(a, W, tile0 - t_begin, tile0, red); break;
     case 13: mkq_body<13, KS, RT, NB, EPI, U, QL, BD>(a, W, tile0 - t_begin, tile0, red); break;
     case 14: mkq_body<14, KS, RT, NB, EPI, U, QL, BD>(a, W, tile0 - t_begin, tile0, red); break;
+    case 23: mkq_body<23, KS, RT, NB, EPI, U, QL, BD>(a, W, tile0 - t_begin, tile0, red); break;
   }
 }
 
@@ -1314,6 +1402,7 @@ __global__ __launch_bounds__(64 * KS) void mkq_pers_seg_kernel(MMArgs a) {
     case 12: mkq_pers_body<12, KS, NKW, TPW, 1, EPI, U, true, true, true>(a, Ws, tb); break;
     case 13: mkq_pers_body<13, KS, NKW, TPW, 1, EPI, U, true, true, true>(a, Ws, tb); break;
     case 14: mkq_pers_body<14, KS, NKW, TPW, 1, EPI, U, true, true, true>(a, Ws, tb); break;
+    case 23: mkq_pers_body<23, KS, NKW, TPW, 1, EPI, U, true, true, true>(a, Ws, tb); break;
   }
 }
 
@@ -1381,7 +1470,7 @@ __global__ __launch_bounds__(64 * W) void mkq_bd_tile_kernel(MMArgs a) {
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < SB; ++k) {
-      kq_compute_bd_lds<T>(acc, ring[k % U], im.B[k], im.bs[k][lane], im.d[k], lane);
+      kq_compute_bd_lds<T>(acc, ring[k % U], im.B[k], T == 23 ? 0 : im.bs[k][lane], im.d[k], lane);
       const int fl = i * SB + k + U;
       if (fl < NF) load_w(ring[k % U], fl);
       __builtin_amdgcn_sched_barrier(0);  // the refill issues here, not sunk below the next compute
@@ -1569,10 +1658,12 @@ static int launch_kq_bd_tile(int epi, const MMArgs& a, const MkqPlan& p, hipStre
   if (epi == EPI_SWIGLU)
     return p.t == 12 ? launch_kq_bd_tile_t<12, EPI_SWIGLU>(a, p, s)
          : p.t == 13 ? launch_kq_bd_tile_t<13, EPI_SWIGLU>(a, p, s)
+         : p.t == 23 ? launch_kq_bd_tile_t<23, EPI_SWIGLU>(a, p, s)
                      : launch_kq_bd_tile_t<14, EPI_SWIGLU>(a, p, s);
   if (epi == EPI_F32)
     return p.t == 12 ? launch_kq_bd_tile_t<12, EPI_F32>(a, p, s)
          : p.t == 13 ? launch_kq_bd_tile_t<13, EPI_F32>(a, p, s)
+         : p.t == 23 ? launch_kq_bd_tile_t<23, EPI_F32>(a, p, s)
                      : launch_kq_bd_tile_t<14, EPI_F32>(a, p, s);
   return -1;
 }
@@ -1583,10 +1674,12 @@ static int launch_kq_pers(int epi, const MMArgs& a, const MkqPlan& p, hipStream_
     case EPI_SWIGLU:
       return t == 12 ? launch_kq_pers_ty<12, 1, EPI_SWIGLU>(a, p, s)
            : t == 13 ? launch_kq_pers_ty<13, 1, EPI_SWIGLU>(a, p, s)
+           : t == 23 ? launch_kq_pers_ty<23, 1, EPI_SWIGLU>(a, p, s)
                      : launch_kq_pers_ty<14, 1, EPI_SWIGLU>(a, p, s);
     case EPI_F32:
       return t == 12 ? launch_kq_pers_ty<12, 1, EPI_F32>(a, p, s)
            : t == 13 ? launch_kq_pers_ty<13, 1, EPI_F32>(a, p, s)
+           : t == 23 ? launch_kq_pers_ty<23, 1, EPI_F32>(a, p, s)
                      : launch_kq_pers_ty<14, 1, EPI_F32>(a, p, s);
   }
   return -1;
@@ -1798,7 +1891,7 @@ __device__ __forceinline__ void mkq_wide_body(const MMArgs& a, int tile, const u
 #pragma unroll
       for (int c = 0; c < 4; ++c) f.x[n][c] = *reinterpret_cast<const u32x4*>(&sq[buf][row][64 * g + 16 * c]);
       f.dx[n] = sdx[buf][row];
-      if constexpr (T != 14) f.xb[n] = *reinterpret_cast<const f32x2*>(&ssb[buf][row][2 * g]);
+      if constexpr (T != 14 && T != 23) f.xb[n] = *reinterpret_cast<const f32x2*>(&ssb[buf][row][2 * g]);
     }
     if constexpr (FOLD) kq_compute_fold<NB>(acc, f, lane);
     else kq_compute<T, 1, NB>(acc, f, g);
@@ -1861,6 +1954,7 @@ __global__ __launch_bounds__(64 * W) void mkq_wide_seg_kernel(MMArgs a) {
     case 12: mkq_wide_body<12, W, NB, EPI, 4>(a, tile, Ws, tile - tb); break;
     case 13: mkq_wide_body<13, W, NB, EPI, 4>(a, tile, Ws, tile - tb); break;
     case 14: mkq_wide_body<14, W, NB, EPI, 2>(a, tile, Ws, tile - tb); break;
+    case 23: mkq_wide_body<23, W, NB, EPI, 4>(a, tile, Ws, tile - tb); break;
   }
 }
 
@@ -1878,6 +1972,7 @@ static int launch_kq_wide_epi(const MMArgs& a, const MkqPlan& p, hipStream_t s) 
     constexpr int W = decltype(wc)::value;
     if (t == 12) launch_kq_wide_t<12, W, EPI>(a, ntiles, s);
     else if (t == 13) launch_kq_wide_t<13, W, EPI>(a, ntiles, s);
+    else if (t == 23) launch_kq_wide_t<23, W, EPI>(a, ntiles, s);
     else launch_kq_wide_t<14, W, EPI>(a, ntiles, s);
     return 0;
   };
@@ -1909,6 +2004,7 @@ int launch_mkq_slab(const MMArgs& a, float* slabs, size_t slab_stride, hipStream
   const int t = a.kq_type[0];
   if (t == 12) launch_kq_wide_t<12, 4, EPI_SLAB>(p, ntiles, s, ks);
   else if (t == 13) launch_kq_wide_t<13, 4, EPI_SLAB>(p, ntiles, s, ks);
+  else if (t == 23) launch_kq_wide_t<23, 4, EPI_SLAB>(p, ntiles, s, ks);
   else launch_kq_wide_t<14, 4, EPI_SLAB>(p, ntiles, s, ks);
   return ks;
 }

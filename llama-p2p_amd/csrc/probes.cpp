@@ -131,6 +131,7 @@ size_t glue_block_bytes(int type) {       // bytes of ggml_block_elems(type) val
     case 12: return 144;
     case 13: return 176;
     case 14: return 210;
+    case 23: return 136;
   }
   return 0;
 }
@@ -1017,7 +1018,7 @@ int mx_kq_matmul_probe(int device, const mx_kq_matmul_args* pa) {
   if (mm && (N < TILE_N || N % TILE_N || N > (1 << 18) || (size_t)N * K > ((size_t)1 << 30) || !p.w || !p.out))
     return fail(MX_ERR_ARG, "mx_kq_matmul_probe: N a multiple of 16 (<= 2^18), N*K <= 2^30, w and out required");
   if (mm && !kq_segments_ok(p.kq_n, p.kq_type, p.kq_tile_end, N))
-    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1..3 segments of type 12 / 13 / 14, tile ends increasing to N / 16");
+    return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1..3 segments of type 12 / 13 / 14 / 23, tile ends increasing to N / 16");
   if (mm && epi == EPI_SWIGLU && (N % 32 || p.kq_n != 1))
     return fail(MX_ERR_ARG, "mx_kq_matmul_probe: SWIGLU: one segment, N a multiple of 32");
   if (M < 1 || M > PREFILL_ROWS) return fail(MX_ERR_ARG, "mx_kq_matmul_probe: 1 <= M <= PREFILL_ROWS rows");
@@ -1223,7 +1224,7 @@ int mx_kq_side_probe(int device, const mx_kq_side_args* pa) {
       const int bb = kq_block_bytes(p.type);
       if (!bb || N % TILE_N || p.pack < PACK_ROWS || p.pack > PACK_UP || p.offset < 0 || p.offset % TILE_N ||
           p.offset > (1 << 18) || (p.pack != PACK_ROWS && p.offset))
-        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 0: type 12 / 13 / 14, N % 16, pack 0..2, offset % 16 (pack 0 only)");
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 0: type 12 / 13 / 14 / 23, N % 16, pack 0..2, offset % 16 (pack 0 only)");
       const int rows = p.pack == PACK_ROWS ? N + p.offset : 2 * N;
       const size_t raw = (size_t)N * SB * bb, wb = kq_matrix_bytes(p.type, rows, K);
       const size_t ob = wb + (size_t)PROBE_GUARD_ROWS * kq_tile_bytes(p.type);
@@ -1240,7 +1241,7 @@ int mx_kq_side_probe(int device, const mx_kq_side_args* pa) {
     }
     if (mode == 1) {  // packed K-quant tiles -> packed bf16 tiles
       if (!kq_segments_ok(p.kq_n, p.kq_type, p.kq_tile_end, N))
-        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 1: 1..3 segments of type 12 / 13 / 14, tile ends increasing to N / 16");
+        return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 1: 1..3 segments of type 12 / 13 / 14 / 23, tile ends increasing to N / 16");
       size_t raw = 0, wb = 0, raw_off[3], w_off[3];
       int rows[3], type[3], tile_end[3];
       for (int i = 0; i < p.kq_n; i++) {
@@ -1269,7 +1270,7 @@ int mx_kq_side_probe(int device, const mx_kq_side_args* pa) {
     }
     const int bb = kq_block_bytes(p.type);  // mode 2: GET_ROWS
     if (!bb || !p.ids || M < 1 || M > PREFILL_ROWS)
-      return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 2: type 12 / 13 / 14, ids [M], 1 <= M <= PREFILL_ROWS");
+      return fail(MX_ERR_ARG, "mx_kq_side_probe: mode 2: type 12 / 13 / 14 / 23, ids [M], 1 <= M <= PREFILL_ROWS");
     for (int i = 0; i < M; i++)
       if (p.ids[i] < 0 || p.ids[i] >= N) return fail(MX_ERR_ARG, "mx_kq_side_probe: id out of range");
     float* d_ssq = nullptr;

@@ -1129,8 +1129,8 @@ def q8_embed_probe(blocks, ids, want_ssq: bool = True, device: int = 0):
 
 
 KQ_KIND = {0: "none", 1: "qkv_pers", 2: "bd_tile", 3: "pers", 4: "wide", 5: "mkq"}
-KQ_BLOCK_BYTES = {12: 144, 13: 176, 14: 210}   # GGUF Q4_K / Q5_K / Q6_K bytes per 256 weights
-KQ_TILE_BYTES = {12: 2368, 13: 2880, 14: 3360}  # packed 16-row x 256-k tile (kquant.hip)
+KQ_BLOCK_BYTES = {12: 144, 13: 176, 14: 210, 23: 136}   # GGUF Q4_K / Q5_K / Q6_K / IQ4_XS bytes per 256 weights
+KQ_TILE_BYTES = {12: 2368, 13: 2880, 14: 3360, 23: 2208}  # packed 16-row x 256-k tile (kquant.hip)
 KQ_NO_BD_TILE, KQ_NO_PERS, KQ_NO_WIDE = 1, 2, 4  # kq_matmul_plan flags: the MX_NO_KQ_* switches as if set
 
 

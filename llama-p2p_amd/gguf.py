@@ -28,10 +28,11 @@ _SCALAR = {
 
 # ggml tensor types used here
 GGML_F32, GGML_F16, GGML_Q4_0, GGML_Q8_0, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_BF16 = 0, 1, 2, 8, 12, 13, 14, 30
+GGML_IQ4_XS = 23
 # block (elements, bytes) of the quantised types (ggml-common.h block_q4_0, block_q8_0, block_q4_K,
-# block_q5_K, block_q6_K; QK_K = 256)
+# block_q5_K, block_q6_K, block_iq4_xs; QK_K = 256)
 BLOCKS = {GGML_Q4_0: (32, 18), GGML_Q8_0: (32, 34), GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176),
-          GGML_Q6_K: (256, 210)}
+          GGML_Q6_K: (256, 210), GGML_IQ4_XS: (256, 136)}
 _TYPE_ELEM_BYTES = {GGML_F32: 4, GGML_F16: 2, GGML_BF16: 2}
 QK8_0 = 32          # ggml block_q8_0: f16 d + 32 x int8 (ggml-common.h)
 Q8_0_BLOCK = 34
@@ -180,6 +181,28 @@ def dequantize_q6_k(blocks: np.ndarray, K: int) -> np.ndarray:
     return y.reshape(blocks.shape[:-1] + (K,))
 
 
+KVALUES_IQ4NL = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)
+
+
+def iq4_xs_fields(blocks: np.ndarray):
+    """block_iq4_xs {f16 d; u16 scales_h; u8 scales_l[4]; u8 qs[128]} -> (d f32 [nb], ls int32 [nb][8] (0..63),
+    codebook indices int32 [nb][8][32]): sub-block j = bytes 16j..16j+15, low nibbles then high nibbles."""
+    b = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1, 136)
+    sh = b[:, 2].astype(np.int32) | (b[:, 3].astype(np.int32) << 8)
+    j = np.arange(8)
+    ls = ((b[:, 4 + (j >> 1)].astype(np.int32) >> (4 * (j & 1))) & 15) | (((sh[:, None] >> (2 * j)) & 3) << 4)
+    qs = b[:, 8:136].reshape(-1, 8, 16).astype(np.int32)
+    return _f16(b[:, 0:2]), ls, np.concatenate([qs & 15, qs >> 4], axis=2)
+
+
+def dequantize_iq4_xs(blocks: np.ndarray, K: int) -> np.ndarray:
+    """ggml dequantize_row_iq4_xs: y = (d * (ls - 32)) * kvalues_iq4nl[index], f32, one rounding per product."""
+    d, ls, idx = iq4_xs_fields(blocks)
+    dl = (d[:, None] * (ls - 32).astype(np.float32)).astype(np.float32)
+    y = (dl[:, :, None] * KVALUES_IQ4NL[idx].astype(np.float32)).astype(np.float32)
+    return y.reshape(blocks.shape[:-1] + (K,))
+
+
 def dequantize(ggml_type: int, data: np.ndarray, shape) -> np.ndarray:
     """Any supported tensor -> f32 [rows][K] (GGUF order), as ggml's to_float does."""
     K = shape[-1]
@@ -190,7 +213,7 @@ def dequantize(ggml_type: int, data: np.ndarray, shape) -> np.ndarray:
     if ggml_type == GGML_BF16:
         return (np.asarray(data, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32).reshape(shape)
     fn = {GGML_Q4_0: dequantize_q4_0, GGML_Q8_0: dequantize_q8_0, GGML_Q4_K: dequantize_q4_k,
-          GGML_Q5_K: dequantize_q5_k, GGML_Q6_K: dequantize_q6_k}[ggml_type]
+          GGML_Q5_K: dequantize_q5_k, GGML_Q6_K: dequantize_q6_k, GGML_IQ4_XS: dequantize_iq4_xs}[ggml_type]
     return fn(np.asarray(data), K).reshape(shape)
 
 
@@ -221,6 +244,8 @@ def random_blocks(ggml_type: int, rows: int, K: int, rng, amp: float = 0.03) -> 
     elif ggml_type == GGML_Q6_K:
         b[:, 192:208] = rng.integers(8, 16, size=(nb, 16)).astype(np.int8).view(np.uint8)
         b[:, 208:210] = np.full((nb, 1), amp / (16 * 32), np.float16).view(np.uint8)
+    elif ggml_type == GGML_IQ4_XS:  # every 6-bit scale and index as drawn: |ls - 32| <= 32, |kv| <= 127
+        b[:, 0:2] = np.full((nb, 1), amp / (32 * 127), np.float16).view(np.uint8)
     return b.reshape(rows, K // be * bb)
 
 
@@ -434,8 +459,11 @@ def synth_q8_0_tensor(arr_bf16: np.ndarray) -> np.ndarray:
 
 # per-tensor types of the mixed test files (Q4_0: Q6_K output) -- the weights of these are random
 # valid blocks, not quantisations of the synthetic model.  "q4_k_m" / "q5_k_m" files follow
-# synth.kq_tensor_type (llama.cpp's per-layer recipe) instead of these entries.
+# synth.kq_tensor_type (llama.cpp's per-layer recipe) instead of these entries, and so does "iq4_xs"
+# (ffn_down is Q5_K in the first n_layer // 8 layers only).
 MIXED = {
+    "iq4_xs": {"token_embd": GGML_IQ4_XS, "output": GGML_Q6_K, "attn_v": GGML_Q5_K, "ffn_down": GGML_Q5_K,
+               "*": GGML_IQ4_XS},
     "q4_k_m": {"token_embd": GGML_Q4_K, "output": GGML_Q6_K, "attn_v": GGML_Q6_K, "ffn_down": GGML_Q6_K,
                "*": GGML_Q4_K},
     "q5_k_m": {"token_embd": GGML_Q5_K, "output": GGML_Q6_K, "attn_v": GGML_Q6_K, "ffn_down": GGML_Q6_K,
@@ -460,8 +488,8 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
                          qk_rows: str = "norm", qk_norm=None, key_length: int = None):
     """Write a LLaMA GGUF with the synthetic weights of synth.py: every matrix bf16, or (wtype
     "q8_0") the Q8_0 quantisation of those bf16 matrices; norms f32 either way.  wtype "q4_k_m",
-    "q5_k_m", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
-    (seeded) for the quantised ones and the synthetic values for f16 -- except "q4_k_m" / "q5_k_m", whose
+    "q5_k_m", "iq4_xs", "q4_0", "f16": matrices in those per-tensor types (MIXED), with random valid blocks
+    (seeded) for the quantised ones and the synthetic values for f16 -- except "q4_k_m" / "q5_k_m" / "iq4_xs", whose
     tensors take llama.cpp's per-layer recipe types with synth.kq_tensor's blocks.  dequant_from: a GGUF of the
     same shape whose matrices are written here dequantised (dequantize(), then bf16 RNE) as BF16.
     rope_freqs: a rope_freqs.weight tensor (head_dim/2 f32, Llama-3.1 style); rope_scaling:
@@ -499,7 +527,7 @@ def write_synthetic_gguf(path: str, shape, seed: int = 0, n_ctx_train: int = Non
     w = GGUFWriter(path)
     w.add_string("general.architecture", arch)
     w.add_string("general.name", f"synthetic-{shape.name}-seed{seed}")
-    w.add_uint32("general.file_type", {"bf16": 32, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "q4_0": 2,
+    w.add_uint32("general.file_type", {"bf16": 32, "q8_0": 7, "q4_k_m": 15, "q5_k_m": 17, "iq4_xs": 30, "q4_0": 2,
                                         "q4_0_synth": 2, "f16": 1}[wtype])  # llama_ftype
     w.add_uint32(A + "context_length", n_ctx_train or shape.n_ctx_train)
     w.add_uint32(A + "embedding_length", shape.n_embd)

@@ -173,12 +173,12 @@ def synth_tensors(shape: LlamaShape, seed: int):
 
 
 # ---------------------------------------------------------------------------------------------
-# K-quant synthetic models ("synthetic:<shape>:q4_k_m" / ":q5_k_m"): the per-tensor ggml types of
-# llama.cpp's Q4_K_M / Q5_K_M recipes (llama_tensor_get_type, Oct 2024) with synthetic blocks.
+# K-quant synthetic models ("synthetic:<shape>:q4_k_m" / ":q5_k_m" / ":iq4_xs"): the per-tensor ggml
+# types of llama.cpp's Q4_K_M / Q5_K_M / IQ4_XS recipes (llama_tensor_get_type, Oct 2024) with synthetic blocks.
 # ---------------------------------------------------------------------------------------------
-GGML_Q4_K, GGML_Q5_K, GGML_Q6_K = 12, 13, 14
-KQ_BLOCK_BYTES = {GGML_Q4_K: 144, GGML_Q5_K: 176, GGML_Q6_K: 210}
-KQ_FTYPES = {"q4_k_m": GGML_Q4_K, "q5_k_m": GGML_Q5_K}
+GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_IQ4_XS = 12, 13, 14, 23
+KQ_BLOCK_BYTES = {GGML_Q4_K: 144, GGML_Q5_K: 176, GGML_Q6_K: 210, GGML_IQ4_XS: 136}
+KQ_FTYPES = {"q4_k_m": GGML_Q4_K, "q5_k_m": GGML_Q5_K, "iq4_xs": GGML_IQ4_XS}
 
 
 def use_more_bits(i_layer: int, n_layers: int) -> bool:
@@ -190,10 +190,13 @@ def kq_tensor_type(ftype: str, kind: str, layer: int, n_layer: int) -> int:
     """ggml type of one tensor of a Q4_K_M / Q5_K_M model.  kind: 'token_embd', 'output' or a layer
     kind ('attn_q', 'attn_k', 'attn_v', 'attn_output', 'ffn_gate', 'ffn_up', 'ffn_down').
     output -> Q6_K; attn_v and ffn_down -> Q6_K on use_more_bits layers; attn_v of an 80-layer
-    (70B) Q4_K_M model otherwise Q5_K; everything else the ftype's base type."""
+    (70B) Q4_K_M model otherwise Q5_K; everything else the ftype's base type.
+    IQ4_XS: output Q6_K, attn_v Q5_K, ffn_down Q5_K in the first n_layer // 8 layers, the rest IQ4_XS."""
     base = KQ_FTYPES[ftype]
     if kind == "output":
         return GGML_Q6_K
+    if base == GGML_IQ4_XS:
+        return GGML_Q5_K if kind == "attn_v" or (kind == "ffn_down" and layer < n_layer // 8) else base
     if kind in ("attn_v", "ffn_down") and use_more_bits(layer, n_layer):
         return GGML_Q6_K
     if kind == "attn_v" and n_layer == 80 and base == GGML_Q4_K:
@@ -216,7 +219,11 @@ def kq_blocks(ggml_type: int, nblocks: int, seed: int, tid: int) -> np.ndarray:
     block stream is byte i%8 of hash(seed, tid, i//8); then the f16 scales are set without any float
     conversion: d = 0x0500 + (its first random byte) (7.6e-5 .. 9.5e-5), dmin = 0x1100 (Q4_K) /
     0x1500 (Q5_K) + the next byte, and Q6_K's int8 scales are folded into [-24, 23] (byte % 48 - 24),
-    so weights come out roughly zero-mean with std ~0.02-0.05.  The engine (csrc/kquant.hip
+    so weights come out roughly zero-mean with std ~0.02-0.05.  IQ4_XS sets d alone, a fixed exponent field with
+    a random mantissa byte like the others, but d = 0x0100 + its first byte (exponent field 0: an f16 subnormal,
+    1.5e-5 .. 3.0e-5): a weight is d (ls - 32) kvalue with |ls - 32| up to 32 and |kvalue| up to 127, an integer range
+    of 4064 against the 945 of Q4_K's d sc q (63 x 15), so the 0x0500 of the other types would give weights of std 0.11; with 0x0100
+    the std is 0.029, beside Q4_K's 0.022.  Its 6-bit scales and 4-bit codebook indices are the hash bytes as they are.  The engine (csrc/kquant.hip
     synth_kq_kernel) and the oracle (orc_kq_synth_blocks) compute the same bytes."""
     bb = KQ_BLOCK_BYTES[ggml_type]
     n = nblocks * bb
@@ -226,6 +233,9 @@ def kq_blocks(ggml_type: int, nblocks: int, seed: int, tid: int) -> np.ndarray:
         b[:, 192:208] = ((b[:, 192:208].astype(np.int32) % 48) - 24).astype(np.int8).view(np.uint8)
         d = 0x0500 + b[:, 208].astype(np.uint16)
         b[:, 208], b[:, 209] = (d & 0xFF).astype(np.uint8), (d >> 8).astype(np.uint8)
+    elif ggml_type == GGML_IQ4_XS:
+        d = 0x0100 + b[:, 0].astype(np.uint16)
+        b[:, 0], b[:, 1] = (d & 0xFF).astype(np.uint8), (d >> 8).astype(np.uint8)
     else:
         d = 0x0500 + b[:, 0].astype(np.uint16)
         m = (0x1500 if ggml_type == GGML_Q5_K else 0x1100) + b[:, 1].astype(np.uint16)
