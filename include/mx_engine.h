@@ -74,6 +74,11 @@ typedef struct {
   uint64_t seed;       /* weights seed for "synthetic:<shape>" model paths */
   int32_t handoff_bf16;/* pipeline stage hand-off: x_in / x_out of mx_batch_step, mx_stage_rows and
                           mx_stage_rows_pick are bf16 [rows][n_embd] (1) instead of f32 (0) */
+  int32_t kv_type;     /* ggml type of the KV cache: 1 (F16, the default) or 8 (Q8_0: one block per position and 32
+                          head-dim elements, 34/64 + 1/n_layer of the f16 cache's memory, attention on the int8 MFMA
+                          -- DESIGN.md section 22).  With 8: whole-model engines only (a layer range is MX_ERR_ARG at
+                          creation); mx_engine_set_prefix_sharing(e, 1) and mx_engine_set_host_cache(e, > 0) are
+                          MX_ERR_STATE.  Any other value is MX_ERR_ARG. */
 } mx_opts;
 
 typedef struct {
@@ -387,6 +392,22 @@ int mx_attention_split_plan(int ctx, int32_t* threshold, int32_t* nseg_max, int3
 int mx_attention_long_probe(int device, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
                             const int32_t* pos, const int32_t* slot, int out_f32, const float* q, void* kcache,
                             void* vcache, void* out);
+
+/* The Q8_0 KV cache's kernels through their production launchers, no engine.  Geometry, pos /
+ * slot and scale as mx_attention_probe.  kq / vq: the raw Q8_0 caches, n_slots * n_head_kv regions of ctx_stride *
+ * head_dim int8 (operand lane order) followed by ctx_stride * head_dim / 32 f16 scales each.
+ * mode 0: kv_quant_kernel -- quantises the K / V of rows (slot[i], pos[i]) from the raw tiled f16 caches kcache /
+ *   vcache (only read) into kq / vq, which are filled with 0xFF bytes on the device first and copied back (their
+ *   contents on entry are ignored); rows at pos == n_ctx store nothing; q / out unused.
+ * mode 1: the decode attention on kq / vq (only read) and final q [M][n_head * head_dim] f32, M 1..4096;
+ * mode 2: the same with long rows split over work-groups and merged (section 20's rule), M 1..64;
+ * mode 3: the prefill attention (rows in 16-row blocks as mx_attention_probe's mode 2).
+ * out (modes 1..3): f32 (out_f32 != 0) or bf16 rows of n_head * head_dim, filled with 0xFF bytes before the launch:
+ *   M rows and a guard of 64 more (modes 1, 3) or 64 rows of which M..63 are the guard (mode 2); the guard must come
+ *   back as 0xFF.  kcache / vcache are unused in modes 1..3.  Anything else is MX_ERR_ARG and nothing is launched. */
+int mx_attention_kvq_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                           const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const void* kcache,
+                           const void* vcache, void* kq, void* vq, void* out);
 
 /* Qwen3's per-head q/k RMS_NORM kernels on caller-supplied split-K slabs, no engine.  Geometry,
  * caches, pos / slot, slabs and rope_cs as mx_attention_probe's mode 1 (M <= 64); q_norm / k_norm: f32 [head_dim],

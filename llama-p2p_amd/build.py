@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libmxllama.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MX_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = [("kernels.hip", "hip"), ("attn_split.hip", "hip"), ("kquant.hip", "hip"), ("kvpack.hip", "hip"), ("lora.hip", "hip"),
+SOURCES = [("kernels.hip", "hip"), ("attn_split.hip", "hip"), ("attn_q8.hip", "hip"), ("kquant.hip", "hip"), ("kvpack.hip", "hip"), ("lora.hip", "hip"),
            ("grammar.hip", "hip"), ("engine.cpp", "hip"),
            ("probes.cpp", "hip"), ("gguf.cpp", "c++"), ("grammar.cpp", "c++")]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

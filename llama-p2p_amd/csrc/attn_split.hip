@@ -262,6 +262,26 @@ size_t attn_split_ws_floats(int M, int n_head, int head_dim) {
   return (size_t)M * n_head * ATTN_NSEG_MAX * split_rec(head_dim);
 }
 
+int launch_attention_merge(const AttnArgs& a, const float* ws, hipStream_t s) {
+  if (!ws || a.M < 1 || a.M > MAX_ROWS || a.n_head_kv < 1 || a.n_head % a.n_head_kv) return -1;
+  const int G = a.n_head / a.n_head_kv;
+  const dim3 grid(a.n_head_kv, a.M);
+#define MX_MERGE(D_)                                                                    \
+  switch (G) {                                                                          \
+    case 1: attn_merge_kernel<D_, 1><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 2: attn_merge_kernel<D_, 2><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 4: attn_merge_kernel<D_, 4><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 5: attn_merge_kernel<D_, 5><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 6: attn_merge_kernel<D_, 6><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 7: attn_merge_kernel<D_, 7><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+    case 8: attn_merge_kernel<D_, 8><<<grid, 256, 0, s>>>(a, ws); return 0;             \
+  }
+  if (a.head_dim == 64) { MX_MERGE(64) }
+  if (a.head_dim == 128) { MX_MERGE(128) }
+#undef MX_MERGE
+  return -1;
+}
+
 int launch_attention_split(const AttnArgs& a, float* ws, hipStream_t s) {
   if (a.slabs || !a.q || !ws || a.M < 1 || a.M > MAX_ROWS || a.n_head_kv < 1 || a.n_head % a.n_head_kv) return -1;
   if (a.head_dim == 64) return launch_split_d<64>(a, ws, s);

@@ -347,11 +347,29 @@ struct mx_engine {
   bool is_long(const int32_t* pos, int n) const { return n > 0 && is_long(*std::max_element(pos, pos + n) + 1); }
   // launch_attention, or its split form in a long forward (final q: at.slabs is never set there)
   // -> 0, or -1 with nothing launched (a geometry the split form does not take; init_common admits none)
-  int attend(const AttnArgs& at, hipStream_t s) const {
+  // blocked: the forward's rows form 16-position blocks and the site runs the prefill attention for them.
+  // kv_type 8: the layer's writers stored f16 tiles into the scratch cache (at.kc / at.vc); one
+  // kv_quant launch moves those positions into the layer's Q8_0 cache, which is all the attention then reads
+  int attend(const AttnArgs& at, hipStream_t s, bool blocked = false) const {
+    if (kv_type == 8) {
+      if (at.slabs || launch_kv_quant(at, s)) return -1;
+      return blocked ? launch_attention_q8_prefill(at, s)
+                     : launch_attention_q8(at, long_fwd && at.M <= MAX_ROWS ? attn_ws : nullptr, s);
+    }
+    if (blocked) return launch_attention_prefill(at, s), 0;
     if (long_fwd && at.M <= MAX_ROWS && !at.slabs) return launch_attention_split(at, attn_ws, s);
     launch_attention(at, s);
     return 0;
   }
+  // Q8_0 KV cache (mx_opts.kv_type 8): kq8cache / vq8cache [layer][slot][kv head] regions of kvq_region_bytes, and
+  // kcache / vcache shrunk to one layer of f16 tiles that every layer's QKV writers reuse (kv_off: no layer offset)
+  int kv_type = 1;
+  uint8_t *kq8cache = nullptr, *vq8cache = nullptr;
+  size_t layer_kvq_stride = 0;  // bytes
+  size_t kv_off(int li) const { return kv_type == 8 ? 0 : layer_kv_stride * li; }
+  // the attention may finish q|k|v from split-K slabs itself (the FIN path): never with a Q8_0 cache, whose
+  // kv_quant launch needs the f16 K/V stored first
+  bool fin_ok() const { return rows_distinct && !long_fwd && kv_type != 8; }
   float* gslabs = nullptr;  // split-K partials of small-M prefill GEMMs, [S][M][N] (launch_gemm_split)
   // K-quant model prefill: one layer's four matrices dequantised to packed bf16 for the GEMM path
   uint16_t *kqd_qkv = nullptr, *kqd_o = nullptr, *kqd_gu = nullptr, *kqd_down = nullptr;
@@ -771,11 +789,23 @@ int mx_engine::init_common() {
   // tiles (kernels.hip kv_k_off / kv_v_off)
   slot_stride = (size_t)n_head_kv * ctx_stride * head_dim;
   layer_kv_stride = slot_stride * n_seq_max;
-  if (int rc = alloc((void**)&kcache, layer_kv_stride * nl * sizeof(_Float16))) return rc;
-  if (int rc = alloc((void**)&vcache, layer_kv_stride * nl * sizeof(_Float16))) return rc;
+  // kv_type 8: one layer of f16 tiles as the writers' scratch, and the Q8_0 caches
+  const size_t f16_layers = kv_type == 8 ? 1 : nl;
+  if (int rc = alloc((void**)&kcache, layer_kv_stride * f16_layers * sizeof(_Float16))) return rc;
+  if (int rc = alloc((void**)&vcache, layer_kv_stride * f16_layers * sizeof(_Float16))) return rc;
   if (!poison) {
-    HIPC(hipMemsetAsync(kcache, 0, layer_kv_stride * nl * sizeof(_Float16), stream));
-    HIPC(hipMemsetAsync(vcache, 0, layer_kv_stride * nl * sizeof(_Float16), stream));
+    HIPC(hipMemsetAsync(kcache, 0, layer_kv_stride * f16_layers * sizeof(_Float16), stream));
+    HIPC(hipMemsetAsync(vcache, 0, layer_kv_stride * f16_layers * sizeof(_Float16), stream));
+  }
+  if (kv_type == 8) {
+    if (!has_embed || !has_head) return fail(MX_ERR_ARG, "kv_type 8 (Q8_0 KV cache) needs a whole-model engine");
+    layer_kvq_stride = (size_t)n_seq_max * n_head_kv * kvq_region_bytes(ctx_stride, head_dim);
+    if (int rc = alloc((void**)&kq8cache, layer_kvq_stride * nl)) return rc;
+    if (int rc = alloc((void**)&vq8cache, layer_kvq_stride * nl)) return rc;
+    if (!poison) {
+      HIPC(hipMemsetAsync(kq8cache, 0, layer_kvq_stride * nl, stream));
+      HIPC(hipMemsetAsync(vq8cache, 0, layer_kvq_stride * nl, stream));
+    }
   }
 
   // RoPE table, ggml_rope_cache_init + rope_yarn (ext_factor 0, mscale 1): theta *= powf(base, -2/d)
@@ -1538,7 +1568,7 @@ MMArgs mx_engine::qkv_args(const Layer& L, int li, const Forward& f) const {
   MMArgs a{};
   a.W = L.qkv; a.N = n_embd + 2 * n_embd_kv; a.K = n_embd; a.M = f.M;
   a.out = q; a.ldo = n_embd; a.n_q = n_embd; a.n_kv = n_embd_kv; a.head_dim = head_dim; a.pos = f.pos; a.slot = f.slot;
-  a.rope_cs = rope_cs; a.kc = kcache + layer_kv_stride * li; a.vc = vcache + layer_kv_stride * li; a.n_ctx = n_ctx;
+  a.rope_cs = rope_cs; a.kc = kcache + kv_off(li); a.vc = vcache + kv_off(li); a.n_ctx = n_ctx;
   a.ctx_stride = ctx_stride; a.n_head_kv = n_head_kv; a.slot_stride = slot_stride;
   a.qkv_bias = L.qkv_bias;
   a.q_norm = L.q_norm; a.k_norm = L.k_norm; a.qk_eps = eps;
@@ -1547,10 +1577,13 @@ MMArgs mx_engine::qkv_args(const Layer& L, int li, const Forward& f) const {
 
 AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
   AttnArgs at{};
-  at.q = q; at.kc = kcache + layer_kv_stride * li; at.vc = vcache + layer_kv_stride * li; at.pos = f.pos; at.slot = f.slot;
+  at.q = q; at.kc = kcache + kv_off(li); at.vc = vcache + kv_off(li); at.pos = f.pos; at.slot = f.slot;
   at.ldo = n_embd; at.M = f.M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
   at.n_ctx = n_ctx; at.ctx_stride = ctx_stride; at.slot_stride = slot_stride;
   at.scale = 1.0f / sqrtf((float)head_dim);
+  if (kv_type == 8) {
+    at.kq8 = kq8cache + layer_kvq_stride * li; at.vq8 = vq8cache + layer_kvq_stride * li;
+  }
   at.qkv_bias = layers[li].qkv_bias;  // read by the FIN path alone (at.slabs)
   at.q_norm = layers[li].q_norm; at.k_norm = layers[li].k_norm; at.qk_eps = eps;
   return at;
@@ -1561,7 +1594,7 @@ AttnArgs mx_engine::attn_args(int li, const Forward& f) const {
 // other's new K/V take qkn_finish_kernel first.  a: qkv_args (q buffer, caches).
 void mx_engine::finish_raw_qkv(const MMArgs& a, AttnArgs& at, const float* raw, int nslab, size_t stride,
                                hipStream_t s) const {
-  if (rows_distinct && a.M <= MAX_ROWS && !long_fwd) {  // a long forward attends in the split form: final q
+  if (fin_ok() && a.M <= MAX_ROWS) {  // a long forward attends in the split form, a Q8_0 cache quantises first: final q
     at.slabs = raw; at.nslab = nslab; at.slab_stride = stride; at.rope_cs = rope_cs; at.kc_w = a.kc; at.vc_w = a.vc;
   } else {
     launch_qkv_finish(a, raw, nslab, stride, s);
@@ -1708,7 +1741,7 @@ int mx_engine::enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_c
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
     // rows of one sequence attend to each other's new K/V, and a long forward attends in the split form (§20):
     // finish q|k|v first
-    const bool fin = rows_distinct && !long_fwd;
+    const bool fin = fin_ok();
     if (!fin) {
       launch_qkv_finish(a, slabs, qsplit, slab_stride, s);
       if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
@@ -1719,8 +1752,7 @@ int mx_engine::enqueue_forward_wide(const Forward& f, hipStream_t s, bool full_c
       at.slabs = slabs; at.nslab = qsplit; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
       at.vc_w = a.vc;
     }
-    if (full_chain && rows_blocked) launch_attention_prefill(at, s);
-    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
+    if (attend(at, s, full_chain && rows_blocked)) return fail(MX_ERR_ARG, "attention launch shape");
     if (dbg_hit(s)) return fail(MX_DEBUG_STOPPED, "forward ended at the mx_debug stop");
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.X = attn_out; b.ldx = h; b.M = M;
@@ -1873,7 +1905,7 @@ int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
         if (mm(EPI_F32, r)) return fail(MX_ERR_ARG, fmt + " qkv launch shape");
       }
       finish_raw_qkv(a, at, qs > 0 ? slabs : raw, qs > 0 ? qs : 1, slab_stride, s);
-    } else if (qs > 0 && rows_distinct && !long_fwd) {  // the attention kernel finishes q/k/v from the split-K slabs
+    } else if (qs > 0 && fin_ok()) {  // the attention kernel finishes q/k/v from the split-K slabs
       at.slabs = slabs; at.nslab = qs; at.slab_stride = slab_stride; at.rope_cs = rope_cs; at.kc_w = a.kc;
       at.vc_w = a.vc;
     } else if (qs > 0) {
@@ -1881,8 +1913,7 @@ int mx_engine::enqueue_forward_quant(const Forward& f, hipStream_t s) {
     } else if (mm(EPI_QKV, a)) {
       return fail(MX_ERR_ARG, fmt + " qkv launch shape");
     }
-    if (M > MAX_ROWS && rows_blocked) launch_attention_prefill(at, s);
-    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
+    if (attend(at, s, M > MAX_ROWS && rows_blocked)) return fail(MX_ERR_ARG, "attention launch shape");
     MMArgs b{};
     b.W = L.o; b.N = h; b.K = h; b.M = M; b.out = x; b.ldo = h;
     if (operand(b, L.kq_o, attn_f, h, nullptr)) return fail(MX_ERR_ARG, fmt + " quantise shape");
@@ -1951,8 +1982,7 @@ int mx_engine::enqueue_forward_gemm(const Forward& f, hipStream_t s) {
     if (launch_gemm_split(EPI_QKV, a, gslabs, GSLAB_FLOATS, gemm_split_target, s) < 0) return fail(MX_ERR_ARG, "prefill qkv GEMM shape");
     AttnArgs at = attn_args(li, f);
     at.out = attn_out;
-    if (rows_blocked) launch_attention_prefill(at, s);
-    else if (attend(at, s)) return fail(MX_ERR_ARG, "split attention launch shape");
+    if (attend(at, s, rows_blocked)) return fail(MX_ERR_ARG, "attention launch shape");
     MMArgs b{};
     b.W = Wo; b.N = h; b.K = h; b.X = attn_out; b.ldx = h; b.M = M; b.out = x; b.ldo = h;
     if ((nslab = launch_gemm_split(EPI_RESID, b, gslabs, GSLAB_FLOATS, gemm_split_target, s)) < 0)
@@ -3467,6 +3497,7 @@ void mx_opts_default(mx_opts* o) {
   o->use_graphs = 1;
   o->seed = 0;
   o->handoff_bf16 = 0;
+  o->kv_type = 1;
 }
 
 void mx_sampling_default(mx_sampling* s) {
@@ -3508,6 +3539,9 @@ static int engine_create(const char* model_path, const mx_opts* opts, std::uniqu
   mx_opts_default(&o);
   if (opts) o = *opts;
   if (o.n_ctx < 1 || o.n_seq_max < 1) return fail(MX_ERR_ARG, "n_ctx and n_seq_max must be >= 1");
+  if (o.kv_type != 1 && o.kv_type != 8) return fail(MX_ERR_ARG, "kv_type must be 1 (F16) or 8 (Q8_0)");
+  if (o.kv_type == 8 && o.layer_begin != 0)
+    return fail(MX_ERR_ARG, "kv_type 8 (Q8_0 KV cache) needs a whole-model engine");
   std::unique_ptr<mx_engine> e(new mx_engine());
   if (lora) {
     e->has_lora = true;
@@ -3521,6 +3555,7 @@ static int engine_create(const char* model_path, const mx_opts* opts, std::uniqu
   e->le = o.layer_end;
   e->use_graphs = o.use_graphs != 0 && getenv("MX_NO_GRAPHS") == nullptr;  // rocprofv3 runs set MX_NO_GRAPHS
   e->handoff_bf16 = o.handoff_bf16 != 0;
+  e->kv_type = o.kv_type;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MX_ERR_HIP, "no HIP device visible");
   if (o.device >= 0) HIPC(hipSetDevice(o.device));
@@ -3683,8 +3718,14 @@ int mx_debug(mx_engine* e, int op, long long arg, void* host, size_t bytes) {
         case 3: src = e->attn_out, n = R * e->n_embd * 2; break;
         case 4: src = e->act, n = R * e->n_ff * 2; break;
         case 5: src = e->slabs, n = e->slab_stride * 8 * 4; break;
-        case 6: src = e->kcache, n = e->layer_kv_stride * nl * 2; break;
-        case 7: src = e->vcache, n = e->layer_kv_stride * nl * 2; break;
+        case 6:  // kv_type 8: the Q8_0 caches
+          if (e->kv_type == 8) src = e->kq8cache, n = e->layer_kvq_stride * nl;
+          else src = e->kcache, n = e->layer_kv_stride * nl * 2;
+          break;
+        case 7:
+          if (e->kv_type == 8) src = e->vq8cache, n = e->layer_kvq_stride * nl;
+          else src = e->vcache, n = e->layer_kv_stride * nl * 2;
+          break;
         case 8: src = e->ssq, n = R * (e->n_embd / 16) * 4; break;
         case 9: src = e->d_pos, n = R * 4; break;
         case 10: src = e->d_slot, n = R * 4; break;
@@ -4373,6 +4414,7 @@ int mx_engine_stats(mx_engine* e, mx_stats* out) {
 int mx_engine_set_prefix_sharing(mx_engine* e, int on) {
   if (!e) return fail(MX_ERR_ARG, "null engine");
   if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "prefix sharing needs a whole-model engine");
+  if (on && e->kv_type == 8) return fail(MX_ERR_STATE, "prefix sharing copies f16 KV tiles: not with kv_type 8");
   std::lock_guard<std::mutex> lk(e->mu);
   e->prefix_sharing = on != 0;
   return 0;
@@ -4391,6 +4433,7 @@ int mx_prefix_sharing_stats(mx_engine* e, mx_sharing_stats* out) {
 int mx_engine_set_host_cache(mx_engine* e, uint64_t capacity_bytes) {
   if (!e) return fail(MX_ERR_ARG, "null engine");
   if (!e->has_embed || !e->has_head) return fail(MX_ERR_STATE, "the host cache needs a whole-model engine");
+  if (capacity_bytes && e->kv_type == 8) return fail(MX_ERR_STATE, "the host cache packs f16 KV tiles: not with kv_type 8");
   std::unique_lock<std::mutex> lk(e->mu);
   e->host_cap_req = capacity_bytes;
   if (!e->worker_started) return 0;  // nothing is stored yet: the scheduler takes it up before its first admission
@@ -4472,7 +4515,7 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
         case 0:
           a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.out = e->q; a.ldo = h; a.n_q = h; a.n_kv = kv;
           a.head_dim = e->head_dim; a.pos = e->d_pos; a.slot = e->d_slot; a.rope_cs = e->rope_cs;
-          a.kc = e->kcache + e->layer_kv_stride * li; a.vc = e->vcache + e->layer_kv_stride * li;
+          a.kc = e->kcache + e->kv_off(li); a.vc = e->vcache + e->kv_off(li);
           a.n_ctx = e->n_ctx; a.ctx_stride = e->ctx_stride; a.n_head_kv = e->n_head_kv; a.slot_stride = e->slot_stride;
           per = qb(h + 2 * kv, h);
           ql_operand(e->x, h, L.attn_norm);
@@ -4507,7 +4550,7 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
         case 0:
           a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.out = e->q; a.ldo = h; a.n_q = h; a.n_kv = kv;
           a.head_dim = e->head_dim; a.pos = e->d_pos; a.slot = e->d_slot; a.rope_cs = e->rope_cs;
-          a.kc = e->kcache + e->layer_kv_stride * li; a.vc = e->vcache + e->layer_kv_stride * li;
+          a.kc = e->kcache + e->kv_off(li); a.vc = e->vcache + e->kv_off(li);
           a.n_ctx = e->n_ctx; a.ctx_stride = e->ctx_stride; a.n_head_kv = e->n_head_kv; a.slot_stride = e->slot_stride;
           L.kq_qkv.set(a);
           per = L.kq_qkv.bytes;
@@ -4538,7 +4581,7 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
       case 0:
         a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.X = e->xn; a.ldx = h; a.out = e->q; a.ldo = h; a.n_q = h;
         a.n_kv = kv; a.head_dim = e->head_dim; a.pos = e->d_pos; a.slot = e->d_slot; a.rope_cs = e->rope_cs;
-        a.kc = e->kcache + e->layer_kv_stride * li; a.vc = e->vcache + e->layer_kv_stride * li; a.n_ctx = e->n_ctx;
+        a.kc = e->kcache + e->kv_off(li); a.vc = e->vcache + e->kv_off(li); a.n_ctx = e->n_ctx;
         a.ctx_stride = e->ctx_stride;
         a.n_head_kv = e->n_head_kv; a.slot_stride = e->slot_stride;
         per = (size_t)(h + 2 * kv) * h * 2;
@@ -4564,8 +4607,8 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
         a.W = L.qkv; a.N = h + 2 * kv; a.K = h; a.X = nullptr; a.xf = e->x; a.norm_w = L.attn_norm; a.eps = e->eps;
         a.ssq = e->ssq; a.np = h / 16;
         a.out = e->q; a.ldo = h; a.n_q = h; a.n_kv = kv; a.head_dim = e->head_dim; a.pos = e->d_pos;
-        a.slot = e->d_slot; a.rope_cs = e->rope_cs; a.kc = e->kcache + e->layer_kv_stride * li;
-        a.vc = e->vcache + e->layer_kv_stride * li; a.n_ctx = e->n_ctx; a.ctx_stride = e->ctx_stride;
+        a.slot = e->d_slot; a.rope_cs = e->rope_cs; a.kc = e->kcache + e->kv_off(li);
+        a.vc = e->vcache + e->kv_off(li); a.n_ctx = e->n_ctx; a.ctx_stride = e->ctx_stride;
         a.n_head_kv = e->n_head_kv; a.slot_stride = e->slot_stride;
         per = (size_t)(h + 2 * kv) * h * 2;
         return launch_mm(EPI_QKV, a, s);
@@ -4584,16 +4627,23 @@ int mx_profile_kernel(mx_engine* e, int kind, int M, int iters, double* us, doub
       }
       case 7: {  // attention at the positions set below (ctx = pos + 1)
         AttnArgs at{};
-        at.q = e->q; at.kc = e->kcache + e->layer_kv_stride * li; at.vc = e->vcache + e->layer_kv_stride * li;
+        at.q = e->q; at.kc = e->kcache + e->kv_off(li); at.vc = e->vcache + e->kv_off(li);
         at.pos = e->d_pos; at.slot = e->d_slot; at.out = e->attn_out; at.ldo = h; at.M = M; at.n_head = e->n_head;
         at.n_head_kv = e->n_head_kv; at.head_dim = e->head_dim; at.n_ctx = e->n_ctx; at.ctx_stride = e->ctx_stride;
         at.slot_stride = e->slot_stride; at.scale = 1.0f / sqrtf((float)e->head_dim);
         at.qkv_bias = L.qkv_bias;
         if (prof_fin) {  // the 32-row decode's form: q/k/v still as 4 split-K slabs, finished here
           at.slabs = e->slabs; at.nslab = 4; at.slab_stride = e->slab_stride; at.rope_cs = e->rope_cs;
-          at.kc_w = e->kcache + e->layer_kv_stride * li; at.vc_w = e->vcache + e->layer_kv_stride * li;
+          at.kc_w = e->kcache + e->kv_off(li); at.vc_w = e->vcache + e->kv_off(li);
         }
         per = (size_t)M * (prof_pos + 1) * kv * 2 * 2;
+        if (e->kv_type == 8) {  // the Q8_0 cache's attention (34 bytes per block of 32); MX_PROF_KVQ=1: kv_quant alone
+          if (prof_fin) return -1;
+          at.kq8 = e->kq8cache + e->layer_kvq_stride * li; at.vq8 = e->vq8cache + e->layer_kvq_stride * li;
+          per = per * 34 / 64;
+          if (getenv("MX_PROF_KVQ")) return launch_kv_quant(at, s);
+          return launch_attention_q8(at, M <= MAX_ROWS && e->is_long(prof_pos + 1) ? e->attn_ws : nullptr, s);
+        }
         // as a forward at these positions runs it: the split form (two launches) past the threshold
         if (!prof_fin && M <= MAX_ROWS && e->is_long(prof_pos + 1)) return launch_attention_split(at, e->attn_ws, s);
         launch_attention(at, s);

@@ -68,6 +68,10 @@ struct AttnArgs {
   const float* q_norm;
   const float* k_norm;
   float qk_eps;
+  // Q8_0 KV cache (attn_q8.hip): this layer's K and V caches, [slots][n_head_kv] regions of
+  // kvq_region_bytes each; kc / vc are then the one-layer f16 scratch the writers stored into (launch_kv_quant
+  // reads it, the attention launchers do not)
+  uint8_t *kq8, *vq8;
 };
 
 struct MMArgs {
@@ -207,9 +211,28 @@ size_t attn_split_ws_floats(int M, int n_head, int head_dim);
 // segment gets launch_attention's bits.  Two launches (segments, merge).  -1 and nothing launched for a.slabs,
 // a.M > MAX_ROWS, a head_dim other than 64 / 128 or a GQA group outside {1, 2, 4, 5, 6, 7, 8}.
 int launch_attention_split(const AttnArgs& a, float* ws, hipStream_t s);
+// attn_merge_kernel alone (the second launch of launch_attention_split) on segment partials already in ws: for the
+// Q8_0-cache attention, which writes the same records.  -1 and nothing launched for a geometry it has no instance of.
+int launch_attention_merge(const AttnArgs& a, const float* ws, hipStream_t s);
 // rows in blocks of 16 consecutive positions of one sequence each (prefill chunks): one
 // work-group per (kv head, block), the 16 queries share every K/V chunk
 void launch_attention_prefill(const AttnArgs& a, hipStream_t s);
+// ---- Q8_0 KV cache (attn_q8.hip): per (slot, kv head) region one Q8_0 block per position and 32
+// consecutive head-dim elements -- an int8 plane of ctx_stride * head_dim bytes in MFMA operand lane order, then the
+// f16 block scales: 34 bytes where the f16 cache holds 64.
+__host__ __device__ inline size_t kvq_region_bytes(int ctx_stride, int head_dim) {
+  return (size_t)ctx_stride * head_dim + (size_t)ctx_stride * (head_dim / 32) * 2;
+}
+// Every launcher: -1 and nothing launched unless a.kq8 / a.vq8 are set, head_dim is 64 or 128 and the GQA group is
+// one of {1, 2, 4, 5, 6, 7, 8}.
+// quantise the K / V of rows (a.slot[c], a.pos[c]), c < a.M, from the f16 tiles a.kc / a.vc (geometry a.slot_stride,
+// a.ctx_stride) into a.kq8 / a.vq8 by ggml's quantize_row_q8_0_ref; rows at pos == n_ctx store nothing
+int launch_kv_quant(const AttnArgs& a, hipStream_t s);
+// launch_attention's non-FIN form on the Q8_0 caches (final q in a.q).  ws: the workspace of launch_attention_split
+// -- long rows are split and merged under its rule (a.M <= MAX_ROWS) -- or nullptr: every row in one work-group
+int launch_attention_q8(const AttnArgs& a, float* ws, hipStream_t s);
+// launch_attention_prefill's form on the Q8_0 caches
+int launch_attention_q8_prefill(const AttnArgs& a, hipStream_t s);
 // prefill (> MAX_ROWS rows): MFMA GEMM over packed weights with the same epilogues (N % 256, K % 64)
 bool gemm_supported(int N, int K);
 int launch_gemm(int epi, const MMArgs& a, hipStream_t s);

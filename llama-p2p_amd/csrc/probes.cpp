@@ -455,6 +455,85 @@ int mx_attention_long_probe(int device, int n_head, int n_head_kv, int head_dim,
   return 0;
 }
 
+int mx_attention_kvq_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
+                           const int32_t* pos, const int32_t* slot, int out_f32, const float* q, const void* kcache,
+                           const void* vcache, void* kq, void* vq, void* out) {
+  // every index a kernel forms from these arguments is checked here: nothing is launched on a bad one
+  const char* who = "mx_attention_kvq_probe";
+  if (mode < 0 || mode > 3 || !pos || !slot || !kq || !vq)
+    return fail(MX_ERR_ARG, std::string(who) + ": mode 0..3, non-null pos / slot / Q8 caches");
+  if (mode == 0 ? (!kcache || !vcache) : (!q || !out))
+    return fail(MX_ERR_ARG, std::string(who) + ": mode 0 takes the f16 caches, modes 1..3 q and out");
+  if ((head_dim != 64 && head_dim != 128) || n_head_kv < 1 || n_head < n_head_kv || n_head % n_head_kv != 0 ||
+      n_head > 1024)
+    return fail(MX_ERR_ARG, std::string(who) + ": head_dim 64 or 128, n_head a multiple of n_head_kv");
+  const int G = n_head / n_head_kv;
+  if (G != 1 && G != 2 && (G < 4 || G > 8))
+    return fail(MX_ERR_ARG, std::string(who) + ": n_head / n_head_kv must be 1, 2 or 4..8");
+  if (n_ctx < 1 || n_ctx > (1 << 20) || n_slots < 1 || n_slots > 4096)
+    return fail(MX_ERR_ARG, std::string(who) + ": 1 <= n_ctx <= 2^20, 1 <= n_slots <= 4096");
+  if (M < 1 || M > (mode == 2 ? MAX_ROWS : PREFILL_ROWS))
+    return fail(MX_ERR_ARG, std::string(who) + ": 1 <= M <= 4096 rows (mode 2: 64)");
+  KvGeom g;
+  if (int rc = g.set(who, n_head_kv, head_dim, n_ctx, n_slots)) return rc;
+  for (int i = 0; i < M; i++) {
+    if (slot[i] < 0 || slot[i] >= n_slots) return fail(MX_ERR_ARG, std::string(who) + ": slot out of range");
+    if (pos[i] < 0 || pos[i] > n_ctx) return fail(MX_ERR_ARG, std::string(who) + ": position outside [0, n_ctx]");
+  }
+  if (mode == 3 && !blocked_rows(slot, pos, nullptr, M))
+    return fail(MX_ERR_ARG, std::string(who) + ": mode 3 needs rows in 16-position blocks of one slot each");
+  const size_t nq = (size_t)n_head * head_dim;
+  const size_t q8_bytes = (size_t)n_slots * n_head_kv * kvq_region_bytes(g.ctx_stride, head_dim);
+  if (device >= 0) HIPC(hipSetDevice(device));
+  DevBufs dev;
+  _Float16 *d_k = nullptr, *d_v = nullptr;
+  uint8_t *d_kq = nullptr, *d_vq = nullptr;
+  float *d_q = nullptr, *d_ws = nullptr;
+  int *d_pos = nullptr, *d_slot = nullptr;
+  void* d_out = nullptr;
+  // out: M rows (mode 2: MAX_ROWS) and PROBE_GUARD_ROWS more, all 0xFF; the split workspace 0xFF too
+  const size_t out_rows = (size_t)(mode == 2 ? MAX_ROWS : M + PROBE_GUARD_ROWS);
+  const size_t out_bytes = out_rows * nq * (out_f32 ? 4 : 2);
+  if (!dev.alloc(&d_pos, (size_t)M * 4) || !dev.alloc(&d_slot, (size_t)M * 4) ||
+      (mode == 0 ? !dev.alloc(&d_k, g.cache_elems * 2) || !dev.alloc(&d_v, g.cache_elems * 2) ||
+                       !dev.alloc_ff(&d_kq, q8_bytes) || !dev.alloc_ff(&d_vq, q8_bytes)
+                 : !dev.alloc(&d_kq, q8_bytes) || !dev.alloc(&d_vq, q8_bytes) || !dev.alloc(&d_q, (size_t)M * nq * 4) ||
+                       !dev.alloc_ff(&d_out, out_bytes)) ||
+      (mode == 2 && !dev.alloc_ff(&d_ws, attn_split_ws_floats(M, n_head, head_dim) * 4)))
+    return fail(MX_ERR_HIP, std::string(who) + ": device allocation");
+  HIPC(hipMemcpy(d_pos, pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d_slot, slot, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (mode == 0) {
+    HIPC(hipMemcpy(d_k, kcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_v, vcache, g.cache_elems * 2, hipMemcpyHostToDevice));
+  } else {
+    HIPC(hipMemcpy(d_kq, kq, q8_bytes, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_vq, vq, q8_bytes, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_q, q, (size_t)M * nq * 4, hipMemcpyHostToDevice));
+  }
+  AttnArgs at{};
+  at.q = d_q; at.kc = d_k; at.vc = d_v; at.kq8 = d_kq; at.vq8 = d_vq; at.pos = d_pos; at.slot = d_slot;
+  if (out_f32) at.outf = (float*)d_out;
+  else at.out = (uint16_t*)d_out;
+  at.ldo = (int)nq; at.M = M; at.n_head = n_head; at.n_head_kv = n_head_kv; at.head_dim = head_dim;
+  at.n_ctx = n_ctx; at.ctx_stride = g.ctx_stride; at.slot_stride = g.slot_stride;
+  at.scale = 1.0f / sqrtf((float)head_dim);
+  HIPC(hipDeviceSynchronize());
+  const int rc = mode == 0   ? launch_kv_quant(at, nullptr)
+                 : mode == 3 ? launch_attention_q8_prefill(at, nullptr)
+                             : launch_attention_q8(at, mode == 2 ? d_ws : nullptr, nullptr);
+  if (rc) return fail(MX_ERR_ARG, std::string(who) + ": launch shape");
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  if (mode == 0) {
+    HIPC(hipMemcpy(kq, d_kq, q8_bytes, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(vq, d_vq, q8_bytes, hipMemcpyDeviceToHost));
+  } else {
+    HIPC(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
 int mx_qkn_probe(int device, int mode, int n_head, int n_head_kv, int head_dim, int n_ctx, int n_slots, int M,
                  const int32_t* pos, const int32_t* slot, const float* slabs, int nslab, const float* rope_cs,
                  const float* q_norm, const float* k_norm, float eps, void* kcache, void* vcache, float* q_out,

@@ -32,7 +32,7 @@ EXPORTS = EXPORTS_KQ + [
     "mx_profile_kernel", "mx_sync", "mx_device_count", "mx_engine_stats", "mx_batch_reset", "mx_stage_rows_pick",
     "mx_probe_copy", "mx_probe_read", "mx_debug",
     "mx_submit_lp", "mx_request_logprobs", "mx_forward_logprobs", "mx_logprob_probe",
-    "mx_attention_probe", "mx_attention_split_plan", "mx_attention_long_probe", "mx_qkn_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
+    "mx_attention_probe", "mx_attention_split_plan", "mx_attention_long_probe", "mx_attention_kvq_probe", "mx_qkn_probe", "mx_matmul_probe", "mx_matmul_plan", "mx_norm_probe",
     "mx_submit_spec", "mx_spec_stats", "mx_draft_probe", "mx_accept_probe",
     "mx_submit_embed", "mx_wait_embed", "mx_pool_probe",
     "mx_engine_set_prefix_sharing", "mx_prefix_sharing_stats", "mx_kv_copy_probe",
@@ -65,7 +65,7 @@ class MxError(RuntimeError):
 class MxOpts(ctypes.Structure):
     _fields_ = [("n_ctx", ctypes.c_int32), ("n_seq_max", ctypes.c_int32), ("layer_begin", ctypes.c_int32),
                 ("layer_end", ctypes.c_int32), ("device", ctypes.c_int32), ("use_graphs", ctypes.c_int32),
-                ("seed", ctypes.c_uint64), ("handoff_bf16", ctypes.c_int32)]
+                ("seed", ctypes.c_uint64), ("handoff_bf16", ctypes.c_int32), ("kv_type", ctypes.c_int32)]
 
 
 class MxModelInfo(ctypes.Structure):
@@ -326,6 +326,7 @@ def lib() -> ctypes.CDLL:
                                          vp, vp]
         L.mx_attention_split_plan.argtypes = [i32, P(i32), P(i32), P(i32), P(i32)]
         L.mx_attention_long_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+        L.mx_attention_kvq_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         L.mx_qkn_probe.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.c_float,
                                    vp, vp, vp, vp]
         L.mx_matmul_probe.argtypes = [i32, P(MxMatmulArgs)]
@@ -656,6 +657,55 @@ def attention_long_probe(n_head: int, n_head_kv: int, head_dim: int, n_ctx: int,
                                          slot.ctypes.data, int(bool(out_f32)), qa.ctypes.data, kc.ctypes.data,
                                          vc.ctypes.data, out.ctypes.data))
     guard = out[min(M, 64):].view(np.uint8).copy()
+    out = out[:M]
+    if not out_f32:
+        out = (out.astype(np.uint32) << 16).view(np.float32)
+    return out, guard
+
+
+def kvq_region_bytes(n_ctx: int, head_dim: int) -> int:
+    """Bytes of one (slot, kv head) region of a Q8_0 K or V cache: the int8 plane, then the scales."""
+    ctx_stride = (max(n_ctx, 0) + KV_POS_ALIGN - 1) // KV_POS_ALIGN * KV_POS_ALIGN
+    return ctx_stride * head_dim + ctx_stride * (head_dim // 32) * 2
+
+
+def attention_kvq_probe(mode: int, n_head: int, n_head_kv: int, head_dim: int, n_ctx: int, n_slots: int, pos, slot,
+                        kcache=None, vcache=None, kq=None, vq=None, q=None, out_f32: bool = True, device: int = 0):
+    """The Q8_0 KV cache's launchers on caller-supplied data (no engine; include/mx_engine.h mx_attention_kvq_probe).
+    mode 0: kv_quant_kernel on the raw tiled f16 caches (uint16, as attention_probe's) for rows (slot, pos); returns
+    (kq, vq): the raw Q8_0 caches as uint8 [n_slots * n_head_kv][kvq_region_bytes], 0xFF wherever nothing was
+    stored.  mode 1 / 2 / 3: decode / split + merge / prefill attention on raw Q8_0 caches kq, vq and q [M][n_head *
+    head_dim] f32; returns (out [M][n_head * head_dim] as f32 -- a bf16 output widened exactly --, guard: the raw
+    bytes of the output rows past M, which must all be 0xFF)."""
+    pos, slot = _i32(pos), _i32(slot)
+    M = len(pos)
+    if len(slot) != M:
+        raise ValueError("one slot per row")
+    nreg, reg = max(n_slots, 0) * max(n_head_kv, 0), kvq_region_bytes(n_ctx, max(head_dim, 0))
+    nq = max(n_head * head_dim, 0)
+    if mode == 0:
+        elems = nreg * (reg - reg // 17) if head_dim > 0 else 0
+        kc = np.ascontiguousarray(kcache, dtype=np.uint16).reshape(-1)
+        vc = np.ascontiguousarray(vcache, dtype=np.uint16).reshape(-1)
+        if kc.size != elems or vc.size != elems:
+            raise ValueError(f"caches hold {kc.size} / {vc.size} elements, the geometry needs {elems}")
+        kqa, vqa = np.empty((nreg, reg), np.uint8), np.empty((nreg, reg), np.uint8)
+        _check(lib().mx_attention_kvq_probe(device, 0, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
+                                            slot.ctypes.data, 1, None, kc.ctypes.data, vc.ctypes.data, kqa.ctypes.data,
+                                            vqa.ctypes.data, None))
+        return kqa, vqa
+    kqa = np.ascontiguousarray(kq, dtype=np.uint8).reshape(-1)
+    vqa = np.ascontiguousarray(vq, dtype=np.uint8).reshape(-1)
+    if kqa.size != nreg * reg or vqa.size != nreg * reg:
+        raise ValueError(f"Q8_0 caches hold {kqa.size} / {vqa.size} bytes, the geometry needs {nreg * reg}")
+    qa = np.ascontiguousarray(q, dtype=np.float32)
+    if qa.size != M * nq:
+        raise ValueError("q [M][n_head * head_dim] expected")
+    out = np.empty((64 if mode == 2 else M + 64, nq), dtype=np.float32 if out_f32 else np.uint16)
+    _check(lib().mx_attention_kvq_probe(device, mode, n_head, n_head_kv, head_dim, n_ctx, n_slots, M, pos.ctypes.data,
+                                        slot.ctypes.data, int(bool(out_f32)), qa.ctypes.data, None, None,
+                                        kqa.ctypes.data, vqa.ctypes.data, out.ctypes.data))
+    guard = out[M:].view(np.uint8).copy()
     out = out[:M]
     if not out_f32:
         out = (out.astype(np.uint32) << 16).view(np.float32)
@@ -1706,9 +1756,11 @@ class Engine:
     def __init__(self, model_path: str, n_ctx: int = 512, n_seq_max: int = 64, layer_begin: int = 0,
                  layer_end: int = -1, device: int = -1, use_graphs: bool = True, seed: int = 0,
                  handoff_bf16: bool = False, prefix_sharing: bool = False, host_cache_bytes: int = 0,
-                 lora_path: Optional[str] = None, lora_scale: float = 1.0):
+                 lora_path: Optional[str] = None, lora_scale: float = 1.0, kv_type: int = 1):
         """lora_path: a GGUF LoRA adapter merged into the weights while the model loads, scaled by
-        lora_scale * alpha / r; a quantised base is then dequantised to bf16 (info.weight_type 30)."""
+        lora_scale * alpha / r; a quantised base is then dequantised to bf16 (info.weight_type 30).
+        kv_type: ggml type of the KV cache, 1 (F16) or 8 (Q8_0, DESIGN.md §22: whole-model engines, no prefix
+        sharing and no host cache)."""
         L = lib()
         opts = MxOpts()
         L.mx_opts_default(ctypes.byref(opts))
@@ -1716,6 +1768,7 @@ class Engine:
         opts.layer_begin, opts.layer_end, opts.device = layer_begin, layer_end, device
         opts.use_graphs, opts.seed = int(use_graphs), seed
         opts.handoff_bf16 = int(handoff_bf16)
+        opts.kv_type = self.kv_type = int(kv_type)
         self.handoff_bf16 = bool(handoff_bf16)
         h = ctypes.c_void_p()
         if lora_path is None:
@@ -1730,6 +1783,8 @@ class Engine:
         self.n_vocab = info.n_vocab
         self.n_embd = info.n_embd
         self.n_ctx = info.n_ctx
+        if self.kv_type == 8:  # the slot-to-slot copy and the host tier move f16 tiles
+            self.supports_prefix_sharing = self.supports_host_cache = False
         if prefix_sharing:
             self.set_prefix_sharing(True)
         if host_cache_bytes:

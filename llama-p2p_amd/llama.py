@@ -54,8 +54,13 @@ class Llama:
                  lora_base: Optional[str] = None, lora_scale: float = 1.0, lora_path: Optional[str] = None,
                  verbose: bool = True, n_seq_max: int = 64, device: int = -1, synthetic_seed: int = 0,
                  draft_model: Optional[LlamaDraftModel] = None, embedding: bool = False,
-                 pooling_type: int = LLAMA_POOLING_TYPE_UNSPECIFIED, **kwargs: Any):
-        """lora_path: a GGUF LoRA adapter (convert_lora_to_gguf.py), scaled by lora_scale * alpha / r.  It is
+                 pooling_type: int = LLAMA_POOLING_TYPE_UNSPECIFIED, type_k: Optional[int] = None,
+                 type_v: Optional[int] = None, flash_attn: bool = False, **kwargs: Any):
+        """type_k / type_v: ggml type of the KV cache, llama-cpp-python's knob: None or 1 (GGML_TYPE_F16) is the f16
+        cache; 8 for both (GGML_TYPE_Q8_0) keeps K and V as Q8_0 blocks at 34/64 + 1/n_layer of the memory, with
+        attention on the int8 MFMA -- set_cache is then not available.  Anything else raises
+        NotImplementedError.  flash_attn is accepted and ignored: attention here is always fused.
+        lora_path: a GGUF LoRA adapter (convert_lora_to_gguf.py), scaled by lora_scale * alpha / r.  It is
         merged into the weights on the device while the model loads: the model served is the one
         a BF16 file of the merged weights would give, and a quantised base is dequantised to bf16 for it.
         lora_base is accepted and ignored: it named an f16 base for llama.cpp's old merge of an adapter into a
@@ -63,6 +68,7 @@ class Llama:
         # n_gpu_layers / n_threads are accepted for signature compatibility: the whole model always runs on
         # the GPU.  n_batch only bounds the tokens of one embed() input, as in llama-cpp-python.
         self._check_pooling_type(pooling_type)
+        kv_type = self._check_kv_type(type_k, type_v)
         self.model_path = model_path
         self.verbose = verbose
         self._seed = seed
@@ -79,7 +85,8 @@ class Llama:
         if lora_path:
             try:
                 self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
-                                              seed=synthetic_seed, lora_path=lora_path, lora_scale=lora_scale)
+                                              seed=synthetic_seed, lora_path=lora_path, lora_scale=lora_scale,
+                                              kv_type=kv_type)
             except _engine.MxError as err:
                 if err.code not in (_engine.MX_ERR_MODEL, _engine.MX_ERR_ARG):
                     raise
@@ -88,13 +95,22 @@ class Llama:
                 self._print_lora_line(model_path)
         else:
             self._engine = _engine.Engine(model_path, n_ctx=n_ctx, n_seq_max=n_seq_max, device=device,
-                                          seed=synthetic_seed)
+                                          seed=synthetic_seed, kv_type=kv_type)
         self._n_ctx = n_ctx
         self.cache = None
         self.n_batch = min(n_batch, n_ctx)
         self._embedding = bool(embedding)
         self._init_tokenizer(model_path, self._engine.info.n_vocab)
         self._pooling_type = self._resolve_pooling_type(pooling_type)
+
+    @staticmethod
+    def _check_kv_type(type_k: Optional[int], type_v: Optional[int]) -> int:
+        """The engine's kv_type for Llama(type_k=, type_v=): 1 (F16) or 8 (Q8_0), K and V alike."""
+        tk, tv = (1 if t is None else t for t in (type_k, type_v))
+        if tk != tv or tk not in (1, 8):
+            raise NotImplementedError(f"type_k={type_k}, type_v={type_v}: the KV cache is F16 (type_k = type_v = None "
+                                      "or 1) or Q8_0 (type_k = type_v = 8)")
+        return int(tk)
 
     def _print_lora_line(self, model_path: str):
         """One line on stderr: how many tensors the adapter was merged into and, for a quantised base, that the
